@@ -13,7 +13,17 @@ flight per GPU (livo_iekf_update_batch_submit / _wait over two alternating
 sets of scans): while the host collects one batch the device already runs the
 next.  `sync_value` is the same steps one synchronous batch at a time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it makes the inputs,
+builds the map, uploads the scan pool, warms up, times the K pipelined steps
+and prints the result line.  --dump-outputs DIR then writes what the last timed
+step returned to its caller (the updated states and the iteration statistics
+of its --batch scans) as DIR/<name>.npy, float64; the inputs are seeded, so
+two builds given the same arguments can be compared array for array.  --full
+adds everything else described below: the extra fields, the side legs and the
+CPU baseline (--legs, --cpu-seconds and --pmc choose among them and mean
+nothing without it).
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK set) this
 process is one rank; otherwise it starts N rank processes itself (before any
@@ -21,7 +31,7 @@ GPU call), relays rank 0's JSON line and fails if any rank fails.  Every rank
 processes its own scans ("weak" scaling); the ranks all-reduce only
 throughput counters (RCCL; gloo when ranks share a GPU in a rehearsal).
 
-Extra fields: `roofline` of the dominant kernel (the batch's first-evaluation
+Extra fields (--full): `roofline` of the dominant kernel (the batch's first-evaluation
 k-NN: HIP events on the library's streams, bytes the cell-grid search reads
 and writes, counted by the kernel; `traffic` from rocprofv3 PMC passes run by
 this bench in child processes), the drop-in regime (one scan at a time,
@@ -74,6 +84,11 @@ def parse():
     ap.add_argument("--scan-points", type=int, default=100_000)
     ap.add_argument("--map-points", type=int, default=1_000_000)
     ap.add_argument("--max-iter", type=int, default=4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (states and iteration statistics) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the extra headline fields, the side legs (--legs), the CPU baseline (--cpu-seconds) "
+                         "and the PMC passes (--pmc); off: the headline only")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget (0: skip)")
     ap.add_argument("--legs", default="all", help="comma list: headline,latency,config5,ikfom,ivox,ikd,vio (all)")
     ap.add_argument("--pmc", default="auto", choices=("auto", "off"),
@@ -153,6 +168,10 @@ def ref_calibration() -> dict:
 
 
 POOL_CAP = 1024  # most distinct scans a rank keeps resident (~17 MB of HBM each at 100k points)
+# A plain run keeps fewer: making a 100k-point scan costs the host ~0.7 core-seconds, so a pool of
+# POOL_CAP scans would take longer to make than all the rest of the run.  256 scans (4 GB) still
+# exceed every cache many times over, and the default run (20 steps + 5 warm-up) stays below it.
+POOL_CAP_PLAIN = 256
 
 
 def gen_scans(n_points: int, seeds, workers: int):
@@ -225,6 +244,34 @@ def pmc_traffic(a, kernel_key: str):
     return res
 
 
+# ---------------------------------------------------------------- outputs ----
+def dump_outputs(out_dir: str, states, stats, n: int) -> None:
+    """What livo_iekf_update_batch_wait handed back for one batch of n scans, one float64
+    array per field as out_dir/<name>.npy: the updated states (rot, pos, vel, bias_g,
+    bias_a, gravity, cov) and the iteration statistics (iterations, knn_passes,
+    converged, rematch_num; effct_feat_num, solution and res_mean per evaluation, zero
+    beyond a scan's last evaluation, where livo_amd.stats_from_c cuts them off)."""
+    import livo_amd
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for k, shape in (("rot", (3, 3)), ("pos", (3,)), ("vel", (3,)), ("bias_g", (3,)), ("bias_a", (3,)),
+                     ("gravity", (3,)), ("cov", (18, 18))):
+        arrays[k] = np.array([getattr(states[b], k)[:] for b in range(n)], np.float64).reshape((n,) + shape)
+    for k in ("iterations", "knn_passes", "converged", "rematch_num"):
+        arrays[k] = np.array([getattr(stats[b], k) for b in range(n)], np.float64)
+    E = livo_amd.MAX_EVALS
+    arrays["effct_feat_num"] = np.zeros((n, E))
+    arrays["solution"] = np.zeros((n, E, 18))
+    arrays["res_mean"] = np.zeros((n, E))
+    for b in range(n):
+        for e in range(min(stats[b].iterations, E)):
+            arrays["effct_feat_num"][b, e] = stats[b].effct_feat_num[e]
+            arrays["solution"][b, e] = stats[b].solution[e][:]
+            arrays["res_mean"][b, e] = stats[b].res_mean[e]
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 # ------------------------------------------------------------------ main ----
 def main():
     a = parse()
@@ -236,7 +283,8 @@ def main():
         sys.stderr.write(f"note: --gpus {a.gpus} but WORLD_SIZE {world}; {world} ranks run\n")
     legs = set(a.legs.split(",")) if a.legs != "all" else {"headline", "latency", "config5", "ikfom", "ivox", "ikd",
                                                            "vio"}
-    if rank > 0:
+    full = a.full
+    if rank > 0 or not full:
         legs = {"headline"}  # the side legs are rank 0's report: other ranks only run the headline
     import livo_amd
     from livo_amd import farm, synth
@@ -246,9 +294,10 @@ def main():
     # A pool of distinct scans (config 4's independent scans, seeds rank * pool
     # + j): every batch of the warm-up and of the timed region takes the next
     # a.batch of them, so no scan repeats within the timed region (up to
-    # POOL_CAP scans; beyond that the pool rotates, and the line says so)
+    # POOL_CAP scans, POOL_CAP_PLAIN without --full; beyond that the pool
+    # rotates, and the line says so)
     m = synth.cached_map(a.map_points)
-    n_batches = max(1, min(POOL_CAP // a.batch, a.steps + max(a.warmup, 2)))
+    n_batches = max(1, min((POOL_CAP if full else POOL_CAP_PLAIN) // a.batch, a.steps + max(a.warmup, 2)))
     pool_n = n_batches * a.batch
     pool_seeds = [rank * pool_n + j for j in range(pool_n)]
     t = time.time()
@@ -262,7 +311,7 @@ def main():
     fused = kind == "tile" and os.environ.get("LIVO_FUSED", "1") != "0"
     unit_kernel = {"leaf": "k_knn_leaf<false", "grid": "k_knn_grid<false, false>"}.get(
         kind, "k_iekf_eval<true>" if fused else "k_knn_grid<false, true>")
-    pmc = pmc_traffic(a, unit_kernel) if (rank == 0 and world == 1) else None
+    pmc = pmc_traffic(a, unit_kernel) if (full and rank == 0 and world == 1) else None
 
     import torch
     import torch.distributed as dist
@@ -302,7 +351,7 @@ def main():
     # V_ref: nodes the reference traversal visits for the first search of the
     # first batch (the reference-order pass k_knn_pass, outside the timed
     # region): the reference-equivalent pricing of SURVEY.md §8d, per query
-    v_ref = sum(ctx.h_share(sid, s, search_en=True)["visits"] for sid, s in zip(sids, st0))
+    v_ref = sum(ctx.h_share(sid, s, search_en=True)["visits"] for sid, s in zip(sids, st0)) if full else 0
     vq_ref = v_ref / max(sum(len(s) for s in scans), 1)
     batches = []  # (scan ids, initial states) of each batch of the pool
     for b in range(n_batches):
@@ -314,7 +363,7 @@ def main():
     nbytes = C.sizeof(init)
     # the round-3 mode beside it: the first 8 scans every step (two uploads, since
     # a scan is in one batch in flight at a time)
-    fixed = [(sids, init), ([ctx.scan_upload(s) for s in scans], init)]
+    fixed = [(sids, init), ([ctx.scan_upload(s) for s in scans], init)] if full else None
 
     def step(b=0):
         """One synchronous batch (livo_iekf_update_batch) of pool batch b: the profiled legs."""
@@ -364,156 +413,134 @@ def main():
     barrier()
     sync()
     elapsed = time.perf_counter() - t0
-    # the fixed-8 rate of round 3 (the same 8 scans every step), untimed for value
-    fixed_counters = farm.Counters()
-    pipeline(2, 0, sets=fixed)
-    sync()
-    t0f = time.perf_counter()
-    pipeline(a.steps, 0, fixed_counters, sets=fixed)
-    sync()
-    elapsed_fixed = time.perf_counter() - t0f
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *outs[(a.steps - 1) % 2], a.batch)
+    if full:
+        # the fixed-8 rate of round 3 (the same 8 scans every step), untimed for value
+        fixed_counters = farm.Counters()
+        pipeline(2, 0, sets=fixed)
+        sync()
+        t0f = time.perf_counter()
+        pipeline(a.steps, 0, fixed_counters, sets=fixed)
+        sync()
+        elapsed_fixed = time.perf_counter() - t0f
 
-    # The farm with each scan's upload inside the clock: every batch's scans go
-    # from host arrays (four distinct batches of the pool, cycled) through ONE
-    # livo_scan_upload_batch_async two batches ahead of their submit, overlapping
-    # the batches in flight, and are released once collected; untimed for value.
-    # value_with_upload: the host arrays page-locked once (livo_host_register, as a
-    # driver filling pinned buffers would), so the copy engine reads them directly;
-    # value_with_upload_pageable: ordinary arrays through the pinned staging ring.
-    # (an A/B build from before livo_scan_upload_batch_async skips these legs)
-    n_up = min(4, len(pool_scans) // a.batch) if hasattr(ctx._L, "livo_scan_upload_batch_async") else 0
-    up_sets = [([np.ascontiguousarray(x[:, :3], np.float32) for x in pool_scans[b * a.batch:(b + 1) * a.batch]],
-                batches[b][1]) for b in range(n_up)]
+        # The farm with each scan's upload inside the clock: every batch's scans go
+        # from host arrays (four distinct batches of the pool, cycled) through ONE
+        # livo_scan_upload_batch_async two batches ahead of their submit, overlapping
+        # the batches in flight, and are released once collected; untimed for value.
+        # value_with_upload: the host arrays page-locked once (livo_host_register, as a
+        # driver filling pinned buffers would), so the copy engine reads them directly;
+        # value_with_upload_pageable: ordinary arrays through the pinned staging ring.
+        # (an A/B build from before livo_scan_upload_batch_async skips these legs)
+        n_up = min(4, len(pool_scans) // a.batch) if hasattr(ctx._L, "livo_scan_upload_batch_async") else 0
+        up_sets = [([np.ascontiguousarray(x[:, :3], np.float32) for x in pool_scans[b * a.batch:(b + 1) * a.batch]],
+                    batches[b][1]) for b in range(n_up)]
 
-    def pipeline_upload(nsteps, counters=None):
-        pending, ahead, nxt = [], [], 0
-        for k in range(nsteps):
-            while len(ahead) < 2 and nxt < nsteps:
-                ahead.append((nxt, ctx.scan_upload_batch_async(up_sets[nxt % n_up][0])))
-                nxt += 1
-            if len(pending) == livo_amd.MAX_INFLIGHT:
-                t, j, ids = pending.pop(0)
+        def pipeline_upload(nsteps, counters=None):
+            pending, ahead, nxt = [], [], 0
+            for k in range(nsteps):
+                while len(ahead) < 2 and nxt < nsteps:
+                    ahead.append((nxt, ctx.scan_upload_batch_async(up_sets[nxt % n_up][0])))
+                    nxt += 1
+                if len(pending) == livo_amd.MAX_INFLIGHT:
+                    t, j, ids = pending.pop(0)
+                    _, st = ctx.iekf_update_batch_wait(t, a.batch, *outs[j])
+                    for sid in ids:
+                        ctx.scan_release(sid)
+                    if counters is not None:
+                        counters.add_stats(st)
+                b, ids = ahead.pop(0)
+                j = k % 2
+                pending.append((ctx.iekf_update_batch_submit(ids, up_sets[b % n_up][1]), j, ids))
+            for t, j, ids in pending:
                 _, st = ctx.iekf_update_batch_wait(t, a.batch, *outs[j])
                 for sid in ids:
                     ctx.scan_release(sid)
                 if counters is not None:
                     counters.add_stats(st)
-            b, ids = ahead.pop(0)
-            j = k % 2
-            pending.append((ctx.iekf_update_batch_submit(ids, up_sets[b % n_up][1]), j, ids))
-        for t, j, ids in pending:
-            _, st = ctx.iekf_update_batch_wait(t, a.batch, *outs[j])
-            for sid in ids:
-                ctx.scan_release(sid)
-            if counters is not None:
-                counters.add_stats(st)
 
-    def upload_leg():
-        c = farm.Counters()
-        pipeline_upload(4)
+        def upload_leg():
+            c = farm.Counters()
+            pipeline_upload(4)
+            sync()
+            t0u = time.perf_counter()
+            pipeline_upload(a.steps, c)
+            sync()
+            return c, time.perf_counter() - t0u
+
+        upload_counters = upload_counters_pg = farm.Counters()
+        elapsed_up = elapsed_up_pg = 0.0
+        if n_up >= 1:
+            for x, _ in up_sets:
+                for arr in x:
+                    ctx.host_register(arr)
+            upload_counters, elapsed_up = upload_leg()
+            for x, _ in up_sets:
+                for arr in x:
+                    ctx.host_unregister(arr)
+            upload_counters_pg, elapsed_up_pg = upload_leg()
+
+        # The same steps one synchronous batch at a time (the host waits for each
+        # batch before the next is queued), untimed for the headline and reported
+        # as sync_value; level-1 profiling: HIP events around the batch's
+        # first-evaluation launch only (the roofline unit).  The per-stage
+        # breakdown (level 2) costs ~10% and is taken from extra steps below.
+        ctx.set_profiling(1)
+        knn_ms = 0.0
+        knn_launches = knn_visits = knn_points = knn_queries = replays = 0
         sync()
-        t0u = time.perf_counter()
-        pipeline_upload(a.steps, c)
+        t0s = time.perf_counter()
+        for k in range(a.steps):
+            step(k)
+            tm = ctx.last_timings()
+            knn_ms += tm["knn_ms"]
+            knn_launches += tm["knn_launches"]
+            knn_visits += tm["knn_visits"]
+            knn_points += tm["knn_points"]
+            knn_queries += tm["knn_queries"]
         sync()
-        return c, time.perf_counter() - t0u
-
-    upload_counters = upload_counters_pg = farm.Counters()
-    elapsed_up = elapsed_up_pg = 0.0
-    if n_up >= 1:
-        for x, _ in up_sets:
-            for arr in x:
-                ctx.host_register(arr)
-        upload_counters, elapsed_up = upload_leg()
-        for x, _ in up_sets:
-            for arr in x:
-                ctx.host_unregister(arr)
-        upload_counters_pg, elapsed_up_pg = upload_leg()
-
-    # The same steps one synchronous batch at a time (the host waits for each
-    # batch before the next is queued), untimed for the headline and reported
-    # as sync_value; level-1 profiling: HIP events around the batch's
-    # first-evaluation launch only (the roofline unit).  The per-stage
-    # breakdown (level 2) costs ~10% and is taken from extra steps below.
-    ctx.set_profiling(1)
-    knn_ms = 0.0
-    knn_launches = knn_visits = knn_points = knn_queries = replays = 0
-    sync()
-    t0s = time.perf_counter()
-    for k in range(a.steps):
-        step(k)
-        tm = ctx.last_timings()
-        knn_ms += tm["knn_ms"]
-        knn_launches += tm["knn_launches"]
-        knn_visits += tm["knn_visits"]
-        knn_points += tm["knn_points"]
-        knn_queries += tm["knn_queries"]
-    sync()
-    elapsed_sync = time.perf_counter() - t0s
-    # per-stage device time (summed over the concurrent stream groups), untimed
-    ctx.set_profiling(2)
-    n_prof = 10
-    t_first = t_rematch = t_plane = t_batch = t_gap = 0.0
-    n_gap = n_remevals = 0
-    replays = 0
-    t0p = time.perf_counter()
-    for k in range(n_prof):
-        step(k)
-        tm = ctx.last_timings()
-        t_first += tm["knn_ms"]
-        t_rematch += tm["rematch_knn_ms"]
-        t_plane += tm["plane_ms"]
-        t_batch += tm["batch_ms"]
-        if tm["gap_ms"] > 0:
-            t_gap += tm["gap_ms"]
-            n_gap += 1
-        n_remevals += sum(1 for e, sc in enumerate(tm["eval_searched"]) if e > 0 and sc > 0)
-        replays += tm["knn_replays"]
-    wall_prof = (time.perf_counter() - t0p) / n_prof
-    ctx.set_profiling(0)
-    counters.knn_visits, counters.knn_queries = knn_visits, knn_queries
+        elapsed_sync = time.perf_counter() - t0s
+        # per-stage device time (summed over the concurrent stream groups), untimed
+        ctx.set_profiling(2)
+        n_prof = 10
+        t_first = t_rematch = t_plane = t_batch = t_gap = 0.0
+        n_gap = n_remevals = 0
+        replays = 0
+        t0p = time.perf_counter()
+        for k in range(n_prof):
+            step(k)
+            tm = ctx.last_timings()
+            t_first += tm["knn_ms"]
+            t_rematch += tm["rematch_knn_ms"]
+            t_plane += tm["plane_ms"]
+            t_batch += tm["batch_ms"]
+            if tm["gap_ms"] > 0:
+                t_gap += tm["gap_ms"]
+                n_gap += 1
+            n_remevals += sum(1 for e, sc in enumerate(tm["eval_searched"]) if e > 0 and sc > 0)
+            replays += tm["knn_replays"]
+        wall_prof = (time.perf_counter() - t0p) / n_prof
+        ctx.set_profiling(0)
+        counters.knn_visits, counters.knn_queries = knn_visits, knn_queries
     elapsed_max = farm.allreduce_max(elapsed, coll_dev)
-    elapsed_sync_max = farm.allreduce_max(elapsed_sync, coll_dev)
+    if full:
+        elapsed_sync_max = farm.allreduce_max(elapsed_sync, coll_dev)
     total = farm.allreduce_counters(counters, coll_dev)
 
-    # roofline of the dominant kernel (rank-local): the first-evaluation k-NN of
-    # one batch (4 concurrent stream-group dispatches + their replays)
-    L = max(knn_launches, 1)
-    launch_ms = knn_ms / L
-    q_launch = knn_queries / L
-    alg_bytes = (knn_visits / L) * B_SLOT + (knn_points / L) * B_POINT + q_launch * B_QUERY_IO
-    achieved = alg_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
-    ref_equiv = (vq_ref * q_launch * B_NODE + q_launch * B_QUERY_REF) / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
+    if full:
+        # roofline of the dominant kernel (rank-local): the first-evaluation k-NN of
+        # one batch (4 concurrent stream-group dispatches + their replays)
+        L = max(knn_launches, 1)
+        launch_ms = knn_ms / L
+        q_launch = knn_queries / L
+        alg_bytes = (knn_visits / L) * B_SLOT + (knn_points / L) * B_POINT + q_launch * B_QUERY_IO
+        achieved = alg_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
+        ref_equiv = (vq_ref * q_launch * B_NODE + q_launch * B_QUERY_REF) / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
 
     result = None
     if rank == 0:
         value = total.scans / elapsed_max
-        roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": round(pmc["hbm_bytes_per_launch"]) if pmc else None,
-                "kernel": (f"first evaluation of the batch: {min(stream_groups(a.batch * a.scan_points), a.batch)} {unit_kernel} dispatch(es) (one "
-                           "per stream group, concurrent; every scan of the group: transform + exact 5-NN of every point with in-place tie replay + plane "
-                           "fit + Jacobian + HTH reduction + solve)") if fused else
-                          (f"first-evaluation k-NN of the batch: {min(stream_groups(a.batch * a.scan_points), a.batch)} concurrent {unit_kernel} dispatches "
-                           "(one per stream group: transform + exact 5-NN of every point) + their tie replays"),
-                "avg_launch_ms": round(launch_ms, 4),
-                "alg_bytes_per_launch": int(alg_bytes),
-                "alg_bytes_terms": {"slots_per_query": round(knn_visits / max(knn_queries, 1), 3),
-                                    "points_per_query": round(knn_points / max(knn_queries, 1), 2),
-                                    "bytes_per_query": round(alg_bytes / max(q_launch, 1), 1)},
-                "frac_fabric_traffic": (round(pmc["hbm_bytes_per_launch"] / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                                        if pmc and launch_ms > 0 else None),
-                "traffic_note": ("traffic = the L2's memory-side requests (2 x FETCH_SIZE + WRITE_SIZE per the MI355X "
-                                 "guide's gfx950 correction): it counts Infinity-Cache hits as well as HBM reads, so it "
-                                 "bounds HBM traffic from above; frac_fabric_traffic = traffic / launch time / HBM peak"),
-                "limiter": ("dependent-load latency: the priced roofline is HBM (bound), but the measured limiter is the "
-                            "chain hash probe -> run chunks per query (L2/MALL hits), not bytes (frac_fabric_traffic)"),
-                "reference_equivalent_GBps": round(ref_equiv, 1),
-                "reference_equivalent_note": ("not a roofline (it exceeds the HBM peak): the bytes the reference's "
-                                              "ikd-Tree search would read per query (visits_per_query_ref x 64 B + "
-                                              "52 B) over this launch's time, a work-equivalence figure only"),
-                "visits_per_query_ref": round(vq_ref, 3)}
-        if pmc:
-            roof["pmc"] = {k: v for k, v in pmc.items() if k != "hbm_bytes_per_launch"}
         result = {
             "metric": "IEKF scan-to-map updates/sec (100k-pt scan, 1M-pt map)",
             "value": round(value, 3),
@@ -544,44 +571,74 @@ def main():
             "scan_pool": {"distinct_scans_per_gpu": pool_n, "batches": n_batches,
                           "repeats_in_timed_region": a.steps > n_batches,
                           "generation_s": round(gen_s, 2)},
-            "value_with_upload": round(world * upload_counters.scans / elapsed_up, 3) if elapsed_up > 0 else None,
-            "value_with_upload_pageable": (round(world * upload_counters_pg.scans / elapsed_up_pg, 3)
-                                           if elapsed_up_pg > 0 else None),
-            "upload_note": ("the same pipelined farm with every batch's scans uploaded inside the clock: host arrays "
-                            "-> ONE livo_scan_upload_batch_async per batch (copy + bounds + keys + one stable sort + "
-                            "gather on the upload stream) two batches ahead of its submit, released once collected; "
-                            f"{n_up} distinct host batches cycled; value_with_upload from page-locked arrays "
-                            "(livo_host_register once, the copy engine reads them), value_with_upload_pageable from "
-                            "ordinary arrays through the pinned staging ring; untimed for value"),
-            "fixed8_value": round(world * fixed_counters.scans / elapsed_fixed, 3),
-            "fixed8_note": ("round 3's headline mode on this rank's GPU (scaled by the rank count): the same first 8 "
-                            "scans every step (two uploads alternating), pipelined like value; untimed for value"),
-            "sync_value": round(world * a.batch * a.steps / elapsed_sync_max, 3),
-            "sync_ms_per_step": round(elapsed_sync_max / a.steps * 1e3, 4),
-            "sync_note": ("the same pool batches with livo_iekf_update_batch (one batch at a time, the host waits for "
-                          "each); untimed for value"),
             "iekf_steps_per_s": round(total.evals / elapsed_max, 3),
             "knn_queries_per_s": round((total.knn_passes * a.scan_points) / elapsed_max, 1),
             "evals_per_scan": round(total.evals / max(total.scans, 1), 3),
             "knn_passes_per_scan": round(total.knn_passes / max(total.scans, 1), 3),
-            "roofline": roof,
-            "device_ms_per_step": {
-                "eval_first": round(t_first / n_prof, 4),
-                "eval_rematch": round(t_rematch / n_prof, 4),
-                "eval_nosearch": round(t_plane / n_prof, 4),
-                "copies_and_launch": round((t_batch - t_first - t_rematch - t_plane) / n_prof, 4),
-                "host_gap": round(t_gap / max(n_gap, 1), 4),
-                "sum": round((t_batch / n_prof) + t_gap / max(n_gap, 1), 4),
-                "wall_ms_per_step_profiled": round(wall_prof * 1e3, 4),
-                "rematch_evals_per_step": round(n_remevals / n_prof, 2),
-                "note": f"{n_prof} extra untimed steps with an event before every evaluation launch: eval_first = the "
-                        "first evaluation (search for every point + plane + reduction + solve), eval_rematch = the later "
-                        "evaluations in which some scan searched again, eval_nosearch = the cached-plane evaluations, "
-                        "copies_and_launch = the rest of the batch span (slot copies in/out), host_gap = device idle "
-                        "between two batches (the host's return, Python step, next call); sum = batch span + host_gap"},
-            "knn_replays_per_step": round(replays / n_prof, 2),
             "map_build_s": round(map_build_s, 3),
         }
+        if full:
+            roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": round(pmc["hbm_bytes_per_launch"]) if pmc else None,
+                    "kernel": (f"first evaluation of the batch: {min(stream_groups(a.batch * a.scan_points), a.batch)} {unit_kernel} dispatch(es) (one "
+                               "per stream group, concurrent; every scan of the group: transform + exact 5-NN of every point with in-place tie replay + plane "
+                               "fit + Jacobian + HTH reduction + solve)") if fused else
+                              (f"first-evaluation k-NN of the batch: {min(stream_groups(a.batch * a.scan_points), a.batch)} concurrent {unit_kernel} dispatches "
+                               "(one per stream group: transform + exact 5-NN of every point) + their tie replays"),
+                    "avg_launch_ms": round(launch_ms, 4),
+                    "alg_bytes_per_launch": int(alg_bytes),
+                    "alg_bytes_terms": {"slots_per_query": round(knn_visits / max(knn_queries, 1), 3),
+                                        "points_per_query": round(knn_points / max(knn_queries, 1), 2),
+                                        "bytes_per_query": round(alg_bytes / max(q_launch, 1), 1)},
+                    "frac_fabric_traffic": (round(pmc["hbm_bytes_per_launch"] / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                            if pmc and launch_ms > 0 else None),
+                    "traffic_note": ("traffic = the L2's memory-side requests (2 x FETCH_SIZE + WRITE_SIZE, "
+                                     "FETCH_SIZE doubled as gfx950 reports half of it): it counts Infinity-Cache hits as well as HBM reads, so it "
+                                     "bounds HBM traffic from above; frac_fabric_traffic = traffic / launch time / HBM peak"),
+                    "limiter": ("dependent-load latency: the priced roofline is HBM (bound), but the measured limiter is the "
+                                "chain hash probe -> run chunks per query (L2/MALL hits), not bytes (frac_fabric_traffic)"),
+                    "reference_equivalent_GBps": round(ref_equiv, 1),
+                    "reference_equivalent_note": ("not a roofline (it exceeds the HBM peak): the bytes the reference's "
+                                                  "ikd-Tree search would read per query (visits_per_query_ref x 64 B + "
+                                                  "52 B) over this launch's time, a work-equivalence figure only"),
+                    "visits_per_query_ref": round(vq_ref, 3)}
+            if pmc:
+                roof["pmc"] = {k: v for k, v in pmc.items() if k != "hbm_bytes_per_launch"}
+            result.update({
+                "value_with_upload": round(world * upload_counters.scans / elapsed_up, 3) if elapsed_up > 0 else None,
+                "value_with_upload_pageable": (round(world * upload_counters_pg.scans / elapsed_up_pg, 3)
+                                               if elapsed_up_pg > 0 else None),
+                "upload_note": ("the same pipelined farm with every batch's scans uploaded inside the clock: host arrays "
+                                "-> ONE livo_scan_upload_batch_async per batch (copy + bounds + keys + one stable sort + "
+                                "gather on the upload stream) two batches ahead of its submit, released once collected; "
+                                f"{n_up} distinct host batches cycled; value_with_upload from page-locked arrays "
+                                "(livo_host_register once, the copy engine reads them), value_with_upload_pageable from "
+                                "ordinary arrays through the pinned staging ring; untimed for value"),
+                "fixed8_value": round(world * fixed_counters.scans / elapsed_fixed, 3),
+                "fixed8_note": ("round 3's headline mode on this rank's GPU (scaled by the rank count): the same first 8 "
+                                "scans every step (two uploads alternating), pipelined like value; untimed for value"),
+                "sync_value": round(world * a.batch * a.steps / elapsed_sync_max, 3),
+                "sync_ms_per_step": round(elapsed_sync_max / a.steps * 1e3, 4),
+                "sync_note": ("the same pool batches with livo_iekf_update_batch (one batch at a time, the host waits for "
+                              "each); untimed for value"),
+                "roofline": roof,
+                "device_ms_per_step": {
+                    "eval_first": round(t_first / n_prof, 4),
+                    "eval_rematch": round(t_rematch / n_prof, 4),
+                    "eval_nosearch": round(t_plane / n_prof, 4),
+                    "copies_and_launch": round((t_batch - t_first - t_rematch - t_plane) / n_prof, 4),
+                    "host_gap": round(t_gap / max(n_gap, 1), 4),
+                    "sum": round((t_batch / n_prof) + t_gap / max(n_gap, 1), 4),
+                    "wall_ms_per_step_profiled": round(wall_prof * 1e3, 4),
+                    "rematch_evals_per_step": round(n_remevals / n_prof, 2),
+                    "note": f"{n_prof} extra untimed steps with an event before every evaluation launch: eval_first = the "
+                            "first evaluation (search for every point + plane + reduction + solve), eval_rematch = the later "
+                            "evaluations in which some scan searched again, eval_nosearch = the cached-plane evaluations, "
+                            "copies_and_launch = the rest of the batch span (slot copies in/out), host_gap = device idle "
+                            "between two batches (the host's return, Python step, next call); sum = batch span + host_gap"},
+                "knn_replays_per_step": round(replays / n_prof, 2),
+            })
 
     # ---- the drop-in regime: one scan at a time through livo_iekf_update (the
     # facade's iterate()), resident scan; and with livo_scan_upload of the
@@ -1030,7 +1087,7 @@ def main():
     # scan update per timing, steady clock), at 1 thread, the reference's 4
     # (MP_PROC_NUM, CMakeLists.txt:30-33) and every core available to the job;
     # + parity of scan 0 against it
-    if rank == 0 and a.cpu_seconds > 0:
+    if rank == 0 and full and a.cpu_seconds > 0:
         import oracle
         tree = oracle.Tree(m)
 

@@ -271,7 +271,6 @@ _CACHE_DIR = os.environ.get("LIVO_SYNTH_CACHE", "/tmp/livo_synth_cache")
 
 def cached_map(n_points: int) -> np.ndarray:
     """make_map with an on-disk cache (maps of 1M-10M points take seconds to generate)."""
-    os.makedirs(_CACHE_DIR, exist_ok=True)
     path = os.path.join(_CACHE_DIR, f"map_{n_points}_{SEED_MAP:x}.npy")
     if os.path.exists(path):
         try:
@@ -280,8 +279,12 @@ def cached_map(n_points: int) -> np.ndarray:
             pass
     m = make_map(n_points)
     tmp = path + f".{os.getpid()}.tmp.npy"
-    np.save(tmp, m)
-    os.replace(tmp, path)
+    try:  # the cache only saves time: a directory this user cannot write to is no error
+        os.makedirs(_CACHE_DIR, exist_ok=True)
+        np.save(tmp, m)
+        os.replace(tmp, path)
+    except OSError:
+        pass
     return m
 
 

@@ -9,7 +9,7 @@ for r in $(seq 1 $R); do
     [ "$spec" != "$n" ] && envs=$(echo "${spec#*@}" | tr ',' ' ')
     if [ "$n" = base ]; then lib=""; else lib=fast-livo-noted_amd/lib/variants/$n.so; fi
     tag=$(echo "$spec" | tr '@=,/' '+-+-')
-    env LIVO_LIB=$lib $envs timeout -k 10 200 python bench.py --steps 20 --warmup 3 --cpu-seconds 0 \
+    env LIVO_LIB=$lib $envs timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 \
         --legs headline --pmc off > gpurun_out/ab_${tag}_$r.log 2>&1 || exit $?
   done
 done

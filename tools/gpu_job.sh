@@ -5,7 +5,7 @@
 # usage: tools/gpu_job.sh TAG STEP [STEP ...]      output: gpurun_out/TAG/
 #   tests[=PATHS]         pytest -m gpu over PATHS (default: tests), one process
 #   smoke                 __graft_entry__.smoke()
-#   bench[=ARGS]          python bench.py ARGS  (default: the full default line)
+#   bench[=ARGS]          python bench.py ARGS  (default: --full, the whole default line)
 #   ab=R=SPEC,SPEC..      pooled-headline A/B in R rounds (tools/ab_pool.sh spec syntax)
 #   abs=R=SPEC;SPEC..     the same with ';' between specs (a spec may set several VAR=VAL,VAR=VAL)
 #   c5ab=SPEC,SPEC..      config-5 leg per variant (tools/c5_ab.sh)
@@ -37,7 +37,7 @@ for step in "$@"; do
     smoke)
       timeout -k 10 150 python -c "import __graft_entry__ as g; g.smoke()" > "$log" 2>&1 || { tail -30 "$log"; exit 1; } ;;
     bench)
-      timeout -k 10 700 python bench.py $arg > "$log" 2> "$log.err" || { tail -30 "$log.err"; exit 1; }
+      timeout -k 10 700 python bench.py ${arg:---full} > "$log" 2> "$log.err" || { tail -30 "$log.err"; exit 1; }
       tail -1 "$log" ;;
     ab)
       rounds=${arg%%=*}; specs=$(echo "${arg#*=}" | tr ',' ' ')
@@ -50,7 +50,7 @@ for step in "$@"; do
     c5ab)
       bash tools/c5_ab.sh $(echo "$arg" | tr ',' ' ') > "$log" 2>&1 || { tail -30 "$log"; exit 1; } ;;
     kt)
-      a=${arg:-"--legs headline --steps 20 --warmup 3 --cpu-seconds 0 --pmc off"}
+      a=${arg:-"--full --legs headline --steps 20 --warmup 3 --cpu-seconds 0 --pmc off"}
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
           -d "$OUT/kt$n" -o kt -- python3 "$R/bench.py" $a) > "$log" 2>&1 || { tail -30 "$log"; exit 1; } ;;
     ktpy)
