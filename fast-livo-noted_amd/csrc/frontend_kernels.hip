@@ -338,9 +338,7 @@ __global__ void k_fe_gather_seg(const float* __restrict__ pts, FeSegs S, const u
         make_float4(pts[3 * (int64_t)jg], pts[3 * (int64_t)jg + 1], pts[3 * (int64_t)jg + 2], 0.f);
     S.iperm[b][j] = (int32_t)k;
     S.perm[b][k] = j;
-    float4* rec = reinterpret_cast<float4*>(S.nn[b]) + 8 * k;  // (128-B NNRec)
-#pragma unroll
-    for (int w = 0; w < 8; w++) rec[w] = make_float4(0.f, 0.f, 0.f, 0.f);
+    rec_clear(reinterpret_cast<NNRec*>(S.nn[b]) + k);
     S.pstate[b][k] = 0;
 }
 

@@ -151,25 +151,20 @@ __device__ __forceinline__ int iv_query(const IvoxParams& V, float qx, float qy,
 template <class Arr>
 __device__ __forceinline__ void iv_write(NNRec* __restrict__ out, const float4* __restrict__ pts, const Arr& a,
                                          int n) {
-    float4* o4 = reinterpret_cast<float4*>(out);
-    int32_t idx[kNN], node[kNN];
+    float4 nb[kNN];
+    int32_t idx[kNN];
 #pragma unroll
     for (int k = 0; k < kNN; k++) {
         float4 v = make_float4(0.f, 0.f, 0.f, INFINITY);
         idx[k] = -1;
-        node[k] = -1;
         if (k < n) {
             const float4 p = pts[a[k].id];
             v = make_float4(p.x, p.y, p.z, a[k].d);
             idx[k] = __float_as_int(p.w);
-            node[k] = (int32_t)a[k].id;
         }
-        o4[k] = v;
+        nb[k] = v;
     }
-    int4* oi = reinterpret_cast<int4*>(out) + 5;
-    oi[0] = make_int4(idx[0], idx[1], idx[2], idx[3]);
-    oi[1] = make_int4(idx[4], n, 0, node[0]);
-    oi[2] = make_int4(node[1], node[2], node[3], node[4]);
+    rec_store_full(out, nb, idx, n, 0);
 }
 
 __device__ __forceinline__ void iv_world(const KnnParams& P, const IekfSlot* slot, const float4 b, float& qx,
@@ -302,21 +297,12 @@ __global__ __launch_bounds__(64) void k_ivox_knn_big_wave(KnnParams P) {
                     v = make_float4(pp.x, pp.y, pp.z, myd);
                     pidx = __float_as_int(pp.w);
                 }
-                reinterpret_cast<float4*>(out)[lane] = v;
+                rec_store_neighbor(out, lane, v);
             }
-            const int32_t node = lane < n ? (int32_t)myid : -1;
-            int32_t ix[kNN], nd[kNN];
+            int32_t ix[kNN];
 #pragma unroll
-            for (int q = 0; q < kNN; q++) {
-                ix[q] = __shfl(pidx, q, 64);
-                nd[q] = __shfl(node, q, 64);
-            }
-            if (lane == 0) {
-                int4* oi = reinterpret_cast<int4*>(out) + 5;
-                oi[0] = make_int4(ix[0], ix[1], ix[2], ix[3]);
-                oi[1] = make_int4(ix[4], n, 0, nd[0]);
-                oi[2] = make_int4(nd[1], nd[2], nd[3], nd[4]);
-            }
+            for (int q = 0; q < kNN; q++) ix[q] = __shfl(pidx, q, 64);
+            if (lane == 0) rec_store_meta(out, ix, n, 0);
         } else if (lane == 0) {  // the depth limit ran out: the exact per-thread search in global memory
             SelElem* a = V.scratch + (int64_t)blockIdx.x * V.slice;
             bool overflow;
@@ -368,7 +354,6 @@ __global__ __launch_bounds__(64) void k_ivox_knn_big(KnnParams P) {
 // NNRec from the wave's first n (<= 5) list entries: lanes 0..4 the points, lane 0 the indices.
 __device__ __forceinline__ void wave_write(NNRec* __restrict__ out, const float4* __restrict__ pts, const WaveLds& L,
                                            int n, int lane) {
-    float4* o4 = reinterpret_cast<float4*>(out);
     const uint32_t myid = lane < n ? L.id[lane] : 0u;
     const float myd = lane < n ? L.d[lane] : INFINITY;
     int32_t pidx = -1;
@@ -379,19 +364,11 @@ __device__ __forceinline__ void wave_write(NNRec* __restrict__ out, const float4
             v = make_float4(pp.x, pp.y, pp.z, myd);
             pidx = __float_as_int(pp.w);
         }
-        o4[lane] = v;
+        rec_store_neighbor(out, lane, v);
     }
-    const int32_t node = lane < n ? (int32_t)myid : -1;
-    const int32_t i0 = __shfl(pidx, 0, 64), i1 = __shfl(pidx, 1, 64), i2 = __shfl(pidx, 2, 64),
-                  i3 = __shfl(pidx, 3, 64), i4 = __shfl(pidx, 4, 64);
-    const int32_t n0 = __shfl(node, 0, 64), n1 = __shfl(node, 1, 64), n2 = __shfl(node, 2, 64),
-                  n3 = __shfl(node, 3, 64), n4 = __shfl(node, 4, 64);
-    if (lane == 0) {
-        int4* oi = reinterpret_cast<int4*>(out) + 5;
-        oi[0] = make_int4(i0, i1, i2, i3);
-        oi[1] = make_int4(i4, n, 0, n0);
-        oi[2] = make_int4(n1, n2, n3, n4);
-    }
+    const int32_t ix[kNN] = {__shfl(pidx, 0, 64), __shfl(pidx, 1, 64), __shfl(pidx, 2, 64), __shfl(pidx, 3, 64),
+                             __shfl(pidx, 4, 64)};
+    if (lane == 0) rec_store_meta(out, ix, n, 0);
 }
 
 // One query (point i of job) by the whole wave: the record written (or the
@@ -785,26 +762,17 @@ __global__ __launch_bounds__(256) void k_ivox_knn_team(KnnParams P) {
     NNRec* out = job.nn + i;
     SelElem e = tl < n ? L[tl] : SelElem{INFINITY, 0u};
     float4 pv = make_float4(0.f, 0.f, 0.f, INFINITY);
-    int32_t pidx = -1, node = -1;
+    int32_t pidx = -1;
     if (tl < n) {
         const float4 p = pts[e.id];
         pv = make_float4(p.x, p.y, p.z, e.d);
         pidx = __float_as_int(p.w);
-        node = (int32_t)e.id;
     }
-    if (tl < kNN) reinterpret_cast<float4*>(out)[tl] = pv;
-    int32_t ix[kNN], nd[kNN];
+    if (tl < kNN) rec_store_neighbor(out, tl, pv);
+    int32_t ix[kNN];
 #pragma unroll
-    for (int k = 0; k < kNN; k++) {
-        ix[k] = __shfl(pidx, tb + k, 64);
-        nd[k] = __shfl(node, tb + k, 64);
-    }
-    if (tl == 0) {
-        int4* oi = reinterpret_cast<int4*>(out) + 5;
-        oi[0] = make_int4(ix[0], ix[1], ix[2], ix[3]);
-        oi[1] = make_int4(ix[4], n, 0, nd[0]);
-        oi[2] = make_int4(nd[1], nd[2], nd[3], nd[4]);
-    }
+    for (int k = 0; k < kNN; k++) ix[k] = __shfl(pidx, tb + k, 64);
+    if (tl == 0) rec_store_meta(out, ix, n, 0);
 }
 
 #ifndef LIVO_IV_WLIST_BLOCKS
@@ -1172,8 +1140,9 @@ __global__ void k_map_incr(MapIncrParams P) {
     const float4 b = reinterpret_cast<const float4*>(P.pts)[j];
     float pw[3];
     world_point(P.slot->state.rot, P.slot->state.pos, P.R_LI, P.t_LI, b.x, b.y, b.z, pw[0], pw[1], pw[2]);
-    const NNRec& r = P.nn[j];
-    const int cnt = r.cnt;
+    float4 nb[kNN];
+    int cnt, rflag;
+    rec_load(P.nn + j, reinterpret_cast<const float4*>(P.keypts), nb, cnt, rflag);
     int cat = 1;
     if (cnt > 0 && P.ekf_inited) {
         const float fs = (float)P.fs;  // Eigen promotes the double scalar to float
@@ -1181,8 +1150,8 @@ __global__ void k_map_incr(MapIncrParams P) {
 #pragma unroll
         for (int a = 0; a < 3; a++) c[a] = (floorf(pw[a] / fs) + 0.5f) * fs;
         const double half = 0.5 * P.fs;
-        if ((double)fabsf(r.p[0][0] - c[0]) > half && (double)fabsf(r.p[0][1] - c[1]) > half &&
-            (double)fabsf(r.p[0][2] - c[2]) > half) {
+        if ((double)fabsf(nb[0].x - c[0]) > half && (double)fabsf(nb[0].y - c[1]) > half &&
+            (double)fabsf(nb[0].z - c[2]) > half) {
             cat = 2;
         } else {
             // common::calc_dist(Vector3f, Vector3f) = (p1 - p2).norm() (common_lib.h:85)
@@ -1195,7 +1164,7 @@ __global__ void k_map_incr(MapIncrParams P) {
             if (cnt >= kNN)
 #pragma unroll
                 for (int k = 0; k < kNN; k++)
-                    if (need_add && (double)norm3(r.p[k][0], r.p[k][1], r.p[k][2]) < (double)dist + 1e-6)
+                    if (need_add && (double)norm3(nb[k].x, nb[k].y, nb[k].z) < (double)dist + 1e-6)
                         need_add = false;
             cat = need_add ? 1 : 0;
         }
@@ -1240,6 +1209,30 @@ __global__ void k_inherit_nn(NNRec* dst, const int32_t* dst_perm, int64_t n_dst,
 int launch_inherit_nn(NNRec* dst, const int32_t* dst_perm, int64_t n_dst, const NNRec* src,
                       const int32_t* src_iperm, int64_t n_src, void* stream) {
     LAUNCH_CHECKED(k_inherit_nn, n_dst, dst, dst_perm, n_dst, src, src_iperm, n_src);
+}
+
+// Coordinates on demand: the cold half of every hot-only record (kRecNoXyz) of
+// a scan from the cell grid's points its keys index; the bit is cleared.  One
+// record per thread; nothing is read for cnt = 0, and only keys k < cnt.
+__global__ void k_fill_nn_coords(NNRec* nn, int64_t n, const float4* __restrict__ gpts) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    NNRec* r = nn + j;
+    int cnt, flag;
+    rec_load_cf(r, cnt, flag);
+    if (!(flag & (int)kRecNoXyz)) return;
+    float4 nb[kNN];
+    rec_load(r, gpts, nb, cnt, flag);
+    float4 c[4];
+    rec_pack_cold(c, nb);
+    float4* o4 = reinterpret_cast<float4*>(r) + 4;
+#pragma unroll
+    for (int k = 0; k < 4; k++) o4[k] = c[k];
+    rec_store_flag(r, cnt, flag & ~(int)kRecNoXyz);
+}
+
+int launch_fill_nn_coords(NNRec* nn, int64_t n, const float* gpts, void* stream) {
+    LAUNCH_CHECKED(k_fill_nn_coords, n, nn, n, reinterpret_cast<const float4*>(gpts));
 }
 
 }  // namespace livo

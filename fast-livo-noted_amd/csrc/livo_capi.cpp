@@ -41,6 +41,7 @@ struct ScanBuf {
     double* ikrows = nullptr;   // IKFoM few-point rows (nblk x kIkFewRows x 13)
     uint32_t* ikcnt = nullptr;  // per block
     bool searched = false;      // a search has filled the neighbour cache
+    bool nn_compact = false;    // a fused batch may have stored hot-only records (kRecNoXyz): ensure_nn_coords
     int64_t cap = 0;            // points the buffers were sized for (>= n; reused after a release)
     hipEvent_t ready = nullptr; // livo_scan_upload_async: recorded on the upload stream when the scan is built
     bool pending = false;       // an asynchronous upload may still be building it (get_scan waits)
@@ -313,6 +314,9 @@ struct livo_ctx {
     bool lane_zc = true;            // submitted batches: staging copies by kernel over host-mapped memory (LIVO_LANE_ZC)
     bool sync_zc = false;           // synchronous batches too (LIVO_SYNC_ZC)
     bool slot_wb = true;            // fused batches: the stopping solve writes the slot back (LIVO_SLOT_WB)
+    // the fused run searches on a static map store hot-only neighbour records, the
+    // coordinates filled on demand (LIVO_REC_COMPACT=0: full records)
+    bool rec_compact = true;
     int last_lane = -1;             // lane of the batch enqueued last
     unsigned long long last_replays = 0;  // profiled batches: the replay counter read back
     IekfSlot* h_slots = nullptr;  // pinned
@@ -491,6 +495,30 @@ static bool any_inflight(const livo_ctx* c) {
     return false;
 }
 
+// Coordinates on demand: a scan whose last fused batch may have stored hot-only
+// neighbour records gets their cold halves on `st`, ahead of a consumer on that
+// stream that reads coordinates from the records.  (The keys index the cell
+// grid as it is now: fill_all_nn_coords runs before anything replaces it.)
+static int ensure_nn_coords(livo_ctx* c, ScanBuf* s, hipStream_t st) {
+    if (!s->nn_compact) return LIVO_OK;
+    s->nn_compact = false;
+    if (s->n == 0 || !c->gpts) return LIVO_OK;
+    return launch_fill_nn_coords(s->nn, s->n, c->gpts, st);
+}
+// Before the map, its grid or its runs change: every flagged live scan, finished.
+static int fill_all_nn_coords(livo_ctx* c) {
+    bool any = false;
+    for (auto& s : c->scans) {
+        if (!s.used || !s.nn_compact) continue;
+        if (s.pending && s.ready) HIP_TRY(hipEventSynchronize(s.ready));
+        const int rc = ensure_nn_coords(c, &s, c->stream);
+        if (rc) return rc;
+        any = true;
+    }
+    if (any) HIP_TRY(hipStreamSynchronize(c->stream));
+    return LIVO_OK;
+}
+
 static bool params_valid(const livo_params* p) {
     return p && p->laser_point_cov > 0.0 && p->max_iterations >= 0 && p->max_iterations + 1 <= LIVO_MAX_EVALS &&
            p->flags == 0;
@@ -573,6 +601,7 @@ static KnnParams make_knn_params(livo_ctx* c) {
     kp.identity = 0;
     kp.iv = ivox_params(c);
     kp.canon = c->dyn.active ? 1 : 0;
+    kp.rec_compact = (LIVO_IDX_RUNS && c->rec_compact && vr && !c->dyn.active) ? 1 : 0;
     return kp;
 }
 
@@ -605,6 +634,7 @@ static HsParams make_hs_params(livo_ctx* c) {
     // the iVox branch has no sqdist gate (laser_mapping.cpp:519-525)
     hp.max_sqd = c->backend == LIVO_BACKEND_IVOX ? INFINITY : c->params.max_nn_sqdist;
     hp.force = -1;
+    hp.keypts = c->gpts;
     return hp;
 }
 
@@ -1390,6 +1420,7 @@ static int dyn_activate(livo_ctx* c) {
     if (d.active) return LIVO_OK;
     if (!c->has_map) return LIVO_E_NOMAP;
     if (c->knn_kind == 0) return LIVO_E_INVALID;  // kept on the cell grid (not LIVO_KNN_KIND=leaf)
+    if (int frc = fill_all_nn_coords(c)) return frc;  // (the grid the records' keys index is about to change)
     if (!d.ctr) {
         if (dev_alloc(&d.ctr, kDynCtrPad + kDynDirtyCap)) return LIVO_E_OOM;
         d.dirty = d.ctr + kDynCtrPad;  // (one allocation: dyn_add clears both with one memset)
@@ -1768,6 +1799,7 @@ static int map_incremental_ikd(livo_ctx* c, int32_t id, const livo_state* state,
     if (set_device(c)) return LIVO_E_HIP;
     const int64_t N = s->n;
     if (counts) counts[0] = counts[1] = 0;
+    // (this path reads no neighbour record; dyn_activate fills every hot-only one before the grid changes)
     int rc = dyn_activate(c);
     if (!rc) rc = dyn_add_scratch(c, std::max<int64_t>(N, 1));
     if (rc) return rc;
@@ -1855,6 +1887,7 @@ int livo_ctx_create(int device, const livo_params* p, livo_ctx** out) {
     if (const char* env = std::getenv("LIVO_LANE_ZC")) c->lane_zc = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_SYNC_ZC")) c->sync_zc = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_SLOT_WB")) c->slot_wb = std::atoi(env) != 0;
+    if (const char* env = std::getenv("LIVO_REC_COMPACT")) c->rec_compact = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_XCD_CHUNK")) c->xcd_chunk = std::max(0, std::atoi(env));  // tuning knob
     if (const char* env = std::getenv("LIVO_GRID_PPC")) {  // tuning knob
         const float v = (float)std::atof(env);
@@ -2468,8 +2501,10 @@ int livo_map_build(livo_ctx* c, const float* xyz, int64_t M, int64_t stride_byte
     if (!c || M < 0 || (M > 0 && !xyz)) return LIVO_E_INVALID;
     if (any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
     if (set_device(c)) return LIVO_E_HIP;
+    int rc = fill_all_nn_coords(c);  // (hot-only records' keys refer to the map being replaced)
+    if (rc) return rc;
     HostMap hm;
-    int rc = build_host_map(xyz, M, stride_bytes, &hm);
+    rc = build_host_map(xyz, M, stride_bytes, &hm);
     if (rc) return rc;
     HostLeafMap lm;
     HostGridMap gm;
@@ -2618,8 +2653,8 @@ int livo_knn(livo_ctx* c, const float* q, int64_t n, int32_t k, int32_t* idx, fl
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n; i++)
         for (int t = 0; t < k; t++) {
-            idx[i * k + t] = hr[i].idx[t];
-            d[i * k + t] = hr[i].p[t][3];
+            idx[i * k + t] = rec_host_idx(hr[i], t);
+            d[i * k + t] = rec_host_sqdist(hr[i], t);
         }
     return LIVO_OK;
 }
@@ -2687,6 +2722,7 @@ static int alloc_scan_buf(livo_ctx* c, ScanBuf& s, int64_t N) {
     }
     s.used = true;
     s.searched = false;
+    s.nn_compact = false;
     s.n = N;
     s.nblk = (int32_t)std::max<int64_t>(1, (N + kBlock * kPtsPerThread - 1) / (kBlock * kPtsPerThread));
     s.pending = false;
@@ -3258,8 +3294,8 @@ int livo_scan_neighbors(livo_ctx* c, int32_t id, int32_t* idx, float* sqdist) {
     for (int64_t j = 0; j < s->n; j++) {
         const int64_t o = (int64_t)s->perm[(size_t)j];  // caller's point index
         for (int k = 0; k < kNN; k++) {
-            if (idx) idx[o * kNN + k] = rec[(size_t)j].idx[k];
-            if (sqdist) sqdist[o * kNN + k] = rec[(size_t)j].p[k][3];
+            if (idx) idx[o * kNN + k] = rec_host_idx(rec[(size_t)j], k);
+            if (sqdist) sqdist[o * kNN + k] = rec_host_sqdist(rec[(size_t)j], k);
         }
     }
     return LIVO_OK;
@@ -3285,6 +3321,8 @@ int livo_h_share(livo_ctx* c, int32_t id, const livo_state* state, int search_en
     rc = ensure_scratch(c, nvb + wb + sb + 2 * fb + ob + cb + 64);
     if (rc) return rc;
     char* base = (char*)c->scratch;
+    rc = ensure_nn_coords(c, s, c->stream);  // (cached neighbours may be read: search_en 0, iVox queries out of range)
+    if (rc) return rc;
     init_slot(c->h_slots[0], *state, *state, c->params.max_iterations);
     fill_job(c->h_jobs[0], *s, c->d_slots);
     HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
@@ -3385,8 +3423,8 @@ int livo_h_share(livo_ctx* c, int32_t id, const livo_state* state, int search_en
         if (!h_sel.empty()) out->selected[i] = h_sel[k];
         if (!recs.empty())
             for (int j = 0; j < 5; j++) {
-                if (out->nn_idx) out->nn_idx[i * 5 + j] = recs[k].idx[j];
-                if (out->nn_sqdist) out->nn_sqdist[i * 5 + j] = recs[k].p[j][3];
+                if (out->nn_idx) out->nn_idx[i * 5 + j] = rec_host_idx(recs[k], j);
+                if (out->nn_sqdist) out->nn_sqdist[i * 5 + j] = rec_host_sqdist(recs[k], j);
             }
     }
     return LIVO_OK;
@@ -3533,6 +3571,12 @@ static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int 
             if (s->pending) HIP_TRY(hipStreamWaitEvent(st, s->ready, 0));
             // IKFoM: its searches rewrite the neighbours without refitting the cached planes
             if (model == kModelIkfom && s->n > 0) HIP_TRY(hipMemsetAsync(s->pstate, 0, (size_t)s->n, st));
+            // the unfused passes may read cached neighbours' coordinates (seeded rematch, IKFoM,
+            // an iVox query with no candidate keeps its record)
+            if (!fused) {
+                rc = ensure_nn_coords(c, s, st);
+                if (rc) return rc;
+            }
         }
         if (prev)
             for (int q = 0; q < prev->ngroups; q++) HIP_TRY(hipStreamWaitEvent(st, prev->done[q], 0));
@@ -3553,6 +3597,9 @@ static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int 
     const int evals = max_iter + 1;
     HsParams hp[kMaxGroups];
     KnnParams kp[kMaxGroups];
+    // (rec_compact: the ikd-Tree backend's run searches on a static map, the only writer of hot-only records)
+    if (fused && make_knn_params(c).rec_compact)
+        for (int32_t b = 0; b < n; b++) get_scan_q(c, ids[b])->nn_compact = true;
     for (int gi = 0; gi < ngroups; gi++) {
         hp[gi] = make_hs_params(c);
         hp[gi].jobs = djobs + g[gi].first;
@@ -3844,8 +3891,11 @@ int livo_ikfom_update(livo_ctx* c, int32_t id, livo_ikfom_state* state, livo_ikf
 int livo_ctx_set_backend(livo_ctx* c, int backend) {
     if (!c || (backend != LIVO_BACKEND_IKDTREE && backend != LIVO_BACKEND_IVOX)) return LIVO_E_INVALID;
     if (any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
-    if (backend != c->backend)
+    if (backend != c->backend) {
+        if (set_device(c)) return LIVO_E_HIP;
+        if (int rc = fill_all_nn_coords(c)) return rc;
         for (auto& s : c->scans) s.searched = false;  // cached neighbours belong to the other map
+    }
     c->backend = backend;
     return LIVO_OK;
 }
@@ -3955,11 +4005,11 @@ int livo_ivox_knn(livo_ctx* c, const float* q, int64_t n, int32_t max_num, doubl
     HIP_TRY(hipMemcpyAsync(hr.data(), dr, rb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n; i++) {
-        cnt[i] = hr[i].cnt;
+        cnt[i] = rec_host_cnt(hr[i]);
         for (int t = 0; t < max_num; t++) {
-            const bool has = hr[i].cnt > t;
-            idx[i * max_num + t] = has ? hr[i].idx[t] : -1;
-            d[i * max_num + t] = has ? hr[i].p[t][3] : INFINITY;
+            const bool has = rec_host_cnt(hr[i]) > t;
+            idx[i * max_num + t] = has ? rec_host_idx(hr[i], t) : -1;
+            d[i * max_num + t] = has ? rec_host_sqdist(hr[i], t) : INFINITY;
         }
     }
     return LIVO_OK;
@@ -4041,9 +4091,12 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
     init_slot(c->h_slots[0], *state, *state, c->params.max_iterations);
     HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(flags, 0, fb, c->stream));
+    rc = ensure_nn_coords(c, s, c->stream);
+    if (rc) return rc;
     MapIncrParams mp{};
     mp.pts = s->pts;
     mp.nn = s->nn;
+    mp.keypts = c->gpts;
     mp.perm = s->d_perm;
     mp.slot = c->d_slots;
     std::memcpy(mp.R_LI, c->params.R_LI, sizeof(mp.R_LI));
@@ -4091,7 +4144,10 @@ int livo_scan_inherit_neighbors(livo_ctx* c, int32_t dst, int32_t src) {
     if (dst == src) return LIVO_OK;
     if (set_device(c)) return LIVO_E_HIP;
     if (d->n == 0) return LIVO_OK;
-    const int rc = launch_inherit_nn(d->nn, d->d_perm, d->n, s->nn, s->d_iperm, s->searched ? s->n : 0, c->stream);
+    int rc = s->searched ? ensure_nn_coords(c, s, c->stream) : LIVO_OK;  // (whole records are copied)
+    if (rc) return rc;
+    d->nn_compact = false;
+    rc = launch_inherit_nn(d->nn, d->d_perm, d->n, s->nn, s->d_iperm, s->searched ? s->n : 0, c->stream);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(d->pstate, 0, (size_t)d->n, c->stream));  // new neighbours: planes to refit
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -275,16 +275,38 @@ struct alignas(128) IekfSlot {
 constexpr size_t kSlotLmBytes = offsetof(IekfSlot, ik);  // bytes of a slot the LaserMapping model reads / writes
 constexpr size_t kSlotWbBytes = offsetof(IekfSlot, covL);  // what the host reads back (no factors, no tickets)
 
-// Nearest_Points[i] + pointSearchSqDis for one point: 128 B, written by the
-// k-NN pass, read by every plane-fit pass until the next search.
+// Nearest_Points[i] + pointSearchSqDis for one point: 128 B in two 64-B
+// halves.  The hot half is what the loop's outputs need (distances, indices,
+// count, flags) plus one key per neighbour; the cold half holds the
+// neighbours' coordinates.  The fused search on a static map stores the hot
+// half only (kRecNoXyz): key[k] is then the neighbour's position in the cell
+// grid's points (KnnParams::gpts), from which a reader fetches (x, y, z) bit
+// for bit (rec_load, device_common.h) and k_fill_nn_coords writes the cold
+// half on demand.  Every other writer stores both halves.  All access goes
+// through the accessors below and in device_common.h.
 struct alignas(16) NNRec {
-    float p[kNN][4];   // x, y, z, squared distance (ascending); +inf pad
-    int32_t idx[kNN];  // map indices (input order of livo_map_build), -1 pad
-    int32_t cnt;       // neighbours found (< 5 only for maps of < 5 points)
-    int32_t flag;      // why the exact replay recomputed it (bits, see k_knn_pass); 0x100: replayed
-    int32_t node[kNN]; // heap node ids of the neighbours (seeds of the next search)
+    float sqdist[kNN];   // squared distances (ascending); +inf pad
+    int32_t idx[kNN];    // map indices (input order of livo_map_build), -1 pad
+    uint32_t key[kNN];   // kRecNoXyz: grid positions of the neighbours (else unused)
+    uint32_t cf;         // count << kRecCntShift | flag bits
+    float xyz[kNN][3];   // cold half: coordinates, 0 pad (stale while kRecNoXyz is set)
+    uint32_t pad_;
 };
 static_assert(sizeof(NNRec) == 128, "NNRec must be 128 bytes");
+static_assert(offsetof(NNRec, xyz) == 64, "hot half: bytes 0-63, cold half: bytes 64-127");
+// flag bits: why the exact replay recomputed the record (see k_knn_pass), 0x100 replayed,
+// 0x1000 kIkDrop (IKFoM); count: neighbours found (< 5 only for maps of < 5 points)
+constexpr uint32_t kRecNoXyz = 0x2000u;  // the cold half was not stored: coordinates come from key[]
+constexpr int kRecCntShift = 24;
+constexpr uint32_t kRecFlagMask = (1u << kRecCntShift) - 1u;
+constexpr int rec_cnt(uint32_t cf) { return (int)(cf >> kRecCntShift); }
+constexpr int rec_flag(uint32_t cf) { return (int)(cf & kRecFlagMask); }
+// The host's view of a record copied back: index and squared distance of
+// neighbour k (the hot half alone), the pads where k >= count.
+// (count -1: a record of a 0xFF-filled buffer that no search wrote, livo_ivox_knn)
+inline int rec_host_cnt(const NNRec& r) { return r.cf == 0xFFFFFFFFu ? -1 : rec_cnt(r.cf); }
+inline int32_t rec_host_idx(const NNRec& r, int k) { return r.idx[k]; }
+inline float rec_host_sqdist(const NNRec& r, int k) { return r.sqdist[k]; }
 
 // One scan of a batched launch.
 struct HsJob {
@@ -323,6 +345,7 @@ struct HsParams {
     int32_t solve;          // 1: the last block of a scan also runs its solve (IEKF loop)
     unsigned* replay_count; // zeroed once per launch (the group's k-NN replay count), may be null
     unsigned* replay_count2;  // iVox: the wave pass's overflow count, zeroed with replay_count (may be null)
+    const float* keypts;      // the points the keys of kRecNoXyz records index (the cell grid's, 4 floats each)
 };
 
 struct KnnParams {
@@ -375,6 +398,9 @@ struct KnnParams {
     const GridSlot* dvslots;  // the delta grid's cell runs (null: none); entries = positions in dpts
     const RunWord* dvidx;
     int32_t dvlog2;
+    // k_iekf_eval's run searches on a static map store the records' hot halves only
+    // (kRecNoXyz; LIVO_REC_COMPACT=0: full records)
+    int32_t rec_compact;
 };
 
 struct SolveParams {
@@ -459,6 +485,7 @@ int prim_exclusive_scan_u32(void* temp, size_t* temp_bytes, const uint32_t* in, 
 struct MapIncrParams {
     const float* pts;         // scan body points (stored order), N x 4
     const NNRec* nn;
+    const float* keypts;      // the points a kRecNoXyz record's keys index (the host fills such records first)
     const int32_t* perm;      // stored position -> caller index
     const IekfSlot* slot;     // its state = the updated state
     double R_LI[9];
@@ -746,5 +773,8 @@ int launch_run_slots(const unsigned long long* skeys, const uint32_t* starts, co
 // Nearest_Points carried over by point index (laser_mapping.cpp:165 resize keeps entries).
 int launch_inherit_nn(NNRec* dst, const int32_t* dst_perm, int64_t n_dst, const NNRec* src,
                       const int32_t* src_iperm, int64_t n_src, void* stream);
+// Coordinates on demand: every kRecNoXyz record of nn[0, n) gets its cold half from
+// gpts (the cell grid's points its keys index) and loses the bit.
+int launch_fill_nn_coords(NNRec* nn, int64_t n, const float* gpts, void* stream);
 
 }  // namespace livo

@@ -575,10 +575,11 @@ __device__ __forceinline__ void sl_insert(SList& s, float d, uint32_t node) {
 }
 
 // One neighbour record per point (Nearest_Points[i] + pointSearchSqDis);
-// flag = 1 if the query goes to the exact replay; node[] = heap ids (seeds of the next search).
+// flag = 1 if the query goes to the exact replay; node[]: the neighbours' heap ids (their points are fetched here).
+// A full record (both halves).
 __device__ __forceinline__ void write_nnrec(NNRec* __restrict__ out, const MapNode* __restrict__ nodes, int cnt,
                                             const float (&d)[kNN], const uint32_t (&node)[kNN], int flag) {
-    float4* o4 = reinterpret_cast<float4*>(out);
+    float4 nb[kNN];
     int32_t idx[kNN];
 #pragma unroll
     for (int k = 0; k < kNN; k++) {
@@ -589,12 +590,9 @@ __device__ __forceinline__ void write_nnrec(NNRec* __restrict__ out, const MapNo
             v = make_float4(a.x, a.y, a.z, d[k]);
             idx[k] = (int32_t)(__float_as_uint(a.w) & kIdxMask);
         }
-        o4[k] = v;
+        nb[k] = v;
     }
-    int4* oi = reinterpret_cast<int4*>(out) + 5;
-    oi[0] = make_int4(idx[0], idx[1], idx[2], idx[3]);
-    oi[1] = make_int4(idx[4], cnt, flag, (int)node[0]);
-    oi[2] = make_int4((int)node[1], (int)node[2], (int)node[3], (int)node[4]);
+    rec_store_full(out, nb, idx, cnt, flag);
 }
 
 // The state an evaluation transforms its points with, wherever it is held
@@ -789,12 +787,14 @@ __device__ __forceinline__ void lq_init(LeafQuery& q, const KnnParams& P, const 
     if (SEEDED) {
         // the point's 5 previous neighbours, re-measured: 5 distinct map points
         // at distance <= B, so B >= d5
-        const NNRec* sr = job.nn + i;
-        if (sr->cnt == kNN) {
+        float4 sn[kNN];
+        int scnt, sflag;
+        rec_load(job.nn + i, reinterpret_cast<const float4*>(P.gpts), sn, scnt, sflag);
+        if (scnt == kNN) {
             float bmax = 0.0f;
 #pragma unroll
             for (int k = 0; k < kNN; k++) {
-                const float4 a = reinterpret_cast<const float4*>(sr->p)[k];
+                const float4 a = sn[k];
                 const float dx = q.qx - a.x, dy = q.qy - a.y, dz = q.qz - a.z;
                 bmax = fmaxf(bmax, (dx * dx + dy * dy) + dz * dz);
             }
@@ -863,14 +863,18 @@ __device__ __forceinline__ float4 cand_point(const float4* __restrict__ lpts, co
 // C2 gap in (0, 1e-10], C2 exact tie with equal x, C1 with e6 == d5 exactly]
 __device__ unsigned long long g_amb_reason[8];
 #endif
-template <bool RUNS = false>
-// stage: the wave's LDS record buffer (64 x 8 float4, part k of lane l's record at
-// l * 8 + ((k + l) & 7): 8 distinct 16-B slots per row, so the lanes' writes spread
-// over the banks); nullptr: the record goes straight to job.nn.
+// A wave's LDS record stage: 64 x 4 float4, one half record per lane; part k of
+// lane l's half at l * 4 + ((k + (l >> 2)) & 3), so that 16 consecutive lanes'
+// 16-B writes of one part cover all 64 banks.
+__device__ __forceinline__ int rec_stage_slot(int l, int k) { return l * 4 + ((k + (l >> 2)) & 3); }
+template <bool RUNS = false, bool NBR = false>  // NBR: nbr takes the neighbours
+// stage: the wave's LDS record stage, which takes the record's hot half (with
+// stage_flag's kRecNoXyz; the caller stores it and, for a full record, the cold
+// half from nbr); nullptr: the full record goes straight to job.nn.
 __device__ __forceinline__ bool lq_finish(LeafQuery& q, const KnnParams& P, const HsJob& job, unsigned bjob,
                                           int i, const float4* __restrict__ lpts, bool overrun, bool enqueue = true,
                                           const float4* __restrict__ vpts = nullptr, float4* nbr = nullptr,
-                                          float4* stage = nullptr) {
+                                          float4* stage = nullptr, int stage_flag = 0) {
     const int cnt = (int)min<int64_t>(P.lM, (int64_t)kNN);
     float4 a[kNN];
 #pragma unroll
@@ -920,32 +924,35 @@ __device__ __forceinline__ bool lq_finish(LeafQuery& q, const KnnParams& P, cons
         for (int k = 0; k < kNN; k++)
             if (k < cnt) a[k] = cand_point<RUNS>(lpts, vpts, q.nd[k]);
     }
-    // neighbour record: points, distances, original indices; node[] = leaf-map slots
-    float4* o4 = reinterpret_cast<float4*>(job.nn + i);
-    const int sl = threadIdx.x & 63;
-    auto put = [&](int k, float4 v) {
-        if (stage) stage[sl * 8 + ((k + sl) & 7)] = v;
-        else o4[k] = v;
-    };
+    // neighbour record: points, distances, original indices; key[] = the candidates' positions
+    float4 nb[kNN];
     int32_t idx[kNN];
+    float d[kNN];
+    uint32_t key[kNN];
 #pragma unroll
     for (int k = 0; k < kNN; k++) {
         float4 v = make_float4(0.f, 0.f, 0.f, INFINITY);
         idx[k] = -1;
+        key[k] = 0u;
         if (k < cnt) {
             v = make_float4(a[k].x, a[k].y, a[k].z, q.d[k]);
             idx[k] = (int32_t)__float_as_uint(a[k].w);
+            key[k] = q.nd[k];
         }
-        put(k, v);
-        if (nbr) nbr[k] = v;  // (x, y, z, sqdist) as the record holds them
+        nb[k] = v;
+        d[k] = v.w;
+        if constexpr (NBR) nbr[k] = v;  // (x, y, z, sqdist) as the record holds them
     }
     const int flag = amb ? 4 : (tie ? 16 : 0);
-    auto i4 = [](int x, int y, int z, int w) {
-        return make_float4(__int_as_float(x), __int_as_float(y), __int_as_float(z), __int_as_float(w));
-    };
-    put(5, i4(idx[0], idx[1], idx[2], idx[3]));
-    put(6, i4(idx[4], cnt, flag, (int)q.nd[0]));
-    put(7, i4((int)q.nd[1], (int)q.nd[2], (int)q.nd[3], (int)q.nd[4]));
+    if (stage) {
+        float4 h[4];
+        rec_pack_hot(h, d, idx, key, cnt, flag | (stage_flag & (int)kRecNoXyz));
+        const int sl = threadIdx.x & 63;
+#pragma unroll
+        for (int k = 0; k < 4; k++) stage[rec_stage_slot(sl, k)] = h[k];
+    } else {
+        rec_store_full(job.nn + i, nb, idx, cnt, flag);
+    }
     if (amb && enqueue) flag_for_replay(P, bjob, i);
     return amb;
 }
@@ -1939,7 +1946,7 @@ __global__ __launch_bounds__(64) void k_knn_replay(KnnParams P) {
         uint32_t on[kNN];
 #pragma unroll
         for (int k = 0; k < kNN; k++) { od[k] = c.d[k]; on[k] = c.node[k]; }
-        write_nnrec(job.nn + i, P.nodes, c.n, od, on, job.nn[i].flag | 0x100);
+        write_nnrec(job.nn + i, P.nodes, c.n, od, on, rec_flag(job.nn[i].cf) | 0x100);
     }
 }
 
@@ -1964,8 +1971,10 @@ __device__ __forceinline__ void canon_query(const KnnParams& P, const HsJob& job
         float qx, qy, qz;
         query_point(P, src, reinterpret_cast<const float4*>(job.pts)[i], qx, qy, qz);
         NNRec* rec = job.nn + i;
-        const float T = rec->cnt == kNN ? rec->p[kNN - 1][3] : INFINITY;
-        const int flag = rec->flag | 0x100;
+        int rcnt, rflag;
+        rec_load_cf(rec, rcnt, rflag);
+        const float T = rcnt == kNN ? rec->sqdist[kNN - 1] : INFINITY;
+        const int flag = rflag | 0x100;
         float bd[kNN], bx[kNN];
         uint32_t bi[kNN], bs[kNN];
 #pragma unroll
@@ -2029,7 +2038,7 @@ __device__ __forceinline__ void canon_query(const KnnParams& P, const HsJob& job
         if (!scanned)
             for (int64_t s = 0; s < P.lM; s++) offer((uint32_t)s);
         const int cnt = (int)min<int64_t>(P.lM, (int64_t)kNN);
-        float4* o4 = reinterpret_cast<float4*>(rec);
+        float4 nb[kNN];
         int32_t idx[kNN];
 #pragma unroll
         for (int k = 0; k < kNN; k++) {
@@ -2040,12 +2049,9 @@ __device__ __forceinline__ void canon_query(const KnnParams& P, const HsJob& job
                 v = make_float4(a.x, a.y, a.z, bd[k]);
                 idx[k] = (int32_t)bi[k];
             }
-            o4[k] = v;
+            nb[k] = v;
         }
-        int4* oi = reinterpret_cast<int4*>(rec) + 5;
-        oi[0] = make_int4(idx[0], idx[1], idx[2], idx[3]);
-        oi[1] = make_int4(idx[4], cnt, flag, (int)bs[0]);
-        oi[2] = make_int4((int)bs[1], (int)bs[2], (int)bs[3], (int)bs[4]);
+        rec_store_full(rec, nb, idx, cnt, flag);
     }
 }
 __global__ __launch_bounds__(64) void k_knn_canon(KnnParams P) {
@@ -2834,11 +2840,10 @@ __device__ __forceinline__ void hshare_point(const HsParams& P, const HsJob& job
             // from its neighbours in registers (in.ps / in.plane, fit_plane)
             uint8_t ps = (search && !prefit) ? 0 : in.ps;
             if (!NOFIT && ps == 0 && !prefit) {  // (NOFIT: the caller fitted every plane state 0 beforehand)
-                const float4* rec = reinterpret_cast<const float4*>(job.nn + i);
+                // (a hot-only record of the fused search: the coordinates through its keys)
                 float4 nb[kNN];
-    #pragma unroll
-                for (int k = 0; k < kNN; k++) nb[k] = rec[k];
-                const int cnt = reinterpret_cast<const int4*>(job.nn + i)[6].y;
+                int cnt, rflag;
+                rec_load(job.nn + i, reinterpret_cast<const float4*>(P.keypts), nb, cnt, rflag);
                 float4 pl;
                 ps = fit_plane(P, job, i, search, nb, cnt, pl);
                 plane_ok = ps == 2;
@@ -3307,7 +3312,7 @@ __device__ __forceinline__ void replay_wave(const KnnParams& P, const HsJob& job
             uint32_t on[kNN];
 #pragma unroll
             for (int k = 0; k < kNN; k++) { od[k] = c.d[k]; on[k] = c.node[k]; }
-            write_nnrec(job.nn + il, P.nodes, c.n, od, on, job.nn[il].flag | 0x100);
+            write_nnrec(job.nn + il, P.nodes, c.n, od, on, rec_flag(job.nn[il].cf) | 0x100);
         }
     }
 }
@@ -3358,7 +3363,7 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
             HsReduceLds R;
             SolveLds solve;  // the scan's last block solves after its search is done
         } rs;
-        float4 nnstage[kEvalBlock / 64][64 * 8];  // each wave's 64 neighbour records (the run searches)
+        float4 nnstage[kEvalBlock / 64][64 * 4];  // each wave's 64 half records (the run searches)
     } U;
     unsigned bjob, bx;
     // the same block order in every evaluation: the plane caches stay in the L2 that wrote them
@@ -3470,43 +3475,64 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
             }
             EVAL_MARK(5);
 #endif
+            // hot-only records (kRecNoXyz) on a static map: the loop's later evaluations read
+            // the plane cache, a plane state 0 point its coordinates through the keys
+#if LIVO_IDX_RUNS
+            const bool compact = P.rec_compact && !dyn && !P.canon;  // (uniform)
+#else
+            constexpr bool compact = false;  // (float4 runs: a key may lie in either run array)
+#endif
+            float4 nb[kNN];
+#pragma unroll
+            for (int k = 0; k < kNN; k++) nb[k] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (valid) {
-                float4 nb[kNN];
                 // candidates: grid positions (index runs, the cell walk), or run positions (float4 runs);
                 // on the incremental map positions in its base set rpts, or kRunPos | delta positions
                 float4* stage = U.nnstage[threadIdx.x >> 6];
+                const int sflag = compact ? (int)kRecNoXyz : 0;
                 if (dyn)
-                    amb = lq_finish<true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(walked ? P.gpts : P.rpts),
-                                          !certified, false, reinterpret_cast<const float4*>(P.dpts), nb, stage);
+                    amb = lq_finish<true, true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(walked ? P.gpts : P.rpts),
+                                          !certified, false, reinterpret_cast<const float4*>(P.dpts), nb, stage, sflag);
                 else
-                    amb = lq_finish<!LIVO_IDX_RUNS>(q, P, job, bjob, i, reinterpret_cast<const float4*>(P.gpts),
-                                                    !certified, false, walked ? nullptr : runs, nb, stage);
+                    amb = lq_finish<!LIVO_IDX_RUNS, true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(P.gpts),
+                                                    !certified, false, walked ? nullptr : runs, nb, stage, sflag);
+            }
+            {
+                // the wave's 64 half records leave as one coalesced run of 64-B pieces
+                // (the AoS record stores put each lane's 16 B in its own 128-B line: 64
+                // lines per store instruction); a full record's cold half follows
+                // through the same stage
+                const int lane = threadIdx.x & 63;
+                float4* st = U.nnstage[threadIdx.x >> 6];
+                const int base = i - lane;
+                float4* dst = reinterpret_cast<float4*>(job.nn + base);
+                auto flush = [&](int half) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int u = j * 64 + lane, rec = u >> 2, part = u & 3;
+                        if (base + rec < job.n) dst[rec * 8 + half * 4 + part] = st[rec_stage_slot(rec, part)];
+                    }
+                };
+                flush(0);
+                if (!compact) {
+                    float4 c[4];
+                    rec_pack_cold(c, nb);
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_wave_barrier();  // (the stage's hot halves have been read)
+#pragma unroll
+                    for (int k = 0; k < 4; k++) st[rec_stage_slot(lane, k)] = c[k];
+                    flush(1);
+                }
                 // the plane from the neighbours in registers (18643 vs 18011 updates/s
-                // re-reading the record just written, profiles/r03_ab_prefit_seed.txt)
-                if (!amb && (!P.canon || dyn)) {  // (a replayed query's plane is fitted from its record below)
+                // re-reading the record just written, profiles/r03_ab_prefit_seed.txt), after
+                // the stage took them: they are not held across the stores
+                if (valid && !amb && (!P.canon || dyn)) {  // (a replayed query's plane is fitted from its record below)
                     float4 pl;
                     pin.ps = fit_plane(E.h, job, i, 1, nb, (int)min<int64_t>(P.lM, (int64_t)kNN), pl);
                     pin.plane = pl;
                     prefit = true;
-                }
-            }
-            {
-                // the wave's 64 records leave as one coalesced 8-KB run (the AoS
-                // record stores put each lane's 16 B in its own 128-B line: 64
-                // lines per store instruction, 8 instructions per wave)
-                const int lane = threadIdx.x & 63;
-                const float4* st = U.nnstage[threadIdx.x >> 6];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-                const int base = i - lane;
-                float4* dst = reinterpret_cast<float4*>(job.nn + base);
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int u = j * 64 + lane, rec = u >> 3;
-#ifdef LIVO_AB_REC_KNOCKOUT  // A/B only (wrong records): 64 of each record's 128 B stored, to price the writes
-                    if ((u & 7) >= 4) continue;
-#endif
-                    if (base + rec < job.n) dst[u] = st[rec * 8 + (((u & 7) + rec) & 7)];
                 }
                 // a flagged query's replay (same wave) reads its record back
                 if (__ballot(amb)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -3924,10 +3950,9 @@ __global__ __launch_bounds__(kBlock) void k_hshare_ik(HsParams P) {
             const float4 pb = reinterpret_cast<const float4*>(job.pts)[i];
             float wx, wy, wz;
             ik_world_point(X, pb.x, pb.y, pb.z, wx, wy, wz);
-            const float4* rec = reinterpret_cast<const float4*>(job.nn + i);
-            int* flagp = reinterpret_cast<int*>(job.nn + i) + 26;  // NNRec::flag
-            const int cnt = reinterpret_cast<const int4*>(job.nn + i)[6].y;
-            const int flag = *flagp;
+            NNRec* rec = job.nn + i;
+            int cnt, flag;
+            rec_load_cf(rec, cnt, flag);
             // Without a search a point is processed only if the last evaluation
             // kept it, and that evaluation fitted its plane from the same five
             // neighbours: the plane cache (pstate 2) holds that fit, so the
@@ -3937,7 +3962,7 @@ __global__ __launch_bounds__(kBlock) void k_hshare_ik(HsParams P) {
 #define LIVO_IK_PLANE_CACHE 1
 #endif
             const uint8_t ps = (search || !LIVO_IK_PLANE_CACHE) ? (uint8_t)0 : job.pstate[i];
-            const bool sel = search ? ((cnt == kNN) && !(rec[kNN - 1].w > P.max_sqd)) : !(flag & kIkDrop);
+            const bool sel = search ? ((cnt == kNN) && !(rec->sqdist[kNN - 1] > P.max_sqd)) : !(flag & kIkDrop);
             bool fin = false;
             float pa[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             float pd2 = 0.0f;
@@ -3949,11 +3974,11 @@ __global__ __launch_bounds__(kBlock) void k_hshare_ik(HsParams P) {
                     planed = true;
                 } else if (ps == 0) {
                     float nx[kNN], ny[kNN], nz[kNN];
+                    float4 nb[kNN];
+                    int c2, f2;
+                    rec_load(rec, reinterpret_cast<const float4*>(P.keypts), nb, c2, f2);
 #pragma unroll
-                    for (int k = 0; k < kNN; k++) {
-                        const float4 v = rec[k];
-                        nx[k] = v.x; ny[k] = v.y; nz[k] = v.z;
-                    }
+                    for (int k = 0; k < kNN; k++) { nx[k] = nb[k].x; ny[k] = nb[k].y; nz[k] = nb[k].z; }
                     planed = esti_plane(nx, ny, nz, P.plane_thr, pa);
                     if (planed) reinterpret_cast<float4*>(job.plane)[i] = make_float4(pa[0], pa[1], pa[2], pa[3]);
                     job.pstate[i] = planed ? 2 : 1;
@@ -3967,7 +3992,7 @@ __global__ __launch_bounds__(kBlock) void k_hshare_ik(HsParams P) {
                 }
             }
             const int nflag = fin ? (flag & ~kIkDrop) : (flag | kIkDrop);
-            if (nflag != flag) *flagp = nflag;
+            if (nflag != flag) rec_store_flag(rec, cnt, nflag);
             if (P.dbg.sel) P.dbg.sel[i] = (fin && (double)fabsf(pd2) <= P.max_res) ? 1 : 0;
             if (fin && (double)fabsf(pd2) <= P.max_res) {
                 const double be[3] = {(double)pb.x, (double)pb.y, (double)pb.z};

@@ -428,11 +428,9 @@ __global__ __launch_bounds__(BLK) void k_lab_seed(const MapNode* __restrict__ no
         sl_init(s);
         bool flag = false;
         // seeds: the previous neighbours, re-measured from the new query point
-        const int4 si0 = reinterpret_cast<const int4*>(seed + i)[7];  // pad holds the node ids (lab only)
-        const int4 si1 = reinterpret_cast<const int4*>(seed + i)[6];
-        const int scnt = si1.y;
-        const uint32_t sn[kNN] = {(uint32_t)si0.x, (uint32_t)si0.y, (uint32_t)si0.z, (uint32_t)si0.w,
-                                  (uint32_t)si1.z};
+        const NNRec* sr = seed + i;  // key[] holds the node ids (lab only)
+        const int scnt = rec_cnt(sr->cf);
+        const uint32_t sn[kNN] = {sr->key[0], sr->key[1], sr->key[2], sr->key[3], sr->key[4]};
 #pragma unroll
         for (int k = 0; k < kNN; k++) {
             if (k < scnt) {
@@ -542,10 +540,8 @@ int lab_set_seed_nodes(const int32_t* node_ids /* n*5, -1 pad */, const int32_t*
     std::vector<NNRec> h((size_t)g_n);
     for (int64_t i = 0; i < g_n; i++) {
         std::memset(&h[i], 0, sizeof(NNRec));
-        h[i].cnt = cnt[i];
-        int* pad = reinterpret_cast<int*>(&h[i]) + 28;  // int4 #7
-        for (int k = 0; k < 4; k++) pad[k] = node_ids[i * 5 + k];
-        reinterpret_cast<int*>(&h[i])[26] = node_ids[i * 5 + 4];  // int4 #6 .z
+        h[i].cf = (uint32_t)cnt[i] << kRecCntShift;
+        for (int k = 0; k < 5; k++) h[i].key[k] = (uint32_t)node_ids[i * 5 + k];
     }
     if (!g_seed) hipMalloc((void**)&g_seed, (size_t)g_n * sizeof(NNRec));
     hipMemcpy(g_seed, h.data(), h.size() * sizeof(NNRec), hipMemcpyHostToDevice);
@@ -650,10 +646,10 @@ double lab_run(int v, int reps, int chunk, int32_t* idx, float* d, long long* vi
     for (int64_t i = 0; i < g_n; i++)
         for (int k = 0; k < 5; k++) {
             idx[i * 5 + k] = h[i].idx[k];
-            d[i * 5 + k] = h[i].p[k][3];
+            d[i * 5 + k] = h[i].sqdist[k];
         }
     if (flags)
-        for (int64_t i = 0; i < g_n; i++) flags[i] = h[i].flag;
+        for (int64_t i = 0; i < g_n; i++) flags[i] = rec_flag(h[i].cf);
     visits[0] = (long long)vv[0];
     visits[1] = (long long)vv[1];
     hipError_t err = hipGetLastError();
@@ -713,6 +709,6 @@ extern "C" int lab_product_pass(int seeded_from_last, int32_t* flags_out, double
     ms_out[1] = (seeded_from_last ? 0 : ms_rep / nr);
     std::vector<NNRec> h((size_t)g_n);
     hipMemcpy(h.data(), g_out, h.size() * sizeof(NNRec), hipMemcpyDeviceToHost);
-    for (int64_t i = 0; i < g_n; i++) flags_out[i] = h[i].flag;
+    for (int64_t i = 0; i < g_n; i++) flags_out[i] = rec_flag(h[i].cf);
     return 0;
 }
