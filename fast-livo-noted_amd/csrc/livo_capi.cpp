@@ -317,6 +317,9 @@ struct livo_ctx {
     // the fused run searches on a static map store hot-only neighbour records, the
     // coordinates filled on demand (LIVO_REC_COMPACT=0: full records)
     bool rec_compact = true;
+    // LIVO_EVAL_GEN=1: every fused evaluation takes the generic kernel (the A/B and test reference
+    // of the static-map specialisation)
+    bool eval_gen = false;
     int last_lane = -1;             // lane of the batch enqueued last
     unsigned long long last_replays = 0;  // profiled batches: the replay counter read back
     IekfSlot* h_slots = nullptr;  // pinned
@@ -602,6 +605,7 @@ static KnnParams make_knn_params(livo_ctx* c) {
     kp.iv = ivox_params(c);
     kp.canon = c->dyn.active ? 1 : 0;
     kp.rec_compact = (LIVO_IDX_RUNS && c->rec_compact && vr && !c->dyn.active) ? 1 : 0;
+    kp.eval_gen = c->eval_gen ? 1 : 0;
     return kp;
 }
 
@@ -1888,6 +1892,7 @@ int livo_ctx_create(int device, const livo_params* p, livo_ctx** out) {
     if (const char* env = std::getenv("LIVO_SYNC_ZC")) c->sync_zc = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_SLOT_WB")) c->slot_wb = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_REC_COMPACT")) c->rec_compact = std::atoi(env) != 0;
+    if (const char* env = std::getenv("LIVO_EVAL_GEN")) c->eval_gen = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_XCD_CHUNK")) c->xcd_chunk = std::max(0, std::atoi(env));  // tuning knob
     if (const char* env = std::getenv("LIVO_GRID_PPC")) {  // tuning knob
         const float v = (float)std::atof(env);

@@ -401,6 +401,7 @@ struct KnnParams {
     // k_iekf_eval's run searches on a static map store the records' hot halves only
     // (kRecNoXyz; LIVO_REC_COMPACT=0: full records)
     int32_t rec_compact;
+    int32_t eval_gen;       // 1: launch_iekf_eval takes the generic kernel whatever the map (LIVO_EVAL_GEN=1)
 };
 
 struct SolveParams {
@@ -436,6 +437,14 @@ int launch_hshare(const HsParams& p, int n_jobs, int max_nblk, bool first, void*
 #define LIVO_EVAL_BLOCK 256
 #endif
 constexpr int kEvalBlock = LIVO_EVAL_BLOCK;  // threads (points) per block of k_iekf_eval
+// The fused kernel by search kind: k_iekf_eval is compiled for the index runs of a
+// static map alone (ball run, cell run, the serial walk beyond the cube; what
+// livo_map_build leaves), k_iekf_eval_gen for everything else (the LDS tile walk
+// without runs, the incremental map's run variants, delta searches and canonical order).
+enum EvalKind : int { kEvalRunsStatic = 0, kEvalGeneric = 1 };
+#ifndef LIVO_EVAL_WAVES
+#define LIVO_EVAL_WAVES 5  // waves per SIMD the static kernel's VGPR budget must allow (<= 96 VGPRs)
+#endif
 int launch_iekf_eval(const KnnParams& kp, const HsParams& hp, int n_jobs, int64_t max_n, bool first, void* stream);
 int launch_solve_ik(const HsParams& p, int n_jobs, void* stream);
 int launch_copy_words(const void* src, void* dst, size_t bytes, void* stream);  // 16-B aligned, bytes % 16 == 0

@@ -3346,25 +3346,33 @@ __device__ unsigned long long g_eval_tl[LIVO_MAX_EVALS][kTlBlocks][2];
 #define EVAL_MARK_SYNC(k) do { } while (0)
 #define EVAL_PROF_DECL do { } while (0)
 #endif
-#ifndef LIVO_EVAL_WAVES
-#define LIVO_EVAL_WAVES 4  // waves per SIMD the VGPR budget must allow (<= 128 VGPRs)
-#endif
-template <bool FIRST>
-__global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalParams E) {
+// The evaluation's LDS: the search's is dead (block barrier) before the reduction and solve use theirs
+struct EvalRsLds {
+    HsReduceLds R;
+    SolveLds solve;  // the scan's last block solves after its search is done
+};
+template <int KIND>
+union EvalLds {
+    BlockTile tile;  // the cell walk's block tile (no vertex runs: an incremental map)
+    EvalRsLds rs;
+    float4 nnstage[kEvalBlock / 64][64 * 4];  // each wave's 64 half records (the run searches)
+};
+template <>
+union EvalLds<kEvalRunsStatic> {  // (the run searches walk no tile)
+    EvalRsLds rs;
+    float4 nnstage[kEvalBlock / 64][64 * 4];
+};
+// KIND (livo_internal.h): kEvalRunsStatic compiles the static map's index-run searches alone
+// (the launcher's rule: vslots set, no dyn_runs, no canon), kEvalGeneric every search under
+// its kernel-parameter branches.
+template <bool FIRST, int KIND>
+__device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND>& U) {
+    constexpr bool kStatic = KIND == kEvalRunsStatic;
     const KnnParams& P = E.k;
     EVAL_PROF_DECL;
 #ifdef LIVO_EVAL_PROF
     const unsigned long long tl_start = __builtin_amdgcn_s_memtime();
 #endif
-    // the search's LDS is dead (block barrier) before the reduction and solve use theirs
-    __shared__ union {
-        BlockTile tile;  // the cell walk's block tile (no vertex runs: an incremental map)
-        struct {
-            HsReduceLds R;
-            SolveLds solve;  // the scan's last block solves after its search is done
-        } rs;
-        float4 nnstage[kEvalBlock / 64][64 * 4];  // each wave's 64 half records (the run searches)
-    } U;
     unsigned bjob, bx;
     // the same block order in every evaluation: the plane caches stay in the L2 that wrote them
     xcd_chunk_block(P.nb, P.xcd_chunk, bjob, bx);
@@ -3373,9 +3381,9 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
     if (bx > 0 && (int)bx * kEvalBlock >= job.n) return;  // (an empty scan keeps one block: it solves)
     const int i = (int)bx * kEvalBlock + threadIdx.x;
     const bool valid = i < job.n;
-    // the point's loads go out with the slot's control reads (after the first
-    // evaluation the plane cache too: used unless this evaluation searches)
-    HsPointIn pin = valid ? hshare_load(job, i, !FIRST) : HsPointIn{};
+    // after the first evaluation the point's loads (body point, plane cache) go out
+    // with the slot's control reads: an evaluation without a search runs on them
+    HsPointIn pin = !FIRST && valid ? hshare_load(job, i, true) : HsPointIn{};
     bool prefit = false;  // the plane of this evaluation fitted in the search branch
     if (slot->ctrl.stop) return;  // block-uniform
     const int search = FIRST ? 1 : slot->ctrl.search_en;
@@ -3390,13 +3398,17 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
         // less than reading their record cost (rematch 0.156 vs 0.159 ms, 18991 vs
         // 18643 updates/s, profiles/r03_ab_prefit_seed.txt); the answer is the
         // same exact list either way
+        // (a search holds no point registers: it fits the planes from its own lists or
+        // the records, and the body point, in cache since lq_init, is read again after it)
+        pin = HsPointIn{};
         LeafQuery q;
         lq_init<false>(q, P, pose, job, i, valid);
         int c0 = 0, c1 = 0, c2 = 0, s0 = 1, s1 = 1, s2 = 1;
         if (valid) grid_cell(P, q, c0, c1, c2, s0, s1, s2);
         unsigned visits = 0, npts = 0;
         bool amb = false;
-        if (P.vslots) {  // (kernel parameter: uniform)
+        const bool canon = !kStatic && P.canon;  // (kernel parameter: uniform)
+        if (kStatic || P.vslots) {  // (kernel parameter: uniform)
             EVAL_MARK(1);
             bool certified = false;
             const float4* runs = reinterpret_cast<const float4*>(P.vpts);  // (float4 run entries only)
@@ -3405,7 +3417,7 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
             bool ball_ok = false;
 #endif
 #if LIVO_IDX_RUNS
-            const bool dyn = P.dyn_runs != 0;  // (uniform) runs on the incremental map
+            const bool dyn = !kStatic && P.dyn_runs != 0;  // (uniform) runs on the incremental map
 #else
             constexpr bool dyn = false;
 #endif
@@ -3478,7 +3490,7 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
             // hot-only records (kRecNoXyz) on a static map: the loop's later evaluations read
             // the plane cache, a plane state 0 point its coordinates through the keys
 #if LIVO_IDX_RUNS
-            const bool compact = P.rec_compact && !dyn && !P.canon;  // (uniform)
+            const bool compact = P.rec_compact && !dyn && !canon;  // (uniform)
 #else
             constexpr bool compact = false;  // (float4 runs: a key may lie in either run array)
 #endif
@@ -3528,7 +3540,7 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
                 // the plane from the neighbours in registers (18643 vs 18011 updates/s
                 // re-reading the record just written, profiles/r03_ab_prefit_seed.txt), after
                 // the stage took them: they are not held across the stores
-                if (valid && !amb && (!P.canon || dyn)) {  // (a replayed query's plane is fitted from its record below)
+                if (valid && !amb && (!canon || dyn)) {  // (a replayed query's plane is fitted from its record below)
                     float4 pl;
                     pin.ps = fit_plane(E.h, job, i, 1, nb, (int)min<int64_t>(P.lM, (int64_t)kNN), pl);
                     pin.plane = pl;
@@ -3538,7 +3550,7 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
                 if (__ballot(amb)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             EVAL_MARK(6);
-        } else {
+        } else if constexpr (!kStatic) {
             const TileView tv = build_tile<kEvalBlock>(U.tile, P, valid, c0, c1, c2, visits, npts);
             EVAL_MARK(1);
             if (valid) {
@@ -3553,8 +3565,9 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
         }
         n_slots = visits;
         n_pts = npts;
+        if (valid) pin.pb = reinterpret_cast<const float4*>(job.pts)[i];
         if (amb) atomicAdd(P.replay_total, 1ull);
-        if (P.canon) {  // (kernel parameter: uniform) the incremental map's exact resolution
+        if (canon) {  // (kernel parameter: uniform) the incremental map's exact resolution
             if (amb) canon_query(P, job, i, pose);
             __syncthreads();  // the tile's LDS is reused by the solve
         } else if (__syncthreads_or(amb)) {  // block-uniform: some query of this block is flagged
@@ -3595,6 +3608,17 @@ __global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalP
         g_eval_tl[tl_e][blockIdx.x][1] = __builtin_amdgcn_s_memtime();
     }
 #endif
+}
+// the static map's kernel (livo_map_build, the batch farm) and the generic one
+template <bool FIRST>
+__global__ __launch_bounds__(kEvalBlock, LIVO_EVAL_WAVES) void k_iekf_eval(EvalParams E) {
+    __shared__ EvalLds<kEvalRunsStatic> U;
+    iekf_eval_body<FIRST, kEvalRunsStatic>(E, U);
+}
+template <bool FIRST>
+__global__ __launch_bounds__(kEvalBlock, 4) void k_iekf_eval_gen(EvalParams E) {
+    __shared__ EvalLds<kEvalGeneric> U;
+    iekf_eval_body<FIRST, kEvalGeneric>(E, U);
 }
 
 // Per-point persistent selection of the IKFoM h-model: point_selected_surf is a
@@ -4380,10 +4404,19 @@ int launch_iekf_eval(const KnnParams& kp, const HsParams& hp, int n_jobs, int64_
     E.k.nb = (int32_t)((max_n + kEvalBlock - 1) / kEvalBlock);
     if ((int64_t)E.k.nb * n_jobs >= (1ll << 31)) return LIVO_E_RANGE;
     const dim3 grid((unsigned)(E.k.nb * n_jobs)), block(kEvalBlock);
-    if (first)
-        hipLaunchKernelGGL(k_iekf_eval<true>, grid, block, 0, (hipStream_t)stream, E);
-    else
-        hipLaunchKernelGGL(k_iekf_eval<false>, grid, block, 0, (hipStream_t)stream, E);
+    // the static kind: index runs of a static map (what livo_map_build leaves)
+    const bool stat = LIVO_IDX_RUNS && kp.vslots && !kp.dyn_runs && !kp.canon && !kp.eval_gen;
+    if (stat) {
+        if (first)
+            hipLaunchKernelGGL(k_iekf_eval<true>, grid, block, 0, (hipStream_t)stream, E);
+        else
+            hipLaunchKernelGGL(k_iekf_eval<false>, grid, block, 0, (hipStream_t)stream, E);
+    } else {
+        if (first)
+            hipLaunchKernelGGL(k_iekf_eval_gen<true>, grid, block, 0, (hipStream_t)stream, E);
+        else
+            hipLaunchKernelGGL(k_iekf_eval_gen<false>, grid, block, 0, (hipStream_t)stream, E);
+    }
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 
