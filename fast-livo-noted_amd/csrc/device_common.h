@@ -156,6 +156,23 @@ __device__ __forceinline__ void xcd_chunk_block(int nb, int C, unsigned& job, un
     bx = wgid % (unsigned)nb;
 }
 
+// The slot of `key` in an open-addressing table of 2^log2 GridSlots (linear
+// probing, load factor <= 1/4), or the empty slot that ends its probe sequence
+// (key != `key`); every slot read counts one visit.
+__device__ __forceinline__ GridSlot grid_find(const GridSlot* __restrict__ slots, int log2, unsigned long long key,
+                                              unsigned& visits) {
+    const uint64_t mask = (1ull << log2) - 1ull;
+    uint64_t sl = grid_hash(key, log2);
+    GridSlot g = slots[sl];
+    visits++;
+    while (g.key != key && g.key != kGridEmpty) {
+        sl = (sl + 1) & mask;
+        g = slots[sl];
+        visits++;
+    }
+    return g;
+}
+
 // Centre of grid cell v along one axis, and the squared distance of a point to
 // a cell centre: the cell runs' sort key (k_cr_rho) and the search's
 // termination test (vrun_search) use exactly these operations, so both see

@@ -88,13 +88,8 @@ __device__ __forceinline__ bool in_two(unsigned long long k, float ds, float x, 
 // Run {start, count} of grid cell (x, y, z); count 0 if empty.
 __device__ __forceinline__ uint2 cell_run(const GridSlot* __restrict__ slots, int log2, int x, int y, int z) {
     const unsigned long long key = pack_key(x, y, z);
-    const uint64_t mask = (1ull << log2) - 1ull;
-    uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2));
-    GridSlot g = slots[sl];
-    while (g.key != key && g.key != kGridEmpty) {
-        sl = (sl + 1) & mask;
-        g = slots[sl];
-    }
+    unsigned visits = 0;  // (not counted here)
+    const GridSlot g = grid_find(slots, log2, key, visits);
     return g.key == key ? make_uint2(g.start, g.count) : make_uint2(0u, 0u);
 }
 // Grid cells that can hold a point of the box (with the grid's rounding slack).
@@ -112,6 +107,7 @@ __device__ __forceinline__ bool box_cells(const DynAddParams& P, const DBox& b, 
 }
 
 // ------------------------------------------------------------ Add_Points ----
+// (the dirty-box set, not a GridSlot table: its own shift and mask, capacity not 2^log2 of a grid)
 __device__ __forceinline__ uint32_t dirty_slot(unsigned long long key, uint32_t cap) {
     return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 40) & (cap - 1u);
 }
@@ -1050,7 +1046,7 @@ __global__ void k_dyn_slots(const unsigned long long* __restrict__ skeys, const 
     const uint32_t s0 = starts[g], s1 = starts[g + 1];
     const unsigned long long key = skeys[s0];
     const uint64_t mask = (1ull << log2) - 1ull;
-    uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2));
+    uint64_t sl = grid_hash(key, log2);
     while (atomicCAS(&slots[sl].key, kGridEmpty, key) != kGridEmpty) sl = (sl + 1) & mask;
     slots[sl].start = s0;
     slots[sl].count = s1 - s0;
@@ -1095,17 +1091,6 @@ __global__ void k_cr_key(const float4* __restrict__ gpts, const uint32_t* __rest
     float rho2;
     cr_entry(G, gpts[e / 27u], e % 27u, v, rho2);
     keys[i] = cr_key(v);
-}
-__global__ void k_cr_fill(const float4* __restrict__ gpts, const uint32_t* __restrict__ e2,
-                          const unsigned long long* __restrict__ skeys, int64_t n, float4* vpts, uint32_t* heads) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n + 8) return;
-    if (i >= n) {  // chunk padding of the run scan (never inside a run: masked by the run length)
-        vpts[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    vpts[i] = gpts[e2[i] / 27u];  // x, y, z, map index bits
-    heads[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1u : 0u;
 }
 
 // ---- ball runs (livo_internal.h), built on the device from the cell grid ----
@@ -1174,19 +1159,7 @@ __global__ void k_br_gather_keys(const unsigned long long* __restrict__ keys, co
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = keys[e1[i]];
 }
-__global__ void k_br_fill(const float4* __restrict__ gpts, const uint32_t* __restrict__ pt,
-                          const uint32_t* __restrict__ e2, const unsigned long long* __restrict__ skeys, int64_t n,
-                          float4* bpts, uint32_t* heads) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n + 8) return;
-    if (i >= n) {  // chunk padding of the run scan
-        bpts[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    bpts[i] = gpts[pt[e2[i]]];  // x, y, z, map index bits
-    heads[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1u : 0u;
-}
-// ---- index runs (LIVO_IDX_RUNS): a run = an aligned segment of grid positions ----
+// ---- index runs: a run = an aligned segment of grid positions ----
 __global__ void k_run_heads(const unsigned long long* __restrict__ skeys, int64_t n, uint32_t* heads) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) heads[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1u : 0u;
@@ -1212,7 +1185,7 @@ __global__ void k_run_slots(const unsigned long long* __restrict__ skeys, const 
     const uint32_t s0 = starts[r], s1 = starts[r + 1];
     const unsigned long long key = skeys[s0];
     const uint64_t mask = (1ull << log2) - 1ull;
-    uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2));
+    uint64_t sl = grid_hash(key, log2);
     while (atomicCAS(&slots[sl].key, kGridEmpty, key) != kGridEmpty) sl = (sl + 1) & mask;
     slots[sl].start = pstart[r];
     slots[sl].count = s1 - s0;
@@ -1375,13 +1348,6 @@ int launch_cr_key(const float* gpts, const uint32_t* e1, int64_t n, const float 
     const CrGeo G{{org[0], org[1], org[2]}, h, 1.0f / h};
     DYN_LAUNCH(k_cr_key, n, reinterpret_cast<const float4*>(gpts), e1, n, G, keys);
 }
-int launch_cr_fill(const float* gpts, const uint32_t* e2, const unsigned long long* skeys, int64_t n,
-                   const float org[3], float h, float* vpts, uint32_t* heads, void* stream) {
-    (void)org;
-    (void)h;
-    DYN_LAUNCH(k_cr_fill, n + 8, reinterpret_cast<const float4*>(gpts), e2, skeys, n,
-               reinterpret_cast<float4*>(vpts), heads);
-}
 static BrGeo br_geo(const float org[3], float h, float rmax, int x0, int x1) {
     return BrGeo{{org[0], org[1], org[2]}, h, 1.0f / h, rmax, rmax * rmax, x0, x1};
 }
@@ -1414,7 +1380,7 @@ __global__ void k_trip_slots(const GridSlot* __restrict__ trip, int64_t nruns, G
     if (r >= nruns) return;
     const GridSlot g = trip[r];
     const uint64_t mask = (1ull << log2) - 1ull;
-    uint64_t sl = (uint64_t)((g.key * 0x9E3779B97F4A7C15ull) >> (64 - log2));
+    uint64_t sl = grid_hash(g.key, log2);
     while (atomicCAS(&slots[sl].key, kGridEmpty, g.key) != kGridEmpty) sl = (sl + 1) & mask;
     slots[sl].start = g.start;
     slots[sl].count = g.count;
@@ -1429,11 +1395,6 @@ int launch_trip_slots(const GridSlot* trip, int64_t nruns, GridSlot* slots, int 
 int launch_br_gather_keys(const unsigned long long* keys, const uint32_t* e1, int64_t n, unsigned long long* out,
                           void* stream) {
     DYN_LAUNCH(k_br_gather_keys, n, keys, e1, n, out);
-}
-int launch_br_fill(const float* gpts, const uint32_t* pt, const uint32_t* e2, const unsigned long long* skeys,
-                   int64_t n, float* bpts, uint32_t* heads, void* stream) {
-    DYN_LAUNCH(k_br_fill, n + 8, reinterpret_cast<const float4*>(gpts), pt, e2, skeys, n,
-               reinterpret_cast<float4*>(bpts), heads);
 }
 int launch_add_u32(uint32_t* v, int64_t n, uint32_t add, void* stream) { DYN_LAUNCH(k_add_u32, n, v, n, add); }
 int launch_dyn_rpos(const float* rpts, int64_t base_n, uint32_t* rpos, void* stream) {

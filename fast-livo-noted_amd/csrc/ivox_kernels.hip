@@ -47,9 +47,7 @@ __device__ __forceinline__ unsigned long long iv_key(int cx, int cy, int cz) {
     return (unsigned long long)(cx + kIvBias) | ((unsigned long long)(cy + kIvBias) << 21) |
            ((unsigned long long)(cz + kIvBias) << 42);
 }
-__device__ __forceinline__ uint64_t iv_hash(unsigned long long key, int log2) {
-    return (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2));
-}
+__device__ __forceinline__ uint64_t iv_hash(unsigned long long key, int log2) { return grid_hash(key, log2); }
 // Pos2Grid on one axis: round(v * inv_resolution) (float product, half away
 // from zero); false beyond `lim` cells (and for NaN).
 __device__ __forceinline__ bool iv_cell(float v, float inv, float lim, int& c) {
@@ -492,17 +490,6 @@ __device__ __forceinline__ bool ivox_wave_query(const KnnParams& P, const HsJob&
         base += __popcll(m);
     }
     wave_sync();
-#ifdef LIVO_IV_DEBUG_Q
-#define IVDBG(tag, cnt)                                                                        \
-    if (i == LIVO_IV_DEBUG_Q && lane == 0) {                                                   \
-        printf("%s n=%d:", tag, (int)(cnt));                                                   \
-        for (int z = 0; z < (int)(cnt); z++) printf(" (%.8f,%u,%d)", L.d[z], L.id[z], (int)L.node[z]); \
-        printf("\n");                                                                           \
-    }
-#else
-#define IVDBG(tag, cnt)
-#endif
-    IVDBG("staged", base);
     if (base == 0) return false;  // no candidate: the reference returns false, the cache stays
     // per grid: KNNPointByCondition's nth_element on its own run (ivox3d_node.hpp:179-183)
     const uint32_t mt = lane < V.nearby ? L.m[lane] : 0u;
@@ -526,7 +513,6 @@ __device__ __forceinline__ bool ivox_wave_query(const KnnParams& P, const HsJob&
         if (m > K) {
             const int s0 = (int)__shfl(S, tt, 64);
             ok = wave_nth(L, s0, s0 + K - 1, s0 + m, lane);
-            IVDBG("pernode", base);
         }
     }
     if (ok) {
@@ -555,15 +541,12 @@ __device__ __forceinline__ bool ivox_wave_query(const KnnParams& P, const HsJob&
                 L.id[dst[r]] = cid[r];
             }
         wave_sync();
-        IVDBG("compact", n_final);
         int n = n_final;
         if (n > K) {  // ivox3d.h:173-177
             ok = wave_nth(L, 0, K - 1, n, lane);
             n = K;
         }
-        IVDBG("nth4", n);
         if (ok) ok = wave_nth(L, 0, 0, n, lane);  // ivox3d.h:178
-        IVDBG("final", n);
         if (ok) {
             wave_write(job.nn + i, pts, L, n, lane);
             return false;

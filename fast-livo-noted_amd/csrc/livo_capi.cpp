@@ -126,8 +126,8 @@ struct DynDev {
     unsigned long long *dirty = nullptr, *ctr = nullptr;
     int64_t gslot_cap = 0, gpts_cap = 0;  // capacities of ctx->gslots / ctx->gpts
     livo_map_add_stats last{};
-    // The IEKF search keeps the cell and ball runs on the incremental map
-    // (LIVO_IDX_RUNS): the runs index the base point set rpts (the map's points
+    // The IEKF search keeps the cell and ball runs on the incremental map:
+    // the runs index the base point set rpts (the map's points
     // in grid order when the runs were built; ids below base_ids), a deleted
     // base point is marked in rpts (x = NaN, never a candidate of the run scans), and
     // the points added since are searched in the delta grid (dslots / dpts, the
@@ -142,7 +142,7 @@ struct DynDev {
     float* dpts = nullptr;
     int32_t dlog2 = 4;
     GridSlot* dvslots = nullptr;     // the delta grid's cell runs (positions in dpts)
-    RunWord* dvidx = nullptr;
+    uint32_t* dvidx = nullptr;
     int32_t dvlog2 = 4;
     int64_t d_n = 0, dslot_cap = 0, dpts_cap = 0;
     int64_t rebases = 0;
@@ -230,7 +230,7 @@ struct livo_ctx {
     // most expensive scan's XCD was the straggler; profiles/r04_ab_block_order.txt)
     int xcd_chunk = 8;
     GridSlot* vslots = nullptr;        // vertex runs (static map only)
-    RunWord* vpts = nullptr;           // run entries (LIVO_IDX_RUNS: grid positions; else x, y, z, map index bits)
+    uint32_t* vpts = nullptr;          // run entries: grid positions (indices into gpts)
     int32_t vlog2 = 0;
     // ball runs (static map only): anchor cells of edge bh, runs of radius brmax
     bool bruns = true;                 // LIVO_BRUNS=0: the cell runs only
@@ -242,7 +242,7 @@ struct livo_ctx {
     // (profiles/r04_ab_ball_radius.txt)
     float br_ha = 2.0f, br_r = 6.0f;
     GridSlot* bslots = nullptr;
-    RunWord* bpts = nullptr;
+    uint32_t* bpts = nullptr;
     int32_t blog2 = 0;
     float bh = 0.f, brmax = 0.f, br5 = 0.f;
     int64_t bentries = 0;
@@ -604,7 +604,7 @@ static KnnParams make_knn_params(livo_ctx* c) {
     kp.identity = 0;
     kp.iv = ivox_params(c);
     kp.canon = c->dyn.active ? 1 : 0;
-    kp.rec_compact = (LIVO_IDX_RUNS && c->rec_compact && vr && !c->dyn.active) ? 1 : 0;
+    kp.rec_compact = (c->rec_compact && vr && !c->dyn.active) ? 1 : 0;
     kp.eval_gen = c->eval_gen ? 1 : 0;
     return kp;
 }
@@ -1168,10 +1168,8 @@ static ScanBuf* get_scan_q(livo_ctx* c, int32_t id);
 }
 static int build_cell_runs(livo_ctx* c, int64_t M);
 static int build_ball_runs(livo_ctx* c, int64_t M, float r5, double ext);
-#if LIVO_IDX_RUNS
-static int build_cell_runs_into(livo_ctx* c, const float* pts, int64_t M, GridSlot** slots, RunWord** idx,
+static int build_cell_runs_into(livo_ctx* c, const float* pts, int64_t M, GridSlot** slots, uint32_t** idx,
                                 int32_t* log2, int64_t* words);
-#endif
 static void dyn_free(DynDev& d) {
     dev_free(d.all); dev_free(d.alive);
     dev_free(d.keys); dev_free(d.skeys); dev_free(d.iota); dev_free(d.svals);
@@ -1402,7 +1400,6 @@ static int dyn_runs_update(livo_ctx* c) {
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     d.dlog2 = log2;
-#if LIVO_IDX_RUNS
     // and its cell runs: a query scans its cube's delta points in one run, as the base's
     int64_t words = 0;
     rc = build_cell_runs_into(c, d.dpts, nd, &d.dvslots, &d.dvidx, &d.dvlog2, &words);
@@ -1412,7 +1409,6 @@ static int dyn_runs_update(livo_ctx* c) {
         dev_free(d.dvidx);
         return rc == LIVO_E_OOM || rc == LIVO_E_RANGE ? dyn_rebase(c) : rc;
     }
-#endif
     return LIVO_OK;
 }
 
@@ -1466,7 +1462,7 @@ static int dyn_activate(livo_ctx* c) {
     // them (marks, delta grid and runs, rebases) takes Add_Points from 0.56 to
     // 1.34 ms, so the odometry loop runs at half the rate.
     const char* env_runs = std::getenv("LIVO_DYN_RUNS");
-    if (LIVO_IDX_RUNS && c->vslots && c->vpts && M > 0 && env_runs && std::atoi(env_runs) == 1) {
+    if (c->vslots && c->vpts && M > 0 && env_runs && std::atoi(env_runs) == 1) {
         rc = dyn_base_from_grid(c);  // the built map's runs index its grid: the grid becomes the base
         if (rc == LIVO_E_OOM) {
             (void)hipGetLastError();
@@ -2023,7 +2019,6 @@ int livo_last_timings(livo_ctx* c, livo_timings* out) {
     return LIVO_OK;
 }
 
-#if LIVO_IDX_RUNS
 // Index runs from n key-sorted entries (skeys; e2 / pt give each entry's grid
 // position, as k_run_place): heads, run ids, run starts, lengths rounded up to
 // 4, their exclusive scan (pstart) and the placed positions in *out (the
@@ -2031,7 +2026,7 @@ int livo_last_timings(livo_ctx* c, livo_timings* out) {
 // (load factor <= 1/4).  plen / pstart: scratch of n + 1 words each.
 static int build_index_runs(livo_ctx* c, int64_t n, const unsigned long long* skeys, const uint32_t* e2,
                             const uint32_t* pt, uint32_t* heads, uint32_t* runid, uint32_t* starts,
-                            unsigned long long* nruns_dev, uint32_t* plen, uint32_t* pstart, RunWord** out,
+                            unsigned long long* nruns_dev, uint32_t* plen, uint32_t* pstart, uint32_t** out,
                             GridSlot** slots, int* log2_out, int64_t* words) {
     int rc = launch_run_heads(skeys, n, heads, c->stream);
     if (!rc) rc = ivox_scan(c, heads, runid, n);
@@ -2053,7 +2048,7 @@ static int build_index_runs(livo_ctx* c, int64_t n, const unsigned long long* sk
     const int64_t total = (int64_t)tail[0] + tail[1];  // (u32 lengths: the scan wraps beyond 2^32 words)
     if (total < n || total + kRunPad >= (int64_t)0xFFFFFFFFll) return LIVO_E_RANGE;
     if (dev_alloc(out, (size_t)(total + kRunPad))) return LIVO_E_OOM;
-    rc = hipMemsetAsync(*out, 0, (size_t)(total + kRunPad) * sizeof(RunWord), c->stream) == hipSuccess ? LIVO_OK
+    rc = hipMemsetAsync(*out, 0, (size_t)(total + kRunPad) * sizeof(uint32_t), c->stream) == hipSuccess ? LIVO_OK
                                                                                                          : LIVO_E_HIP;
     if (!rc) rc = launch_run_place(e2, pt, heads, runid, starts, pstart, n, *out, c->stream);
     int log2 = 4;
@@ -2072,34 +2067,23 @@ static int build_index_runs(livo_ctx* c, int64_t n, const unsigned long long* sk
     *words = total + kRunPad;
     return LIVO_OK;
 }
-#endif
 
 // The cell runs of the static map's grid (livo_internal.h), built on the
 // device: two stable radix sorts (rho2, then the run key) of the 27 M entries,
 // the runs' heads and starts, and their hash table (load factor <= 1/4).
-#if LIVO_IDX_RUNS
-static int build_cell_runs_into(livo_ctx* c, const float* pts, int64_t M, GridSlot** slots, RunWord** idx,
-                                int32_t* log2, int64_t* words);
 static int build_cell_runs(livo_ctx* c, int64_t M) {
     int64_t words = 0;
     const int rc = build_cell_runs_into(c, c->gpts, M, &c->vslots, &c->vpts, &c->vlog2, &words);
-    if (!rc && M > 0) c->grid_bytes += (int64_t)(((int64_t)1 << c->vlog2) * sizeof(GridSlot) + words * sizeof(RunWord));
+    if (!rc && M > 0) c->grid_bytes += (int64_t)(((int64_t)1 << c->vlog2) * sizeof(GridSlot) + words * sizeof(uint32_t));
     return rc;
 }
 // The cell runs of M grid-ordered points pts (the map's grid; on the incremental
 // map also its delta grid): *slots / *idx replaced, run entries = positions in pts.
-static int build_cell_runs_into(livo_ctx* c, const float* pts, int64_t M, GridSlot** slots, RunWord** idx,
+static int build_cell_runs_into(livo_ctx* c, const float* pts, int64_t M, GridSlot** slots, uint32_t** idx,
                                 int32_t* log2, int64_t* words) {
     dev_free(*slots);
     dev_free(*idx);
     if (M <= 0) return LIVO_OK;
-#else
-static int build_cell_runs(livo_ctx* c, int64_t M) {
-    const float* pts = c->gpts;
-    dev_free(c->vslots);
-    dev_free(c->vpts);
-    if (M <= 0) return LIVO_OK;
-#endif
     const int64_t n = M * 27;
     if (n + 8 >= (int64_t)kRunPosLimit) return LIVO_E_RANGE;  // 31-bit run positions (kRunPos)
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -2118,11 +2102,7 @@ static int build_cell_runs(livo_ctx* c, int64_t M) {
     unsigned long long* skeys = (unsigned long long*)p; p += b8;
     uint32_t* starts = (uint32_t*)p; p += al(((size_t)n + 1) * 4);
     unsigned long long* nruns = (unsigned long long*)p;
-    int rc = LIVO_OK;
-#if !LIVO_IDX_RUNS
-    if (dev_alloc(&c->vpts, (size_t)(n + kRunPad) * kRunWords)) rc = LIVO_E_OOM;
-#endif
-    if (!rc) rc = launch_cr_rho(pts, n, c->gorg, c->gh, rho, iota, c->stream);
+    int rc = launch_cr_rho(pts, n, c->gorg, c->gh, rho, iota, c->stream);
     if (!rc) {
         size_t tb = 0;
         rc = prim_sort_pairs_u32(nullptr, &tb, rho, srho, iota, e1, n, 32, c->stream);
@@ -2132,39 +2112,13 @@ static int build_cell_runs(livo_ctx* c, int64_t M) {
     }
     if (!rc) rc = launch_cr_key(pts, e1, n, c->gorg, c->gh, keys, c->stream);
     if (!rc) rc = sort_u64(c, keys, skeys, e1, e2, n);
-#if LIVO_IDX_RUNS
     // (rho, iota: dead after the sorts) the padded run lengths and their scan
     if (!rc) rc = build_index_runs(c, n, skeys, e2, nullptr, heads, runid, starts, nruns, rho, iota, idx, slots, log2,
                                    words);
     (void)hipFree(scr);
     return rc;
-#else
-    if (!rc) rc = launch_cr_fill(pts, e2, skeys, n, c->gorg, c->gh, c->vpts, heads, c->stream);
-    if (!rc) rc = ivox_scan(c, heads, runid, n);
-    if (!rc) rc = launch_dyn_runs(heads, runid, n, starts, nruns, c->stream);
-    unsigned long long runs = 0;
-    if (!rc && hipMemcpyAsync(&runs, nruns, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    int log2 = 4;
-    while (((int64_t)1 << log2) < 4 * (int64_t)runs) log2++;
-    const int64_t table = (int64_t)1 << log2;
-    if (!rc && dev_alloc(&c->vslots, (size_t)table)) rc = LIVO_E_OOM;
-    if (!rc) rc = launch_ivox_clear(c->vslots, table, c->stream);
-    if (!rc) rc = launch_dyn_slots(skeys, starts, (int64_t)runs, c->vslots, log2, c->stream);
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    (void)hipFree(scr);
-    if (rc) {
-        dev_free(c->vslots);
-        dev_free(c->vpts);
-        return rc;
-    }
-    c->vlog2 = log2;
-    c->grid_bytes += (int64_t)(table * sizeof(GridSlot) + (size_t)(n + kRunPad) * 16);
-    return LIVO_OK;
-#endif
 }
 
-#if LIVO_IDX_RUNS
 // The index ball runs, built in chunks of anchors (their x index in [x0, x1)),
 // each chunk at most `cap` entries (LIVO_BR_CHUNK, default 2^29: ~26 GB of sort
 // scratch), so the 32-bit sort indices and offsets of one chunk never wrap
@@ -2172,8 +2126,8 @@ static int build_cell_runs(livo_ctx* c, int64_t M) {
 // 2^31).  A chunk is counted, placed behind the runs of the chunks before it in
 // one run array (every run starts on a 4-word boundary), and its runs recorded
 // as {key, start / 4, count}; the hash table then takes every record, so a slot's
-// start addresses 2^34 words.  The runs' contents and order are those of the
-// one-pass build.
+// start addresses 2^34 words.  The runs' contents and order do not depend on
+// the chunking.
 static int build_ball_runs_idx(livo_ctx* c, int64_t M, float r5, float bh, float brmax, double ext) {
     int64_t cap = (int64_t)1 << 29;
     if (const char* env = std::getenv("LIVO_BR_CHUNK")) cap = std::max<int64_t>(1 << 16, std::atoll(env));
@@ -2235,7 +2189,7 @@ static int build_ball_runs_idx(livo_ctx* c, int64_t M, float r5, float bh, float
     // the run array: the entries plus the padding of every run to 4 words (grown if short)
     int64_t words_cap = total_entries + total_entries / 8 + 4096 + kRunPad;
     if (dev_alloc(&c->bpts, (size_t)words_cap) ||
-        hipMemsetAsync(c->bpts, 0, (size_t)words_cap * sizeof(RunWord), c->stream) != hipSuccess) {
+        hipMemsetAsync(c->bpts, 0, (size_t)words_cap * sizeof(uint32_t), c->stream) != hipSuccess) {
         dev_free(cnt);
         dev_free(off);
         dev_free(c->bpts);
@@ -2307,13 +2261,13 @@ static int build_ball_runs_idx(livo_ctx* c, int64_t M, float r5, float bh, float
         }
         if (base + words + kRunPad > words_cap) {  // more padding than reserved: grow the run array
             const int64_t ncap = (base + words + kRunPad) + (base + words) / 8;
-            RunWord* nb = nullptr;
+            uint32_t* nb = nullptr;
             if (dev_alloc(&nb, (size_t)ncap)) {
                 rc = LIVO_E_OOM;
                 break;
             }
-            if (hipMemsetAsync(nb, 0, (size_t)ncap * sizeof(RunWord), c->stream) != hipSuccess ||
-                hipMemcpyAsync(nb, c->bpts, (size_t)base * sizeof(RunWord), hipMemcpyDeviceToDevice, c->stream) !=
+            if (hipMemsetAsync(nb, 0, (size_t)ncap * sizeof(uint32_t), c->stream) != hipSuccess ||
+                hipMemcpyAsync(nb, c->bpts, (size_t)base * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream) !=
                     hipSuccess ||
                 hipStreamSynchronize(c->stream) != hipSuccess)
                 rc = LIVO_E_HIP;
@@ -2372,17 +2326,16 @@ static int build_ball_runs_idx(livo_ctx* c, int64_t M, float r5, float bh, float
     c->br5 = r5;
     c->bentries = total_entries;
     c->bchunks = (int32_t)chunks.size();
-    c->grid_bytes += (int64_t)(((int64_t)1 << log2) * sizeof(GridSlot) + words_cap * sizeof(RunWord));
+    c->grid_bytes += (int64_t)(((int64_t)1 << log2) * sizeof(GridSlot) + words_cap * sizeof(uint32_t));
     return LIVO_OK;
 }
-#endif
 
 // The ball runs of the static map (livo_internal.h KnnParams::bslots), built on
 // the device: every grid point emits one entry per anchor cell (edge bh) whose
 // centre lies within brmax (k_br_count, a scan, k_br_emit); a stable radix sort
 // by rho2, a gather of the anchor keys and a stable sort by key leave each
-// anchor's run contiguous and sorted by rho2; heads, starts and the hash table
-// as for the cell runs.  r5: the map's median 5-NN distance (sample_knn_radius).
+// anchor's run contiguous and sorted by rho2 (build_ball_runs_idx, chunk by
+// chunk).  r5: the map's median 5-NN distance (sample_knn_radius).
 static int build_ball_runs(livo_ctx* c, int64_t M, float r5, double ext) {
     dev_free(c->bslots);
     dev_free(c->bpts);
@@ -2395,111 +2348,7 @@ static int build_ball_runs(livo_ctx* c, int64_t M, float r5, double ext) {
     // ball radius) spans that many anchors keeps the cell runs only, rather
     // than letting keys alias into a run not sorted about its own anchor
     if ((ext + 2.0 * (double)brmax) / (double)bh + 4.0 >= (double)(kGridBias - 8)) return LIVO_OK;
-#if LIVO_IDX_RUNS
     return build_ball_runs_idx(c, M, r5, bh, brmax, ext);
-#endif
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    uint32_t* cnt = nullptr;
-    uint32_t* off = nullptr;
-    unsigned long long* tot = nullptr;
-    if (dev_alloc(&cnt, (size_t)M) || dev_alloc(&off, (size_t)M) || dev_alloc(&tot, 1)) {
-        dev_free(cnt);
-        dev_free(off);
-        dev_free(tot);
-        return LIVO_E_OOM;
-    }
-    int rc = hipMemsetAsync(tot, 0, 8, c->stream) == hipSuccess ? LIVO_OK : LIVO_E_HIP;
-    if (!rc) rc = launch_br_count(c->gpts, M, c->gorg, bh, brmax, cnt, tot, c->stream);
-    if (!rc) rc = ivox_scan(c, cnt, off, M);
-    unsigned long long n64 = 0;
-    if (!rc && hipMemcpyAsync(&n64, tot, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    dev_free(cnt);
-    dev_free(tot);
-    // 31-bit run positions (kRunPos) and u32 offsets; a map too dense for the ball keeps the cell runs
-    if (rc || n64 == 0 || (int64_t)n64 + 8 >= (int64_t)kRunPosLimit) {
-        dev_free(off);
-        return rc;
-    }
-    const int64_t n = (int64_t)n64;
-    const size_t b4 = al((size_t)n * 4), b8 = al((size_t)n * 8);
-    char* scr = nullptr;
-    if (hipMalloc((void**)&scr, 7 * b4 + 3 * b8 + al(((size_t)n + 1) * 4) + 256) != hipSuccess) {
-        dev_free(off);
-        return LIVO_E_OOM;
-    }
-    char* p = scr;
-    uint32_t* rho = (uint32_t*)p; p += b4;
-    uint32_t* iota = (uint32_t*)p; p += b4;
-    uint32_t* srho = (uint32_t*)p; p += b4;
-    uint32_t* e1 = (uint32_t*)p; p += b4;
-    uint32_t* e2 = (uint32_t*)p; p += b4;
-    uint32_t* pt = (uint32_t*)p; p += b4;
-    uint32_t* heads = (uint32_t*)p; p += b4;
-    unsigned long long* keys = (unsigned long long*)p; p += b8;
-    unsigned long long* key1 = (unsigned long long*)p; p += b8;
-    unsigned long long* skeys = (unsigned long long*)p; p += b8;
-    uint32_t* starts = (uint32_t*)p; p += al(((size_t)n + 1) * 4);
-    unsigned long long* nruns = (unsigned long long*)p;
-    uint32_t* runid = rho;  // (rho is dead after the first sort)
-#if !LIVO_IDX_RUNS
-    if (dev_alloc(&c->bpts, (size_t)(n + kRunPad) * kRunWords)) rc = LIVO_E_OOM;
-#endif
-    if (!rc) rc = launch_br_emit(c->gpts, M, c->gorg, bh, brmax, off, rho, keys, pt, iota, c->stream);
-    if (!rc) {
-        size_t tb = 0;
-        rc = prim_sort_pairs_u32(nullptr, &tb, rho, srho, iota, e1, n, 32, c->stream);
-        if (!rc) rc = ensure_prim(c, tb);
-        tb = c->prim_bytes;
-        if (!rc) rc = prim_sort_pairs_u32(c->prim_tmp, &tb, rho, srho, iota, e1, n, 32, c->stream);
-    }
-    if (!rc) rc = launch_br_gather_keys(keys, e1, n, key1, c->stream);
-    if (!rc) rc = sort_u64(c, key1, skeys, e1, e2, n);
-#if LIVO_IDX_RUNS
-    int64_t words = 0;
-    // (srho, iota: dead after the sorts) the padded run lengths and their scan
-    if (!rc) rc = build_index_runs(c, n, skeys, e2, pt, heads, runid, starts, nruns, srho, iota, &c->bpts,
-                                   &c->bslots, &c->blog2, &words);
-    (void)hipFree(scr);
-    dev_free(off);
-    if (rc) return rc;
-    c->bh = bh;
-    c->brmax = brmax;
-    c->br5 = r5;
-    c->bentries = n;
-    c->bchunks = 1;
-    c->grid_bytes += (int64_t)(((int64_t)1 << c->blog2) * sizeof(GridSlot) + words * sizeof(RunWord));
-    return LIVO_OK;
-#else
-    if (!rc) rc = launch_br_fill(c->gpts, pt, e2, skeys, n, c->bpts, heads, c->stream);
-    if (!rc) rc = ivox_scan(c, heads, runid, n);
-    if (!rc) rc = launch_dyn_runs(heads, runid, n, starts, nruns, c->stream);
-    unsigned long long runs = 0;
-    if (!rc && hipMemcpyAsync(&runs, nruns, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    int log2 = 4;
-    while (((int64_t)1 << log2) < 4 * (int64_t)runs) log2++;
-    const int64_t table = (int64_t)1 << log2;
-    if (!rc && dev_alloc(&c->bslots, (size_t)table)) rc = LIVO_E_OOM;
-    if (!rc) rc = launch_ivox_clear(c->bslots, table, c->stream);
-    if (!rc) rc = launch_dyn_slots(skeys, starts, (int64_t)runs, c->bslots, log2, c->stream);
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
-    (void)hipFree(scr);
-    dev_free(off);
-    if (rc) {
-        dev_free(c->bslots);
-        dev_free(c->bpts);
-        return rc;
-    }
-    c->blog2 = log2;
-    c->bh = bh;
-    c->brmax = brmax;
-    c->br5 = r5;
-    c->bentries = n;
-    c->bchunks = 1;
-    c->grid_bytes += (int64_t)(table * sizeof(GridSlot) + (size_t)(n + kRunPad) * 16);
-    return LIVO_OK;
-#endif
 }
 
 int livo_map_build(livo_ctx* c, const float* xyz, int64_t M, int64_t stride_bytes) {

@@ -1,6 +1,7 @@
 // livo_internal.h — layouts shared by the host runtime (livo_capi.cpp,
 // map_build.cpp) and the CDNA4 kernels (livo_kernels.hip).  Not part of the ABI.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -11,25 +12,13 @@
 #define LIVO_PTS_PER_THREAD 1  // plane pass: 1 point per thread (A/B on MI355X: 4 -> 1 = +7 % at config 2)
 #endif
 
-// Run entries (cell runs / ball runs, KnnParams::vpts / bpts).  1 (default):
-// one 4-B grid position (an index into the cell grid's points, gpts) per
-// entry, every run a 4-entry aligned segment, so a run scan reads 8 positions
-// (two aligned 16-B loads) and gathers their points from the 16 B x M cell grid
-// that stays cache-resident: a quarter of the bytes of 0, which stores the
-// point itself (x, y, z, map index bits: 16 B) in every run it belongs to.
-#ifndef LIVO_IDX_RUNS
-#define LIVO_IDX_RUNS 1
-#endif
-
 namespace livo {
 
-#if LIVO_IDX_RUNS
-using RunWord = uint32_t;
-constexpr int kRunWords = 1;  // words per run entry
-#else
-using RunWord = float;
-constexpr int kRunWords = 4;
-#endif
+// Run entries (cell runs / ball runs, KnnParams::vpts / bpts): one 4-B grid
+// position (an index into the cell grid's points, gpts) per entry, every run
+// a 4-entry aligned segment, so a run scan reads 8 positions (two aligned
+// 16-B loads) and gathers their points from the 16 B x M cell grid that stays
+// cache-resident.
 constexpr int kRunPad = 8;    // entries of padding behind the last run (chunk reads)
 
 constexpr int kNN = LIVO_NUM_MATCH_POINTS;  // 5
@@ -145,6 +134,30 @@ struct HostGridMap {
 };
 // cell_h <= 0: chosen from the map (about ppc_target points per occupied cell, 20 if 0;
 // ppc_target < 0: -ppc_target x clamp((M / 1M)^0.3, 1, 4), the cell runs' sizing)
+// Home slot of `key` in a table of 2^log2 GridSlots (linear probing from there):
+// the one hash of every insert and every lookup, host and device.
+SEL_HD uint64_t grid_hash(unsigned long long key, int log2) {
+    return (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2));
+}
+// The cells [lo, hi] per axis that can hold a point within sqrt(t) of (qx, qy, qz)
+// on the grid (org, h): the radius carries the certification margins (1e-9 on t
+// for the 1e-10 tie fuzz, a relative 1e-5, and eps, the float slack of the cell
+// assignment).  False (lo / hi unspecified) when an index leaves +-(kGridBias - 8),
+// which also rejects t = +inf and NaN.
+SEL_HD bool ball_cells(const float org[3], float h, float eps, float qx, float qy, float qz, float t, int lo[3],
+                       int hi[3]) {
+    const double rad = sqrt((double)t + 1e-9) * (1.0 + 1e-5) + (double)eps;
+    const double ih = 1.0 / (double)h, lim = (double)(kGridBias - 8);
+    const double q3[3] = {(double)qx, (double)qy, (double)qz};
+    bool ok = true;
+    for (int a = 0; a < 3; a++) {
+        const double l = floor((q3[a] - rad - (double)org[a]) * ih), u = floor((q3[a] + rad - (double)org[a]) * ih);
+        ok = ok && fabs(l) < lim && fabs(u) < lim;
+        lo[a] = ok ? (int)l : 0;
+        hi[a] = ok ? (int)u : -1;
+    }
+    return ok;
+}
 int build_grid_map(const float* xyz, int64_t M, int64_t stride_bytes, float cell_h, HostGridMap* out,
                    float ppc_target = 0.f);
 float sample_knn_radius(const HostGridMap& gm, int samples);  // median 5-NN distance of map points
@@ -154,10 +167,9 @@ void free_grid_map(HostGridMap* m);
 
 // Cell runs: the search structure of the batched IEKF k-NN on a static map.
 // The run of cell c holds every map point of the 3x3x3 cells around c (27x
-// the points: 432 MB for a 1M map), sorted by the squared distance rho2 to
-// c's centre.  Entry: (x, y, z, map index bits) -- the coordinates and index
-// the neighbour record needs, so a search reads nothing else; rho2 is
-// recomputed from the entry with the build's float operations (same bits).
+// the entries: 108 MB for a 1M map), sorted by the squared distance rho2 to
+// c's centre.  Entry: the point's grid position; rho2 is recomputed from the
+// gathered point with the build's float operations (same bits).
 // A query takes its own cell's run: one hash probe, one contiguous scan that
 // stops at the first entry with rho > |q - centre| + the current bound.
 
@@ -379,10 +391,10 @@ struct KnnParams {
     float geps;             // cell-bound slack for float rounding of the cell assignment
     int32_t glog2;          // log2 of the hash table size
     const GridSlot* vslots; // cell runs (null: the cell walk of grid_search)
-    const RunWord* vpts;    // run entries (LIVO_IDX_RUNS: grid positions; else x, y, z, map index bits)
+    const uint32_t* vpts;   // run entries: grid positions (indices into rpts)
     int32_t vlog2;
     const GridSlot* bslots; // ball runs (null: the cell runs only); entries in bpts
-    const RunWord* bpts;
+    const uint32_t* bpts;
     int32_t blog2;
     float bh;               // anchor cell edge (origin gorg)
     float bcert2;           // certified if the final scan bound b satisfies b * b <= bcert2
@@ -396,7 +408,7 @@ struct KnnParams {
     const GridSlot* dslots; // delta grid (null: no point added since the base); points in dpts
     const float* dpts;
     const GridSlot* dvslots;  // the delta grid's cell runs (null: none); entries = positions in dpts
-    const RunWord* dvidx;
+    const uint32_t* dvidx;
     int32_t dvlog2;
     // k_iekf_eval's run searches on a static map store the records' hot halves only
     // (kRecNoXyz; LIVO_REC_COMPACT=0: full records)
@@ -738,8 +750,7 @@ int launch_dyn_delete_boxes(const float* all, uint8_t* alive, int64_t n_ids, con
                             unsigned long long* cnt, void* stream);
 
 // Cell runs on the device from the cell grid (gpts: n / 27 points): entry e's
-// rho2 (bits) and e; the run key of pass-1-sorted entries; the final runs
-// (x, y, z, map index bits) and the run heads.
+// rho2 (bits) and e; the run key of pass-1-sorted entries.
 // ball runs (k_br_*, ikd_incr_kernels.hip)
 int launch_br_count(const float* gpts, int64_t n, const float org[3], float h, float rmax, uint32_t* cnt,
                     unsigned long long* total, void* stream, int x0 = -(1 << 30), int x1 = 1 << 30);
@@ -752,16 +763,12 @@ int launch_run_trip(const unsigned long long* skeys, const uint32_t* starts, con
 int launch_trip_slots(const GridSlot* trip, int64_t nruns, GridSlot* slots, int log2, void* stream);
 int launch_br_gather_keys(const unsigned long long* keys, const uint32_t* e1, int64_t n, unsigned long long* out,
                           void* stream);
-int launch_br_fill(const float* gpts, const uint32_t* pt, const uint32_t* e2, const unsigned long long* skeys,
-                   int64_t n, float* bpts, uint32_t* heads, void* stream);
 int launch_add_u32(uint32_t* v, int64_t n, uint32_t add, void* stream);
 int launch_cr_rho(const float* gpts, int64_t n, const float org[3], float h, uint32_t* rho_bits, uint32_t* iota,
                   void* stream);
 int launch_cr_key(const float* gpts, const uint32_t* e1, int64_t n, const float org[3], float h,
                   unsigned long long* keys, void* stream);
-int launch_cr_fill(const float* gpts, const uint32_t* e2, const unsigned long long* skeys, int64_t n,
-                   const float org[3], float h, float* vpts, uint32_t* heads, void* stream);
-// Index runs (LIVO_IDX_RUNS): the run heads of key-sorted entries; each run's
+// Index runs: the run heads of key-sorted entries; each run's
 // length rounded up to 4; every entry's grid position (pt ? pt[e2[i]] :
 // e2[i] / 27) at pstart[run] + its offset in the run; the runs' hash slots
 // {key, pstart, length}.

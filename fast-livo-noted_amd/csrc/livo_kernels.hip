@@ -727,9 +727,6 @@ __global__ __launch_bounds__(kKnnBlock, 8) void k_knn_pass(KnnParams P) {  // 8 
         node = 2u * node + (left_first ? 1u : 2u);
     }
     flag |= s.fuzz ? 1u : 0u;
-#ifdef LIVO_LAB_NOFLAGS
-    flag = 0;
-#endif
     float od[kNN];
     uint32_t on[kNN];
 #pragma unroll
@@ -762,8 +759,9 @@ __global__ __launch_bounds__(kKnnBlock, 8) void k_knn_pass(KnnParams P) {  // 8 
 // query (exact replay on the ikd-Tree) if C1 or C2 fails.
 // One query of the leaf-map search: its world point, seed bound, sorted
 // 5-candidate list and e6 (smallest distance rejected or evicted).
-// A candidate's position in the cell runs (vrun_search) rather than a grid /
-// leaf-map slot: lq_finish reads it from P.vpts.
+// A candidate of the incremental map's delta set (points added since its runs
+// were built): kRunPos | its position in P.dpts, rather than a slot of the
+// searched point array (lq_finish reads it from P.dpts).
 constexpr uint32_t kRunPos = 0x80000000u;
 struct LeafQuery {
     float qx, qy, qz, B, e6;
@@ -851,11 +849,12 @@ __device__ __forceinline__ void lq_point(LeafQuery& q, const float4 v, uint32_t 
 // is a strict total order on the 5 points, so sorting by (dist, x) gives the
 // reference's order.  A gap in (0, 1e-10] (CMP not transitive) or an exact tie
 // with equal x (neither point "less") still goes to the exact replay.
-// RUNS: candidates may be cell-run positions (kRunPos, vrun_search) besides slots of lpts
-template <bool RUNS>
-__device__ __forceinline__ float4 cand_point(const float4* __restrict__ lpts, const float4* __restrict__ vpts,
+// DELTA (the incremental map's run search): candidates may be delta-set positions
+// (kRunPos | position in dpts) besides slots of lpts
+template <bool DELTA>
+__device__ __forceinline__ float4 cand_point(const float4* __restrict__ lpts, const float4* __restrict__ dpts,
                                              uint32_t nd) {
-    if constexpr (RUNS) return (nd & kRunPos) ? vpts[nd & ~kRunPos] : lpts[nd];
+    if constexpr (DELTA) return (nd & kRunPos) ? dpts[nd & ~kRunPos] : lpts[nd];
     return lpts[nd];
 }
 #ifdef LIVO_EVAL_PROF
@@ -867,18 +866,18 @@ __device__ unsigned long long g_amb_reason[8];
 // lane l's half at l * 4 + ((k + (l >> 2)) & 3), so that 16 consecutive lanes'
 // 16-B writes of one part cover all 64 banks.
 __device__ __forceinline__ int rec_stage_slot(int l, int k) { return l * 4 + ((k + (l >> 2)) & 3); }
-template <bool RUNS = false, bool NBR = false>  // NBR: nbr takes the neighbours
+template <bool DELTA = false, bool NBR = false>  // NBR: nbr takes the neighbours
 // stage: the wave's LDS record stage, which takes the record's hot half (with
 // stage_flag's kRecNoXyz; the caller stores it and, for a full record, the cold
 // half from nbr); nullptr: the full record goes straight to job.nn.
 __device__ __forceinline__ bool lq_finish(LeafQuery& q, const KnnParams& P, const HsJob& job, unsigned bjob,
                                           int i, const float4* __restrict__ lpts, bool overrun, bool enqueue = true,
-                                          const float4* __restrict__ vpts = nullptr, float4* nbr = nullptr,
+                                          const float4* __restrict__ dpts = nullptr, float4* nbr = nullptr,
                                           float4* stage = nullptr, int stage_flag = 0) {
     const int cnt = (int)min<int64_t>(P.lM, (int64_t)kNN);
     float4 a[kNN];
 #pragma unroll
-    for (int k = 0; k < kNN; k++) a[k] = k < cnt ? cand_point<RUNS>(lpts, vpts, q.nd[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < kNN; k++) a[k] = k < cnt ? cand_point<DELTA>(lpts, dpts, q.nd[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
     bool amb = overrun || q.e6 - q.d[kNN - 1] <= kFuzz;  // C1 (false while e6 = +inf)
     bool tie = false;
 #pragma unroll
@@ -922,7 +921,7 @@ __device__ __forceinline__ bool lq_finish(LeafQuery& q, const KnnParams& P, cons
         }
 #pragma unroll
         for (int k = 0; k < kNN; k++)
-            if (k < cnt) a[k] = cand_point<RUNS>(lpts, vpts, q.nd[k]);
+            if (k < cnt) a[k] = cand_point<DELTA>(lpts, dpts, q.nd[k]);
     }
     // neighbour record: points, distances, original indices; key[] = the candidates' positions
     float4 nb[kNN];
@@ -957,13 +956,10 @@ __device__ __forceinline__ bool lq_finish(LeafQuery& q, const KnnParams& P, cons
     return amb;
 }
 
-// Q queries per thread walk the tree together (a box is entered if any of them
-// may need it; a pending far son keeps the smallest of their box distances and
-// is re-checked against the largest threshold, which may visit a box no query
-// needs, never skip one).  Only Q = 1 is launched: measured on MI355X, Q = 2
-// (Morton-adjacent pairs sharing each load) was 1.4x slower at 8 scans.
-template <bool SEEDED, int Q>
-__global__ __launch_bounds__(kKnnBlock, Q == 1 ? 8 : 6) void k_knn_leaf(KnnParams P) {
+// One query per thread (measured on MI355X: Morton-adjacent pairs of queries
+// sharing each load were 1.4x slower at 8 scans).
+template <bool SEEDED>
+__global__ __launch_bounds__(kKnnBlock, 8) void k_knn_leaf(KnnParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned bjob, bx;
     xcd_block(P.nb, bjob, bx);
@@ -975,14 +971,13 @@ __global__ __launch_bounds__(kKnnBlock, Q == 1 ? 8 : 6) void k_knn_leaf(KnnParam
         if (slot->ctrl.stop) return;
         if (SEEDED && !slot->ctrl.search_en) return;
     }
-    const int i0 = ((int)bx * kKnnBlock + threadIdx.x) * Q;
-    if (i0 >= job.n) return;
+    const int i = (int)bx * kKnnBlock + threadIdx.x;
+    if (i >= job.n) return;
     float* dstack = reinterpret_cast<float*>(smem) + threadIdx.x;
     const float4* __restrict__ lnodes = reinterpret_cast<const float4*>(P.lnodes);
     const float4* __restrict__ lpts = reinterpret_cast<const float4*>(P.lpts);
-    LeafQuery q[Q];
-#pragma unroll
-    for (int u = 0; u < Q; u++) lq_init<SEEDED>(q[u], P, slot, job, i0 + u, i0 + u < job.n);
+    LeafQuery q;
+    lq_init<SEEDED>(q, P, slot, job, i, true);
     const int D = P.ldepth;
     const uint32_t first_leaf = (1u << D) - 1u;
     const int64_t M = P.lM;
@@ -1003,10 +998,7 @@ __global__ __launch_bounds__(kKnnBlock, Q == 1 ? 8 : 6) void k_knn_leaf(KnnParam
             const int L = 31 - __clz(trail);
             trail &= ~(1u << L);
             const float de = dstack[(L - 1) * kKnnBlock];
-            float thr = lq_thr(q[0]);
-#pragma unroll
-            for (int u = 1; u < Q; u++) thr = fmaxf(thr, lq_thr(q[u]));
-            if (de - thr > kFuzz) continue;
+            if (de - lq_thr(q) > kFuzz) continue;
             const uint32_t a = ((cur + 1u) >> (level_of(cur) - L)) - 1u;
             node = ((a - 1u) ^ 1u) + 1u;
         }
@@ -1022,10 +1014,7 @@ __global__ __launch_bounds__(kKnnBlock, Q == 1 ? 8 : 6) void k_knn_leaf(KnnParam
                 for (int w = 0; w < 4; w++) v[w] = lpts[k0 + w];  // padded by 3 points
 #pragma unroll
                 for (int w = 0; w < 4; w++)
-                    if (k0 + w < hi) {
-#pragma unroll
-                        for (int u = 0; u < Q; u++) lq_point(q[u], v[w], (uint32_t)(k0 + w));
-                    }
+                    if (k0 + w < hi) lq_point(q, v[w], (uint32_t)(k0 + w));
             }
             has = false;
             continue;
@@ -1034,34 +1023,24 @@ __global__ __launch_bounds__(kKnnBlock, Q == 1 ? 8 : 6) void k_knn_leaf(KnnParam
         const float4 b = rp[0];
         const float4 cc = rp[1];
         const float4 dd = rp[2];
-        bool want_l = false, want_r = false;
-        float ml = INFINITY, mr = INFINITY;
-#pragma unroll
-        for (int u = 0; u < Q; u++) {
-            const float dl = box_dist(q[u].qx, q[u].qy, q[u].qz, b.x, b.y, b.z, b.w, cc.x, cc.y);
-            const float dr = box_dist(q[u].qx, q[u].qy, q[u].qz, cc.z, cc.w, dd.x, dd.y, dd.z, dd.w);
-            const float thr = lq_thr(q[u]);
-            want_l |= dl - thr <= kFuzz;
-            want_r |= dr - thr <= kFuzz;
-            ml = fminf(ml, dl);
-            mr = fminf(mr, dr);
-        }
-        const bool left_first = ml <= mr;
+        const float dl = box_dist(q.qx, q.qy, q.qz, b.x, b.y, b.z, b.w, cc.x, cc.y);
+        const float dr = box_dist(q.qx, q.qy, q.qz, cc.z, cc.w, dd.x, dd.y, dd.z, dd.w);
+        const float thr = lq_thr(q);
+        const bool want_l = dl - thr <= kFuzz, want_r = dr - thr <= kFuzz;
+        const bool left_first = dl <= dr;
         const bool want_near = left_first ? want_l : want_r, want_far = left_first ? want_r : want_l;
         // the far son waits on the stack only while the near son is searched
         // first (a pop must find cur at or below the pending level); if only
         // the far son is wanted, go there directly
         if (want_near && want_far) {
             const int Lc = level_of(node) + 1;
-            dstack[(Lc - 1) * kKnnBlock] = left_first ? mr : ml;
+            dstack[(Lc - 1) * kKnnBlock] = left_first ? dr : dl;
             trail |= 1u << Lc;
         }
         has = want_near || want_far;
         node = 2u * node + ((left_first == want_near) ? 1u : 2u);
     }
-#pragma unroll
-    for (int u = 0; u < Q; u++)
-        if (i0 + u < job.n) lq_finish(q[u], P, job, bjob, i0 + u, lpts, overrun);
+    lq_finish(q, P, job, bjob, i, lpts, overrun);
     count_visits(P, slot, visits);
 }
 
@@ -1196,7 +1175,7 @@ __device__ __forceinline__ TileView build_tile(TileLds<CELLS, PTS>& L, const Knn
         const int t = tid + NT * u;
         if (t < V) {
             key[u] = grid_key_d(tv.lo0 + t % tv.d0, tv.lo1 + (t / tv.d0) % tv.d1, tv.lo2 + t / (tv.d0 * tv.d1));
-            sl[u] = (uint64_t)((key[u] * 0x9E3779B97F4A7C15ull) >> (64 - P.glog2));
+            sl[u] = grid_hash(key[u], P.glog2);
             gs[u] = slots[sl[u]];
             visits++;
         }
@@ -1345,7 +1324,6 @@ __device__ __forceinline__ bool grid_search(LeafQuery& q, const KnnParams& P, in
     const float4* __restrict__ gpts = reinterpret_cast<const float4*>(P.gpts);
     const GridSlot* __restrict__ slots = P.gslots;
     const float h = P.gh, eps = P.geps;
-    const uint64_t mask = (1ull << P.glog2) - 1ull;
     auto visit = [&](int cx, int cy, int cz) __attribute__((always_inline)) {
         const float x0 = P.gorg[0] + (float)cx * h - eps, y0 = P.gorg[1] + (float)cy * h - eps;
         const float z0 = P.gorg[2] + (float)cz * h - eps;
@@ -1367,14 +1345,7 @@ __device__ __forceinline__ bool grid_search(LeafQuery& q, const KnnParams& P, in
             return;
         }
         const unsigned long long key = grid_key_d(cx, cy, cz);
-        uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - P.glog2));
-        GridSlot gs = slots[sl];
-        visits++;
-        while (gs.key != key && gs.key != kGridEmpty) {  // linear probing (load factor <= 1/4)
-            sl = (sl + 1) & mask;
-            gs = slots[sl];
-            visits++;
-        }
+        const GridSlot gs = grid_find(slots, P.glog2, key, visits);
         if (gs.key != key) return;
         const int lo = (int)gs.start, hi = (int)(gs.start + gs.count);
         npts += gs.count;
@@ -1405,14 +1376,9 @@ __device__ __forceinline__ bool grid_search(LeafQuery& q, const KnnParams& P, in
     // the cells that can hold a point within sqrt(t) (+ the fuzz, + the float
     // slack of the cell assignment); false if that box is too large
     auto range_of = [&](float t, CBox& r) {
-        const double rad = sqrt((double)t + 1e-9) * (1.0 + 1e-5) + (double)eps;
-        const double ih = 1.0 / (double)h;
-        const double lim = (double)(kGridBias - 8);
-        const double l0 = floor(((double)q.qx - rad - (double)P.gorg[0]) * ih), h0 = floor(((double)q.qx + rad - (double)P.gorg[0]) * ih);
-        const double l1 = floor(((double)q.qy - rad - (double)P.gorg[1]) * ih), h1 = floor(((double)q.qy + rad - (double)P.gorg[1]) * ih);
-        const double l2 = floor(((double)q.qz - rad - (double)P.gorg[2]) * ih), h2 = floor(((double)q.qz + rad - (double)P.gorg[2]) * ih);
-        if (!(fmax(fmax(fabs(l0), fabs(h0)), fmax(fmax(fabs(l1), fabs(h1)), fmax(fabs(l2), fabs(h2)))) < lim)) return false;
-        r = CBox{(int)l0, (int)h0, (int)l1, (int)h1, (int)l2, (int)h2};
+        int lo[3], hi[3];
+        if (!ball_cells(P.gorg, h, eps, q.qx, q.qy, q.qz, t, lo, hi)) return false;
+        r = CBox{lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]};
         return true;
     };
     if (!(P.lM > 0)) return false;
@@ -1472,15 +1438,6 @@ __device__ __forceinline__ bool grid_search(LeafQuery& q, const KnnParams& P, in
 // and the scan stops at the first chunk whose first entry has rho > b = dqv +
 // sqrt(bound) (+ margins), every later entry being farther than the bound.
 // Returns the entries read.  The run array is padded by kRunPad entries.
-//
-// LIVO_RUN_PIPE = 1: two chunks in flight (A / B ping-pong): the loads of
-// chunk k+2 are issued as soon as chunk k is consumed, so a lane waits for one
-// load round trip per two chunks.  Chunk k+2 is not loaded when the run ends
-// before it or when chunk k's last entry is already beyond b (the entries are
-// sorted, so the scan stops at chunk k+1 at the latest).
-#ifndef LIVO_RUN_PIPE
-#define LIVO_RUN_PIPE 0
-#endif
 __device__ __forceinline__ float run_bound(const LeafQuery& q, float dqv) {
     const float thr = lq_thr(q);
     return thr < INFINITY ? dqv + __builtin_amdgcn_sqrtf(thr) * (1.0f + 1e-6f) + 1e-4f : INFINITY;
@@ -1502,7 +1459,6 @@ __device__ __forceinline__ void run_chunk(LeafQuery& q, const float4 (&v)[8], ui
         for (int u = 0; u < 8; u++) lq_offer(q, dist[u], slot(u));
     }
 }
-#if LIVO_IDX_RUNS
 // Index runs: the run holds grid positions (4-aligned run start); a chunk's 8
 // positions are two aligned 16-B loads, its points are gathered from the cell
 // grid (pts), and the next chunk's positions are loaded with this chunk's
@@ -1535,53 +1491,14 @@ __device__ __forceinline__ uint32_t scan_run(LeafQuery& q, const uint32_t* __res
     }
     return min(k0, cnt);
 }
-#else
-__device__ __forceinline__ uint32_t scan_run(LeafQuery& q, const float4* __restrict__ run, uint32_t cnt, uint32_t lo,
-                                             float cx, float cy, float cz, float dqv) {
-    auto slot = [&](uint32_t k0) { return [=](int u) { return kRunPos | (lo + k0 + (uint32_t)u); }; };
-    uint32_t k0 = 0;
-#if LIVO_RUN_PIPE
-    if (cnt == 0) return 0;
-    float4 A[8], B[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) A[u] = run[u];
-    if (cnt > 8) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) B[u] = run[8 + u];
-    }
-    // one chunk: stop test, distances, then the loads two chunks ahead into the same registers
-    auto step = [&](float4 (&v)[8]) __attribute__((always_inline)) -> bool {
-        const float b = run_bound(q, dqv);
-        if (centre_d2(cx, cy, cz, v[0].x, v[0].y, v[0].z) > b * b) return false;  // rho of every later entry > b
-        run_chunk(q, v, k0, cnt, slot(k0));
-        const float b2 = run_bound(q, dqv);
-        const bool more = k0 + 16 < cnt && !(centre_d2(cx, cy, cz, v[7].x, v[7].y, v[7].z) > b2 * b2);
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) v[u] = run[k0 + 16 + u];
-        }
-        k0 += 8;
-        return k0 < cnt;
-    };
-#pragma unroll 1
-    while (true) {
-        if (!step(A)) break;
-        if (!step(B)) break;
-    }
-#else
-#pragma unroll 1
-    for (; k0 < cnt; k0 += 8) {
-        float4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = run[k0 + u];  // padded by kRunPad entries
-        const float b = run_bound(q, dqv);
-        if (centre_d2(cx, cy, cz, v[0].x, v[0].y, v[0].z) > b * b) break;  // rho of every later entry > b
-        run_chunk(q, v, k0, cnt, slot(k0));
-    }
-#endif
-    return min(k0, cnt);
+
+// true when the ball of the list's bound (+ grid_search's margins) lies in the cube [c - 1, c + 1]
+__device__ __forceinline__ bool cube_inside(const LeafQuery& q, const KnnParams& P, int c0, int c1, int c2) {
+    const float t = lq_thr(q);
+    int lo[3], hi[3];
+    if (!(t < INFINITY) || !ball_cells(P.gorg, P.gh, P.geps, q.qx, q.qy, q.qz, t, lo, hi)) return false;
+    return lo[0] >= c0 - 1 && hi[0] <= c0 + 1 && lo[1] >= c1 - 1 && hi[1] <= c1 + 1 && lo[2] >= c2 - 1 && hi[2] <= c2 + 1;
 }
-#endif
 
 // ------------------------------------------------------------ cell-run search ----
 // The batched IEKF search on the cell runs (livo_internal.h): the run of the
@@ -1595,8 +1512,8 @@ __device__ __forceinline__ uint32_t scan_run(LeafQuery& q, const float4* __restr
 // is farther than bound + 1e-10, so it could neither enter the list nor make
 // e6 - d5 <= 1e-10, exactly as a pruned cell of grid_search).  Within a chunk
 // of 8 entries a lane takes the per-point insertion path only when one of
-// them is below its e6.  Candidates carry their run position (kRunPos bit
-// set); lq_finish reads coordinates and map index from the run entry.  If the
+// them is below its e6.  Candidates are grid positions (slots of P.rpts);
+// lq_finish reads coordinates and map index from there.  If the
 // ball of the final bound lies in the cube the list is certified (every point
 // within the bound was scanned); else the lane continues with grid_search's
 // stage 2 outside the cube (candidates there are cell-grid slots).
@@ -1608,42 +1525,15 @@ __device__ __forceinline__ bool vrun_search(LeafQuery& q, const KnnParams& P, bo
                                             int s0, int s1, int s2, unsigned& visits, unsigned& npts) {
     if (!valid || !(P.lM > 0)) return false;
     const unsigned long long key = grid_key_d(c0, c1, c2);
-    const uint64_t mask = (1ull << P.vlog2) - 1ull;
-    uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - P.vlog2));
-    GridSlot g = P.vslots[sl];
-    visits++;
-    while (g.key != key && g.key != kGridEmpty) {  // linear probing (load factor <= 1/4)
-        sl = (sl + 1) & mask;
-        g = P.vslots[sl];
-        visits++;
-    }
+    const GridSlot g = grid_find(P.vslots, P.vlog2, key, visits);
     const uint32_t lo = g.key == key ? g.start : 0u, cnt = g.key == key ? g.count : 0u;
     const float h = P.gh;
     const float cx = cell_centre(P.gorg[0], h, c0), cy = cell_centre(P.gorg[1], h, c1);
     const float cz = cell_centre(P.gorg[2], h, c2);
     const float dqv = __builtin_amdgcn_sqrtf(centre_d2(cx, cy, cz, q.qx, q.qy, q.qz)) * (1.0f + 1e-6f);
-#if LIVO_IDX_RUNS
     npts += scan_run(q, P.vpts + lo, cnt, reinterpret_cast<const float4*>(P.rpts), cx, cy, cz, dqv);
-#else
-    const float4* __restrict__ run = reinterpret_cast<const float4*>(P.vpts) + lo;
-    npts += scan_run(q, run, cnt, lo, cx, cy, cz, dqv);
-#endif
     // certified when the ball of the final bound lies in the cube [c - 1, c + 1]
-    const float t = lq_thr(q);
-    if (t < INFINITY) {
-        const double rad = sqrt((double)t + 1e-9) * (1.0 + 1e-5) + (double)P.geps;
-        const double ih = 1.0 / (double)P.gh;
-        const double q3[3] = {(double)q.qx, (double)q.qy, (double)q.qz};
-        const int cc[3] = {c0, c1, c2};
-        bool inside = true;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const double l = floor((q3[a] - rad - (double)P.gorg[a]) * ih);
-            const double hh = floor((q3[a] + rad - (double)P.gorg[a]) * ih);
-            inside = inside && l >= (double)(cc[a] - 1) && hh <= (double)(cc[a] + 1);
-        }
-        if (inside) return true;
-    }
+    if (cube_inside(q, P, c0, c1, c2)) return true;
     if constexpr (DYN) return false;
     TileView none;
     return grid_search(q, P, c0, c1, c2, s0, s1, s2, none, visits, npts, nullptr, true);
@@ -1663,7 +1553,7 @@ __device__ __forceinline__ bool vrun_search(LeafQuery& q, const KnnParams& P, bo
 // in the run and was scanned.  Points outside the ball are farther than b, so,
 // as a pruned cell of grid_search, they could neither enter the list nor make
 // e6 - d5 <= 1e-10.  Not certified (or no run): the caller searches the cell
-// runs from scratch.  Candidates carry their position in P.bpts (kRunPos set).
+// runs from scratch.  Candidates are grid positions, as the cell runs'.
 template <bool DYN = false>
 __device__ __forceinline__ bool brun_search(LeafQuery& q, const KnnParams& P, bool valid, unsigned& visits,
                                             unsigned& npts) {
@@ -1678,38 +1568,20 @@ __device__ __forceinline__ bool brun_search(LeafQuery& q, const KnnParams& P, bo
         a[k] = (int)f;
     }
     const unsigned long long key = grid_key_d(a[0], a[1], a[2]);
-    const uint64_t mask = (1ull << P.blog2) - 1ull;
-    uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - P.blog2));
-    GridSlot g = P.bslots[sl];
-    visits++;
-    while (g.key != key && g.key != kGridEmpty) {  // linear probing (load factor <= 1/4)
-        sl = (sl + 1) & mask;
-        g = P.bslots[sl];
-        visits++;
-    }
+    const GridSlot g = grid_find(P.bslots, P.blog2, key, visits);
     if (g.key != key) return false;
-#if LIVO_IDX_RUNS
     const size_t lo = (size_t)g.start << 2;  // (ball-run starts are stored / 4: 2^34 words addressable)
-#else
-    const uint32_t lo = g.start;
-#endif
     const uint32_t cnt = g.count;
     const float cx = cell_centre(P.gorg[0], P.bh, a[0]), cy = cell_centre(P.gorg[1], P.bh, a[1]);
     const float cz = cell_centre(P.gorg[2], P.bh, a[2]);
     const float dqv = __builtin_amdgcn_sqrtf(centre_d2(cx, cy, cz, q.qx, q.qy, q.qz)) * (1.0f + 1e-6f);
-#if LIVO_IDX_RUNS
     npts += scan_run(q, P.bpts + lo, cnt, reinterpret_cast<const float4*>(P.rpts), cx, cy, cz, dqv);
-#else
-    const float4* __restrict__ run = reinterpret_cast<const float4*>(P.bpts) + lo;
-    npts += scan_run(q, run, cnt, lo, cx, cy, cz, dqv);
-#endif
     const float t = lq_thr(q);
     if (!(t < INFINITY)) return false;
     const float b = dqv + __builtin_amdgcn_sqrtf(t) * (1.0f + 1e-6f) + 1e-4f;
     return b * b <= P.bcert2;
 }
 
-#if LIVO_IDX_RUNS
 // The incremental map's delta (points added since its runs were built) has
 // cell runs of its own over the delta grid: the query's cell's run (its
 // 3x3x3 cube's delta points, sorted by rho2) scanned like the base's, its
@@ -1719,39 +1591,13 @@ __device__ __forceinline__ bool brun_search(LeafQuery& q, const KnnParams& P, bo
 __device__ __forceinline__ void dvrun_scan(LeafQuery& q, const KnnParams& P, int c0, int c1, int c2, unsigned& visits,
                                            unsigned& npts) {
     const unsigned long long key = grid_key_d(c0, c1, c2);
-    const uint64_t mask = (1ull << P.dvlog2) - 1ull;
-    uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - P.dvlog2));
-    GridSlot g = P.dvslots[sl];
-    visits++;
-    while (g.key != key && g.key != kGridEmpty) {
-        sl = (sl + 1) & mask;
-        g = P.dvslots[sl];
-        visits++;
-    }
+    const GridSlot g = grid_find(P.dvslots, P.dvlog2, key, visits);
     if (g.key != key) return;
     const float h = P.gh;
     const float cx = cell_centre(P.gorg[0], h, c0), cy = cell_centre(P.gorg[1], h, c1);
     const float cz = cell_centre(P.gorg[2], h, c2);
     const float dqv = __builtin_amdgcn_sqrtf(centre_d2(cx, cy, cz, q.qx, q.qy, q.qz)) * (1.0f + 1e-6f);
     npts += scan_run(q, P.dvidx + g.start, g.count, reinterpret_cast<const float4*>(P.dpts), cx, cy, cz, dqv, kRunPos);
-}
-#endif
-// true when the ball of the list's bound (+ grid_search's margins) lies in the cube [c - 1, c + 1]
-__device__ __forceinline__ bool cube_inside(const LeafQuery& q, const KnnParams& P, int c0, int c1, int c2) {
-    const float t = lq_thr(q);
-    if (!(t < INFINITY)) return false;
-    const double rad = sqrt((double)t + 1e-9) * (1.0 + 1e-5) + (double)P.geps;
-    const double ih = 1.0 / (double)P.gh;
-    const double q3[3] = {(double)q.qx, (double)q.qy, (double)q.qz};
-    const int cc[3] = {c0, c1, c2};
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const double l = floor((q3[a] - rad - (double)P.gorg[a]) * ih);
-        const double hh = floor((q3[a] + rad - (double)P.gorg[a]) * ih);
-        inside = inside && l >= (double)(cc[a] - 1) && hh <= (double)(cc[a] + 1);
-    }
-    return inside;
 }
 
 // The delta grid of the incremental map (points added since its runs were
@@ -1765,22 +1611,11 @@ constexpr int kDeltaMaxCells = 64;
 __device__ __forceinline__ bool delta_search(LeafQuery& q, const KnnParams& P, unsigned& visits, unsigned& npts) {
     const float t = lq_thr(q);
     if (!(t < INFINITY)) return false;
-    const double rad = sqrt((double)t + 1e-9) * (1.0 + 1e-5) + (double)P.geps;
-    const double ih = 1.0 / (double)P.gh, lim = (double)(kGridBias - 8);
-    const double q3[3] = {(double)q.qx, (double)q.qy, (double)q.qz};
     int l[3], h[3];
-    double span = 1.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const double lo = floor((q3[a] - rad - (double)P.gorg[a]) * ih), hi = floor((q3[a] + rad - (double)P.gorg[a]) * ih);
-        if (!(fabs(lo) < lim && fabs(hi) < lim)) return false;
-        l[a] = (int)lo;
-        h[a] = (int)hi;
-        span *= hi - lo + 1.0;
-    }
+    if (!ball_cells(P.gorg, P.gh, P.geps, q.qx, q.qy, q.qz, t, l, h)) return false;
+    const double span = (double)(h[0] - l[0] + 1) * (double)(h[1] - l[1] + 1) * (double)(h[2] - l[2] + 1);
     if (span > (double)kDeltaMaxCells) return false;
     const float4* __restrict__ dp = reinterpret_cast<const float4*>(P.dpts);
-    const uint64_t mask = (1ull << P.dlog2) - 1ull;
 #pragma unroll 1
     for (int cz = l[2]; cz <= h[2]; cz++)
 #pragma unroll 1
@@ -1788,14 +1623,7 @@ __device__ __forceinline__ bool delta_search(LeafQuery& q, const KnnParams& P, u
 #pragma unroll 1
             for (int cx = l[0]; cx <= h[0]; cx++) {
                 const unsigned long long key = grid_key_d(cx, cy, cz);
-                uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - P.dlog2));
-                GridSlot g = P.dslots[sl];
-                visits++;
-                while (g.key != key && g.key != kGridEmpty) {
-                    sl = (sl + 1) & mask;
-                    g = P.dslots[sl];
-                    visits++;
-                }
+                const GridSlot g = grid_find(P.dslots, P.dlog2, key, visits);
                 if (g.key != key) continue;
                 npts += g.count;
 #pragma unroll 1
@@ -1850,7 +1678,6 @@ __global__ __launch_bounds__(TILE ? 64 : kKnnBlock, TILE ? 4 : LIVO_GRID_WAVES) 
     count_visits(P, slot, visits, npts);
 }
 
-#if LIVO_IDX_RUNS
 // The runs' search as a pass of its own (the unfused paths: the IKFoM update,
 // LIVO_FUSED=0): k_iekf_eval's search stage -- ball run, cell run, the cell
 // walk past the cube -- for every point of the batch, the neighbour record
@@ -1886,7 +1713,6 @@ __global__ __launch_bounds__(kEvalBlock) void k_knn_runs(KnnParams P) {
     if (valid) lq_finish<false>(q, P, job, bjob, i, reinterpret_cast<const float4*>(P.gpts), !certified, true);
     count_visits(P, slot, visits, npts);
 }
-#endif
 
 // Exact reference-order recomputation of the queries the fast pass flagged:
 // KD_TREE::Search's visiting order with the far sons on an LDS stack and the
@@ -1966,7 +1792,6 @@ __device__ __forceinline__ bool canon_less(float d1, float x1, uint32_t i1, floa
 template <class Src>
 __device__ __forceinline__ void canon_query(const KnnParams& P, const HsJob& job, int i, const Src& src) {
     const float4* __restrict__ gpts = reinterpret_cast<const float4*>(P.gpts);
-    const uint64_t mask = (1ull << P.glog2) - 1ull;
     {
         float qx, qy, qz;
         query_point(P, src, reinterpret_cast<const float4*>(job.pts)[i], qx, qy, qz);
@@ -1999,21 +1824,9 @@ __device__ __forceinline__ void canon_query(const KnnParams& P, const HsJob& job
         };
         bool scanned = false;
         if (T < INFINITY && P.lM > 0) {
-            const double rad = sqrt((double)T + 1e-9) * (1.0 + 1e-5) + (double)P.geps;
-            const double ih = 1.0 / (double)P.gh, lim = (double)(kGridBias - 8);
-            const double q3[3] = {qx, qy, qz};
             int l[3], h[3];
-            bool ok = true;
-            double span = 1.0;
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                const double lo = floor((q3[a] - rad - (double)P.gorg[a]) * ih);
-                const double hi = floor((q3[a] + rad - (double)P.gorg[a]) * ih);
-                ok = ok && fabs(lo) < lim && fabs(hi) < lim;
-                l[a] = ok ? (int)lo : 0;
-                h[a] = ok ? (int)hi : -1;
-                span *= hi - lo + 1.0;
-            }
+            const bool ok = ball_cells(P.gorg, P.gh, P.geps, qx, qy, qz, T, l, h);
+            const double span = (double)(h[0] - l[0] + 1) * (double)(h[1] - l[1] + 1) * (double)(h[2] - l[2] + 1);
             if (ok && span <= (double)kCanonMaxCells) {
                 const float eps = P.geps, w = P.gh + 2 * eps;
                 for (int cz = l[2]; cz <= h[2]; cz++)
@@ -2023,12 +1836,8 @@ __device__ __forceinline__ void canon_query(const KnnParams& P, const HsJob& job
                             const float z0 = P.gorg[2] + (float)cz * P.gh - eps;
                             if (box_dist(qx, qy, qz, x0, x0 + w, y0, y0 + w, z0, z0 + w) - T > kFuzz) continue;
                             const unsigned long long key = grid_key_d(cx, cy, cz);
-                            uint64_t sl = (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - P.glog2));
-                            GridSlot gs = P.gslots[sl];
-                            while (gs.key != key && gs.key != kGridEmpty) {
-                                sl = (sl + 1) & mask;
-                                gs = P.gslots[sl];
-                            }
+                            unsigned probes = 0;  // (not counted: the replayed queries are rare)
+                            const GridSlot gs = grid_find(P.gslots, P.glog2, key, probes);
                             if (gs.key != key) continue;
                             for (uint32_t s = gs.start; s < gs.start + gs.count; s++) offer(s);
                         }
@@ -2410,10 +2219,6 @@ __device__ __forceinline__ int solve_scan(IekfSlot* slot, SolveLds& L, const int
         // every lane factors it in registers (the same values, no cross-lane steps):
         // the pivoted 6x6 LU's argmax / row broadcasts are off the chain.
         const double* const Lf = L.covL;
-#ifdef LIVO_TAIL_TWICE  // I-cache probe (tools/tail_prof.py): T and Q formed twice, the first pass timed into marks 8, 9
-#pragma unroll 1
-        for (int rep = 0; rep < 2; rep++) {
-#endif
         // T = C L (lanes 0..35): T(r, c) = sum_{k >= c} C(r, k) L(k, c)
         if (lane < 36) {
             const int r = lane / 6, c = lane % 6;
@@ -2424,11 +2229,7 @@ __device__ __forceinline__ int solve_scan(IekfSlot* slot, SolveLds& L, const int
             L.T[lane] = t;
         }
         WAVE_SYNC();
-#ifdef LIVO_TAIL_TWICE
-        SPH_MARK(rep == 0 ? 8 : 1);
-#else
         SPH_MARK(1);
-#endif
         // Q = I6 + L^T T (lanes 0..35): Q(r, c) = [r == c] + sum_{k >= r} L(k, r) T(k, c)
         if (lane < 36) {
             const int r = lane / 6, c = lane % 6;
@@ -2439,10 +2240,6 @@ __device__ __forceinline__ int solve_scan(IekfSlot* slot, SolveLds& L, const int
             L.Q[lane] = (r == c ? 1.0 : 0.0) + q;
         }
         WAVE_SYNC();
-#ifdef LIVO_TAIL_TWICE
-        if (rep == 0) SPH_MARK(9);
-        }
-#endif
         // LDL^T of Q in place (f: packed lower, D on the diagonal), every lane
         double f[21], di[6];
 #pragma unroll
@@ -2968,9 +2765,6 @@ __device__ unsigned long long g_tail_prof[3][8];
 #else
 #define TAIL_MARK(k, t) do { } while (0)
 #endif
-#ifndef LIVO_SOLVE_PRIO
-#define LIVO_SOLVE_PRIO 1
-#endif
 #ifndef LIVO_RED_INFLIGHT
 #define LIVO_RED_INFLIGHT 32
 #endif
@@ -3136,10 +2930,8 @@ __device__ __forceinline__ void hs_scan_tail(const HsParams& P, const HsJob& job
 #endif
 ) {
     const int tid = threadIdx.x;
-#if LIVO_SOLVE_PRIO
     // the scan's serial tail (reduction, solve) ahead of the other waves on its SIMDs
     __builtin_amdgcn_s_setprio(3);
-#endif
 #ifdef LIVO_TAIL_PROF
     if (pk >= 0 && tid == 0) atomicAdd(&g_tail_prof[pk][5], 1ull);
 #endif
@@ -3411,19 +3203,13 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
         if (kStatic || P.vslots) {  // (kernel parameter: uniform)
             EVAL_MARK(1);
             bool certified = false;
-            const float4* runs = reinterpret_cast<const float4*>(P.vpts);  // (float4 run entries only)
 #ifdef LIVO_EVAL_PROF
             const unsigned np0 = npts;
             bool ball_ok = false;
 #endif
-#if LIVO_IDX_RUNS
             const bool dyn = !kStatic && P.dyn_runs != 0;  // (uniform) runs on the incremental map
-#else
-            constexpr bool dyn = false;
-#endif
             if (P.bslots) {  // (uniform) the ball runs first; the cell runs for a query they do not certify
                 certified = dyn ? brun_search<true>(q, P, valid, visits, npts) : brun_search<false>(q, P, valid, visits, npts);
-                if (certified) runs = reinterpret_cast<const float4*>(P.bpts);  // (float4 run entries only)
                 if (valid && !certified) lq_init<false>(q, P, pose, job, i, valid);
 #ifdef LIVO_EVAL_PROF
                 ball_ok = certified;
@@ -3437,14 +3223,12 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
                                 : vrun_search<false>(q, P, valid, c0, c1, c2, s0, s1, s2, visits, npts);
             // the incremental map's points added since its runs (none: no delta grid): the
             // cube's delta run; the list is exact if the base was and its ball lies in the cube
-#if LIVO_IDX_RUNS
             if (dyn && valid && P.dvslots) {
                 dvrun_scan(q, P, c0, c1, c2, visits, npts);
                 certified = certified && cube_inside(q, P, c0, c1, c2);
             } else if (dyn && valid && certified && P.dslots) {
                 certified = delta_search(q, P, visits, npts);
             }
-#endif
             // (a query the runs leave uncertified: vrun_search's serial walk beyond the cube; a
             // wave-parallel walk of one query's cells was slower)
             bool walked = false;
@@ -3489,25 +3273,21 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
 #endif
             // hot-only records (kRecNoXyz) on a static map: the loop's later evaluations read
             // the plane cache, a plane state 0 point its coordinates through the keys
-#if LIVO_IDX_RUNS
             const bool compact = P.rec_compact && !dyn && !canon;  // (uniform)
-#else
-            constexpr bool compact = false;  // (float4 runs: a key may lie in either run array)
-#endif
             float4 nb[kNN];
 #pragma unroll
             for (int k = 0; k < kNN; k++) nb[k] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (valid) {
-                // candidates: grid positions (index runs, the cell walk), or run positions (float4 runs);
-                // on the incremental map positions in its base set rpts, or kRunPos | delta positions
+                // candidates: grid positions (the runs, the cell walk); on the incremental map's runs
+                // positions in its base set rpts, or kRunPos | positions in its delta set dpts
                 float4* stage = U.nnstage[threadIdx.x >> 6];
                 const int sflag = compact ? (int)kRecNoXyz : 0;
                 if (dyn)
                     amb = lq_finish<true, true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(walked ? P.gpts : P.rpts),
                                           !certified, false, reinterpret_cast<const float4*>(P.dpts), nb, stage, sflag);
                 else
-                    amb = lq_finish<!LIVO_IDX_RUNS, true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(P.gpts),
-                                                    !certified, false, walked ? nullptr : runs, nb, stage, sflag);
+                    amb = lq_finish<false, true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(P.gpts), !certified,
+                                                 false, nullptr, nb, stage, sflag);
             }
             {
                 // the wave's 64 half records leave as one coalesced run of 64-B pieces
@@ -3982,10 +3762,7 @@ __global__ __launch_bounds__(kBlock) void k_hshare_ik(HsParams P) {
             // neighbours: the plane cache (pstate 2) holds that fit, so the
             // neighbours are not read and esti_plane not rerun.  A search (or a
             // point not fitted since one, pstate 0) fits and caches it.
-#ifndef LIVO_IK_PLANE_CACHE
-#define LIVO_IK_PLANE_CACHE 1
-#endif
-            const uint8_t ps = (search || !LIVO_IK_PLANE_CACHE) ? (uint8_t)0 : job.pstate[i];
+            const uint8_t ps = search ? (uint8_t)0 : job.pstate[i];
             const bool sel = search ? ((cnt == kNN) && !(rec->sqdist[kNN - 1] > P.max_sqd)) : !(flag & kIkDrop);
             bool fin = false;
             float pa[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -4246,9 +4023,9 @@ int launch_knn_leaf(const KnnParams& p, int n_jobs, int64_t max_n, bool seeded, 
     const dim3 grid((unsigned)(q.nb * n_jobs)), block(kKnnBlock);
     const size_t lds = knn_lds_bytes(p.ldepth + 1);
     if (seeded)
-        hipLaunchKernelGGL((k_knn_leaf<true, 1>), grid, block, lds, (hipStream_t)stream, q);
+        hipLaunchKernelGGL(k_knn_leaf<true>, grid, block, lds, (hipStream_t)stream, q);
     else
-        hipLaunchKernelGGL((k_knn_leaf<false, 1>), grid, block, lds, (hipStream_t)stream, q);
+        hipLaunchKernelGGL(k_knn_leaf<false>, grid, block, lds, (hipStream_t)stream, q);
     if (hipGetLastError() != hipSuccess) return LIVO_E_HIP;
     hipLaunchKernelGGL(k_knn_replay, dim3(kReplayBlocks), dim3(64), replay_lds_bytes(q.depth), (hipStream_t)stream, q);
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
@@ -4261,7 +4038,6 @@ int launch_knn_grid(const KnnParams& p, int n_jobs, int64_t max_n, bool seeded, 
     q.nb = (int32_t)((max_n + B - 1) / B);
     if ((int64_t)q.nb * n_jobs >= (1ll << 31)) return LIVO_E_RANGE;
     const dim3 grid((unsigned)(q.nb * n_jobs)), block(B);
-#if LIVO_IDX_RUNS
     if (q.vslots && !q.canon && !q.dyn_runs) {  // the runs of a static map: their search pass
         q.nb = (int32_t)((max_n + kEvalBlock - 1) / kEvalBlock);
         if ((int64_t)q.nb * n_jobs >= (1ll << 31)) return LIVO_E_RANGE;  // (the grid actually launched)
@@ -4270,9 +4046,7 @@ int launch_knn_grid(const KnnParams& p, int n_jobs, int64_t max_n, bool seeded, 
             hipLaunchKernelGGL(k_knn_runs<true>, rgrid, rblock, 0, (hipStream_t)stream, q);
         else
             hipLaunchKernelGGL(k_knn_runs<false>, rgrid, rblock, 0, (hipStream_t)stream, q);
-    } else
-#endif
-    if (tile) {
+    } else if (tile) {
         if (seeded)
             hipLaunchKernelGGL((k_knn_grid<true, true>), grid, block, 0, (hipStream_t)stream, q);
         else
@@ -4405,7 +4179,7 @@ int launch_iekf_eval(const KnnParams& kp, const HsParams& hp, int n_jobs, int64_
     if ((int64_t)E.k.nb * n_jobs >= (1ll << 31)) return LIVO_E_RANGE;
     const dim3 grid((unsigned)(E.k.nb * n_jobs)), block(kEvalBlock);
     // the static kind: index runs of a static map (what livo_map_build leaves)
-    const bool stat = LIVO_IDX_RUNS && kp.vslots && !kp.dyn_runs && !kp.canon && !kp.eval_gen;
+    const bool stat = kp.vslots && !kp.dyn_runs && !kp.canon && !kp.eval_gen;
     if (stat) {
         if (first)
             hipLaunchKernelGGL(k_iekf_eval<true>, grid, block, 0, (hipStream_t)stream, E);

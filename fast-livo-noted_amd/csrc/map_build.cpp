@@ -293,9 +293,6 @@ static inline unsigned long long grid_key(int64_t cx, int64_t cy, int64_t cz) {
     return (unsigned long long)(cx + kGridBias) | ((unsigned long long)(cy + kGridBias) << 21) |
            ((unsigned long long)(cz + kGridBias) << 42);
 }
-static inline uint64_t grid_hash(unsigned long long key, int log2) {
-    return (uint64_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2));
-}
 
 int build_grid_map(const float* xyz, int64_t M, int64_t stride_bytes, float cell_h, HostGridMap* out, float ppc_target) {
     if (!out || M < 0 || (M > 0 && !xyz)) return LIVO_E_INVALID;

@@ -36,6 +36,20 @@ def test_nth_element_restatement_matches_libstdcxx(tmp_path):
     assert " 0 mismatches" in out.stdout
 
 
+def test_ball_cells_matches_inline_range(tmp_path):
+    """livo_internal.h ball_cells (the cell range of a bound ball, host-callable) against a literal
+    restatement of the expressions the searches held inline: equal integer ranges and equal rejections."""
+    exe = tmp_path / "ball_cells_check"
+    # (host code only; the header's HIP vector types come with hipcc, as for the library's own .cpp files)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
+                           "-I", os.path.join(ROOT, "fast-livo-noted_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "native", "ball_cells_check.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe), "5000"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert " 0 mismatches" in out.stdout
+
+
 def _round_half_away(x):
     return np.where(x >= 0, np.floor(x + np.float32(0.5)), -np.floor(-x + np.float32(0.5)))
 

@@ -55,9 +55,6 @@ def main():
               f"{r[2] / nl * us:6.2f}  solve {r[3] / nl * us:6.2f}  slot write {r[4] / nl * us:6.2f} us")
         ph = tbuf[24 + 16 * s: 24 + 16 * s + 16]
         print("    solve: " + "  ".join(f"{k} {v / nl * us:.2f}" for k, v in zip(names, ph)) + " us")
-        if ph[8] or ph[9]:  # LIVO_TAIL_TWICE: the same T / Q code timed cold (first pass) and warm (second)
-            print(f"    I-cache probe: T cold {ph[8] / nl * us:.2f} warm {ph[1] / nl * us:.2f} us;  Q cold "
-                  f"{ph[9] / nl * us:.2f} us")
 
 
 if __name__ == "__main__":
