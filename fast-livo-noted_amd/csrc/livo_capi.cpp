@@ -165,32 +165,73 @@ struct DynDev {
     ScanCtx scan;                    // the one-launch scans' ticket and status words
 };
 
-// One batch's staging and streams.  LaserMapping batches: slots packed at
-// kLmStride (the part before the IKFoM block) followed by the jobs, one
-// contiguous staging area each way.  Lane 0 borrows the context's streams;
-// the other lanes own theirs (created on first use).
+// A batch's staging area: its slots, then its jobs, in a device buffer (d) and
+// in pinned host memory (h), one contiguous copy each way.
+struct Staging {
+    char* h = nullptr;
+    char* d = nullptr;
+    char* h_dev = nullptr;  // h's device address (host-mapped), for the kernel copies; null: DMA copies
+    size_t cap = 0;
+    void free() {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        h = d = h_dev = nullptr;
+        cap = 0;
+    }
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return LIVO_OK;
+        free();
+        if (hipMalloc((void**)&d, bytes) != hipSuccess) {
+            d = nullptr;
+            return LIVO_E_OOM;
+        }
+        // mapped + coherent: a submitted batch's staging copies are kernels
+        // (launch_copy_words) that read and write it; DMA copies behind another
+        // lane's kernels held the submitting host 2-3 ms per batch
+        if (hipHostMalloc((void**)&h, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+            h = nullptr;
+            return LIVO_E_OOM;
+        }
+        if (hipHostGetDevicePointer((void**)&h_dev, h, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            h_dev = nullptr;  // DMA copies then
+        }
+        cap = bytes;
+        return LIVO_OK;
+    }
+};
+
+// What batch_enqueue decided for the batch a lane carries; batch_collect reads it.
+struct BatchPlan {
+    int model = 0;
+    int32_t n = 0;
+    bool fused = false;  // search + replay + plane pass + solve in one launch per evaluation
+    bool kcopy = false;  // staging copies by kernel over host-mapped memory (else DMA)
+    bool wb = false;     // the stopping solve writes its slot into the host staging copy itself
+    bool iv = false;     // iVox search (its own overflow replay lists)
+    int prof = 0;        // profiling level of this batch (0: no event is recorded)
+    Staging* stage = nullptr;
+    size_t stride = 0;   // bytes from one slot to the next
+    int ngroups = 0;
+    struct Group {
+        int32_t first, count;
+        int max_nblk;
+        int64_t max_n, off;  // off: the group's start in the lane's replay list
+        hipStream_t st;
+    } g[kMaxGroups];
+};
+
+// One batch in flight: its staging (one area per model: LaserMapping slots are
+// packed at kLmStride, the part before the IKFoM block; IKFoM slots are whole),
+// its plan and its end events.  Every lane queues on the context's streams.
 struct BatchLane {
-    char* h_lm = nullptr;
-    char* d_lm = nullptr;
-    char* h_lm_dev = nullptr;  // h_lm's device address (host-mapped), for the kernel copies
-    size_t lm_cap = 0;
-    // IKFoM batches: whole slots (their IKFoM block included) then the jobs,
-    // host pinned and device, per lane so two IKFoM batches can be in flight
-    char* h_ik = nullptr;
-    char* d_ik = nullptr;
-    char* h_ik_dev = nullptr;  // h_ik's device address (host-mapped), for the kernel copies
-    size_t ik_cap = 0;
+    Staging stage[2];  // by model
     hipStream_t st[kMaxGroups] = {};
-    hipEvent_t fork = nullptr;
     hipEvent_t done[kMaxGroups] = {};  // each group's last operation (its slot copy back)
-    bool owned = false;       // streams created for this lane
-    bool owned_fork = false;  // fork event created for this lane
     bool busy = false;   // submitted, not yet collected
     int32_t ticket = -1;
     int32_t n = 0;
-    int model = 0;
-    int ngroups = 0;
-    int32_t gfirst[kMaxGroups] = {}, gcount[kMaxGroups] = {};
+    BatchPlan plan;
     std::vector<int32_t> ids;
 };
 
@@ -204,11 +245,10 @@ struct livo_ctx {
     hipStream_t xstream[kMaxGroups - 1] = {};
     hipEvent_t xjoin[kMaxGroups - 1] = {};
     // stream groups per batch (LIVO_STREAM_GROUPS; 0: the default of
-    // batch_enqueue, four for the fused and IKFoM paths, two for iVox,
+    // batch_plan, four for the fused and IKFoM paths, two for iVox,
     // profiles/r04_ab_groups.txt)
     int groups = 0;
     int leaf_size = kLeafSize;         // leaf-map points per leaf (LIVO_LEAF_SIZE)
-    hipEvent_t fork = nullptr;
     livo_params params{};
     // map
     MapNode* nodes = nullptr;
@@ -299,20 +339,16 @@ struct livo_ctx {
     hipEvent_t bsrc_free[2] = {nullptr, nullptr};
     bool bsrc_used[2] = {false, false};
     int bsrc_next = 0;
-    // batch resources
-    int32_t slot_cap = 0;
+    // one slot and one job: the scratch of the single-scan entry points (ensure_slot)
     IekfSlot* d_slots = nullptr;
     // batches in flight (livo_iekf_update_batch_submit): lane 0 also carries
     // every synchronous batch
     BatchLane lane[LIVO_MAX_INFLIGHT];
     int32_t lane_gen = 0;  // tickets: generation * LIVO_MAX_INFLIGHT + lane
-    bool lane_own_streams = false;  // LIVO_LANE_STREAMS=own: lanes > 0 on streams of their own
     // LIVO_LANE_SERIAL=1: a queued batch starts only once every group of the one
     // before it is done; default 0: its group 0 starts when stream 0 frees, beside
     // the other groups' tails (20.5k vs 19.1k updates/s, profiles/r03_ab_lanes.txt)
     bool lane_serial = false;
-    bool lane_zc = true;            // submitted batches: staging copies by kernel over host-mapped memory (LIVO_LANE_ZC)
-    bool sync_zc = false;           // synchronous batches too (LIVO_SYNC_ZC)
     bool slot_wb = true;            // fused batches: the stopping solve writes the slot back (LIVO_SLOT_WB)
     // the fused run searches on a static map store hot-only neighbour records, the
     // coordinates filled on demand (LIVO_REC_COMPACT=0: full records)
@@ -351,6 +387,11 @@ struct livo_ctx {
     do {                                            \
         if ((x) != hipSuccess) return LIVO_E_HIP;   \
     } while (0)
+#define RC_TRY(x)                  \
+    do {                           \
+        const int rc_ = (x);       \
+        if (rc_) return rc_;       \
+    } while (0)
 
 // Host wait for a stream: spin on hipStreamQuery (microseconds to notice
 // completion), then fall back to the blocking wait after ~50 ms.
@@ -385,20 +426,19 @@ static int ensure_scratch(livo_ctx* c, size_t bytes) {
     return LIVO_OK;
 }
 
-static int ensure_slots(livo_ctx* c, int32_t n) {
-    if (n <= c->slot_cap) return LIVO_OK;
-    int32_t cap = std::max(n, 8);
-    dev_free(c->d_slots);
-    dev_free(c->d_jobs);
-    if (c->h_slots) (void)hipHostFree(c->h_slots);
-    if (c->h_jobs) (void)hipHostFree(c->h_jobs);
-    c->h_slots = nullptr;
-    c->h_jobs = nullptr;
-    c->slot_cap = 0;
-    if (dev_alloc(&c->d_slots, cap) || dev_alloc(&c->d_jobs, cap)) return LIVO_E_OOM;
-    if (hipHostMalloc((void**)&c->h_slots, sizeof(IekfSlot) * cap, hipHostMallocDefault) != hipSuccess) return LIVO_E_OOM;
-    if (hipHostMalloc((void**)&c->h_jobs, sizeof(HsJob) * cap, hipHostMallocDefault) != hipSuccess) return LIVO_E_OOM;
-    c->slot_cap = cap;
+// The single-scan entry points' slot and job (livo_knn, livo_h_share, livo_ivox_knn,
+// livo_map_incremental), device and pinned host; batches stage in their lane.
+static int ensure_slot(livo_ctx* c) {
+    if (!c->d_slots && dev_alloc(&c->d_slots, 1)) return LIVO_E_OOM;
+    if (!c->d_jobs && dev_alloc(&c->d_jobs, 1)) return LIVO_E_OOM;
+    if (!c->h_slots && hipHostMalloc((void**)&c->h_slots, sizeof(IekfSlot), hipHostMallocDefault) != hipSuccess) {
+        c->h_slots = nullptr;
+        return LIVO_E_OOM;
+    }
+    if (!c->h_jobs && hipHostMalloc((void**)&c->h_jobs, sizeof(HsJob), hipHostMallocDefault) != hipSuccess) {
+        c->h_jobs = nullptr;
+        return LIVO_E_OOM;
+    }
     return LIVO_OK;
 }
 
@@ -408,87 +448,25 @@ static_assert(kLmStride % alignof(HsJob) == 0 && kLmStride % alignof(IekfSlot) =
 static_assert(kLmStride % 16 == 0, "kernel staging copies move 16-B words");
 // bytes of a batch's packed staging area, rounded up to whole 16-B words
 static size_t lm_bytes(int32_t n) { return ((size_t)n * (kLmStride + sizeof(HsJob)) + 15) & ~(size_t)15; }
-static int ensure_lm(BatchLane& B, int32_t n) {
-    const size_t need = lm_bytes(n);
-    if (need <= B.lm_cap) return LIVO_OK;
-    const size_t cap = std::max(need, lm_bytes(8));
-    dev_free(B.d_lm);
-    if (B.h_lm) (void)hipHostFree(B.h_lm);
-    B.h_lm = nullptr;
-    B.lm_cap = 0;
-    if (hipMalloc((void**)&B.d_lm, cap) != hipSuccess) {
-        B.d_lm = nullptr;
-        return LIVO_E_OOM;
-    }
-    // mapped + coherent: the lane's kernel copies (launch_copy_words) read and write it
-    if (hipHostMalloc((void**)&B.h_lm, cap, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        B.h_lm = nullptr;
-        return LIVO_E_OOM;
-    }
-    B.h_lm_dev = nullptr;
-    if (hipHostGetDevicePointer((void**)&B.h_lm_dev, B.h_lm, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        B.h_lm_dev = nullptr;  // DMA copies then
-    }
-    B.lm_cap = cap;
-    return LIVO_OK;
+// bytes of a batch's staging area by model, never less than a batch of 8 needs
+static size_t stage_bytes(int model, int32_t n) {
+    n = std::max(n, 8);
+    return model == kModelIkfom ? (size_t)n * (sizeof(IekfSlot) + sizeof(HsJob)) : lm_bytes(n);
 }
 
-static int ensure_ik(BatchLane& B, int32_t n) {
-    const size_t need = (size_t)n * (sizeof(IekfSlot) + sizeof(HsJob));
-    if (need <= B.ik_cap) return LIVO_OK;
-    const size_t cap = std::max(need, (size_t)8 * (sizeof(IekfSlot) + sizeof(HsJob)));
-    dev_free(B.d_ik);
-    if (B.h_ik) (void)hipHostFree(B.h_ik);
-    B.h_ik = nullptr;
-    B.ik_cap = 0;
-    if (hipMalloc((void**)&B.d_ik, cap) != hipSuccess) {
-        B.d_ik = nullptr;
-        return LIVO_E_OOM;
-    }
-    // mapped + coherent: a submitted batch's staging copies are kernels (as the
-    // LaserMapping lanes'); DMA copies behind another lane's kernels held the
-    // submitting host 2-3 ms per batch
-    if (hipHostMalloc((void**)&B.h_ik, cap, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        B.h_ik = nullptr;
-        return LIVO_E_OOM;
-    }
-    B.h_ik_dev = nullptr;
-    if (hipHostGetDevicePointer((void**)&B.h_ik_dev, B.h_ik, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        B.h_ik_dev = nullptr;  // DMA copies then
-    }
-    B.ik_cap = cap;
-    return LIVO_OK;
-}
-
-// A lane's group streams: lane 0 the context's, the others their own.
+// A lane's end events and group streams.  Every lane queues on the context's
+// streams: a batch submitted behind another starts the moment the device
+// finishes the first (no host round trip, copy or launch latency in between),
+// without running beside it (MI355X, 8 x 100k: two batches on streams of their
+// own, so concurrent, 10-13k updates/s against 16.9k for one at a time,
+// profiles/r03_ab_lanes.txt).
 static int lane_streams(livo_ctx* c, int L) {
     BatchLane& B = c->lane[L];
     if (B.st[0]) return LIVO_OK;
     for (int k = 0; k < kMaxGroups; k++)
         if (!B.done[k] && hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming) != hipSuccess) return LIVO_E_HIP;
-    if (L == 0) {
-        B.st[0] = c->stream;
-        for (int k = 0; k < kMaxGroups - 1; k++) B.st[k + 1] = c->xstream[k];
-        B.fork = c->fork;
-        return LIVO_OK;
-    }
-    // By default every lane queues on the context's streams: a batch submitted
-    // behind another starts the moment the device finishes the first (no host
-    // round trip, copy or launch latency in between), without running beside
-    // it (MI355X, 8 x 100k: two batches on their own streams, so concurrent,
-    // 10-13k updates/s against 16.9k for one at a time, profiles/r03_ab_lanes.txt).
-    // LIVO_LANE_STREAMS=own gives each lane its own streams.
-    if (!c->lane_own_streams) {
-        for (int k = 0; k < kMaxGroups; k++) B.st[k] = c->lane[0].st[k] ? c->lane[0].st[k] : (k ? c->xstream[k - 1] : c->stream);
-    } else {
-        B.owned = true;
-        for (int k = 0; k < kMaxGroups; k++)
-            if (hipStreamCreateWithFlags(&B.st[k], hipStreamNonBlocking) != hipSuccess) return LIVO_E_HIP;
-    }
-    if (hipEventCreateWithFlags(&B.fork, hipEventDisableTiming) != hipSuccess) return LIVO_E_HIP;
-    B.owned_fork = true;
+    B.st[0] = c->stream;
+    for (int k = 0; k < kMaxGroups - 1; k++) B.st[k + 1] = c->xstream[k];
     return LIVO_OK;
 }
 
@@ -1873,7 +1851,6 @@ int livo_ctx_create(int device, const livo_params* p, livo_ctx** out) {
     if (const char* env = std::getenv("LIVO_KNN_KIND"))
         c->knn_kind = std::strcmp(env, "leaf") == 0 ? 0 : std::strcmp(env, "grid") == 0 ? 1 : 2;
     if (const char* env = std::getenv("LIVO_VRUNS")) c->vruns = std::atoi(env) != 0;
-    if (const char* env = std::getenv("LIVO_LANE_STREAMS")) c->lane_own_streams = std::strcmp(env, "own") == 0;
     if (const char* env = std::getenv("LIVO_BRUNS")) c->bruns = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_BR_HA")) {
         const float v = (float)std::atof(env);
@@ -1884,8 +1861,6 @@ int livo_ctx_create(int device, const livo_params* p, livo_ctx** out) {
         if (v > 0.5f && v < 20.f) c->br_r = v;
     }
     if (const char* env = std::getenv("LIVO_LANE_SERIAL")) c->lane_serial = std::atoi(env) != 0;
-    if (const char* env = std::getenv("LIVO_LANE_ZC")) c->lane_zc = std::atoi(env) != 0;
-    if (const char* env = std::getenv("LIVO_SYNC_ZC")) c->sync_zc = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_SLOT_WB")) c->slot_wb = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_REC_COMPACT")) c->rec_compact = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_EVAL_GEN")) c->eval_gen = std::atoi(env) != 0;
@@ -1899,7 +1874,7 @@ int livo_ctx_create(int device, const livo_params* p, livo_ctx** out) {
         if (v > 0.f) c->grid_cell = v;
     }
     if (set_device(c) || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->fork, hipEventDisableTiming) != hipSuccess || create_group_streams(c)) {
+        create_group_streams(c)) {
         delete c;
         return LIVO_E_HIP;
     }
@@ -1911,11 +1886,7 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (!c) return LIVO_E_INVALID;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (BatchLane& B : c->lane) {  // batches never collected: let them finish
-        for (int k = 0; k < kMaxGroups && B.owned; k++)
-            if (B.st[k]) (void)hipStreamSynchronize(B.st[k]);
-    }
-    for (int k = 0; k < kMaxGroups - 1; k++)
+    for (int k = 0; k < kMaxGroups - 1; k++)  // batches never collected: let them finish
         if (c->xstream[k]) (void)hipStreamSynchronize(c->xstream[k]);
     if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
     if (c->cp_stream) (void)hipStreamSynchronize(c->cp_stream);
@@ -1959,14 +1930,7 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->h_slots) (void)hipHostFree(c->h_slots);
     if (c->h_jobs) (void)hipHostFree(c->h_jobs);
     for (BatchLane& B : c->lane) {
-        dev_free(B.d_lm);
-        if (B.h_lm) (void)hipHostFree(B.h_lm);
-        if (B.owned)
-            for (int k = 0; k < kMaxGroups; k++)
-                if (B.st[k]) (void)hipStreamDestroy(B.st[k]);
-        if (B.owned_fork && B.fork) (void)hipEventDestroy(B.fork);
-        dev_free(B.d_ik);
-        if (B.h_ik) (void)hipHostFree(B.h_ik);
+        for (Staging& s : B.stage) s.free();
         for (hipEvent_t e : B.done)
             if (e) (void)hipEventDestroy(e);
     }
@@ -1983,7 +1947,6 @@ int livo_ctx_destroy(livo_ctx* c) {
         if (c->xjoin[k]) (void)hipEventDestroy(c->xjoin[k]);
         if (c->xstream[k]) (void)hipStreamDestroy(c->xstream[k]);
     }
-    if (c->fork) (void)hipEventDestroy(c->fork);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return LIVO_OK;
@@ -2474,7 +2437,7 @@ int livo_knn(livo_ctx* c, const float* q, int64_t n, int32_t k, int32_t* idx, fl
     if (n == 0) return LIVO_OK;
     if (n > (int64_t)0x7FFFFFFF - kBlock) return LIVO_E_RANGE;
     if (set_device(c)) return LIVO_E_HIP;
-    int rc = ensure_slots(c, 1);
+    int rc = ensure_slot(c);
     if (rc) return rc;
     const size_t qb = (size_t)n * 4 * sizeof(float), rb = (size_t)n * sizeof(NNRec);
     rc = ensure_scratch(c, qb + rb + 256);
@@ -3163,7 +3126,7 @@ int livo_h_share(livo_ctx* c, int32_t id, const livo_state* state, int search_en
     if (!s) return LIVO_E_NOSCAN;
     if (!map_ready(c)) return LIVO_E_NOMAP;
     if (set_device(c)) return LIVO_E_HIP;
-    int rc = ensure_slots(c, 1);
+    int rc = ensure_slot(c);
     if (rc) return rc;
     const int64_t N = s->n;
     // debug scratch: normvec N*4, world N*3, sel N; laserCloudOri compaction: flags N, pos N, ori N*3, corr N*4
@@ -3289,6 +3252,256 @@ int livo_h_share(livo_ctx* c, int32_t id, const livo_state* state, int search_en
 // in two halves over one batch lane: batch_enqueue puts the whole loop, and the
 // copies of the slots back, on the lane's streams; batch_collect waits for them
 // and unpacks the results.  Profiling (events, timings) on synchronous batches only.
+static bool batch_fused(const livo_ctx* c, int model) {
+    return c->fused && model == kModelLaserMapping && c->backend == LIVO_BACKEND_IKDTREE && c->knn_kind == 2;
+}
+
+// Slot b of a batch in its lane's staging area, host and device.  (A packed
+// LaserMapping slot is addressed as an IekfSlot whose IKFoM block lies outside
+// the buffer; the LaserMapping kernels never touch it.)
+static IekfSlot& hslot(const BatchPlan& P, int32_t b) {
+    return *reinterpret_cast<IekfSlot*>(P.stage->h + (size_t)b * P.stride);
+}
+static IekfSlot* dslot(const BatchPlan& P, int32_t b) {
+    return reinterpret_cast<IekfSlot*>(P.stage->d + (size_t)b * P.stride);
+}
+
+// Profiling levels at which an event is recorded (bit k: livo_ctx_set_profiling level k).
+enum { kProfL1 = 1 << 1, kProfL2 = 1 << 2, kProfAny = kProfL1 | kProfL2 };
+// Records ev on st if the batch is profiled at one of `levels`; nothing otherwise.
+static hipError_t prof_record(const BatchPlan& P, int levels, hipEvent_t ev, hipStream_t st) {
+    return (levels >> P.prof) & 1 ? hipEventRecord(ev, st) : hipSuccess;
+}
+
+// What is refused is refused here, before any device work, so a refused batch
+// leaves nothing queued.
+static int batch_validate(livo_ctx* c, int L, int32_t n, const int32_t* ids, int model, bool sync) {
+    if (!map_ready(c)) return LIVO_E_NOMAP;
+    if (model == kModelIkfom && c->backend != LIVO_BACKEND_IKDTREE) return LIVO_E_INVALID;  // ikd-Tree h-model only
+    for (int32_t b = 0; b < n; b++)
+        if (!get_scan_q(c, ids[b])) return LIVO_E_NOSCAN;
+    // a scan's neighbour records, plane cache and partials are per scan: the
+    // same id twice in one batch would have two updates write them concurrently
+    std::vector<int32_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return LIVO_E_INVALID;
+    // nor may a scan be in two batches in flight
+    for (int l = 0; l < LIVO_MAX_INFLIGHT; l++)
+        if (l != L && c->lane[l].busy)
+            for (int32_t id : c->lane[l].ids)
+                if (std::binary_search(sorted.begin(), sorted.end(), id)) return LIVO_E_INVALID;
+    // the unfused LaserMapping passes (iVox: per-context search scratch) run as
+    // synchronous batches only; IKFoM batches keep their staging and replay
+    // lists per lane
+    if (!batch_fused(c, model) && model != kModelIkfom && (L != 0 || !sync)) return LIVO_E_INVALID;
+    return LIVO_OK;
+}
+
+// The lane's plan for a batch of n: the path it takes and its stream groups.
+// Returns the batch's points (the replay list's size).
+static int64_t batch_plan(livo_ctx* c, int L, int32_t n, const int32_t* ids, int model, bool sync) {
+    BatchLane& B = c->lane[L];
+    BatchPlan& P = B.plan;
+    P.model = model;
+    P.n = n;
+    P.fused = batch_fused(c, model);
+    // LaserMapping slots: only the part before the IKFoM block, packed at
+    // kLmStride; IKFoM slots whole.  The jobs lie behind the slots, so the
+    // batch crosses PCIe in one copy each way.
+    P.stage = &B.stage[model];
+    P.stride = model == kModelIkfom ? sizeof(IekfSlot) : kLmStride;
+    // kernel copies for submitted batches, which may queue behind another on the
+    // shared streams (a DMA copy there waits on an engine hand-off); DMA copies
+    // for synchronous ones (profiles/r03_ab_lanes.txt, r04_ab_block_order.txt)
+    P.kcopy = !sync && P.stage->h_dev;
+    // fused batches: the solve that stops a scan writes its slot into the
+    // host-mapped staging copy itself (LIVO_SLOT_WB=0: copies after the batch)
+    P.wb = P.fused && P.stage->h_dev && c->slot_wb;
+    P.iv = c->backend == LIVO_BACKEND_IVOX && model != kModelIkfom;  // (synchronous batches only: lane 0)
+    // synchronous batches only; 1: first-search events, 2: every evaluation, the batch span and the gap
+    P.prof = sync && L == 0 && c->events_ready ? c->profiling : 0;
+    // The batch in groups on separate streams: the latency-bound kernels of one
+    // group (18x18 solve, tie replay, launch gaps, evaluations without a search)
+    // overlap the throughput-bound k-NN / plane passes of the others.  Each group
+    // keeps its own replay list.  Default: four groups, one per hardware queue
+    // (round 4, 8 x 100k distinct scans, pipelined: 1 / 2 / 3 / 4 groups 18675 /
+    // 21170 / 22350 / 22984 updates/s; 6 / 8 share the box's 4 queues and lose,
+    // profiles/r04_ab_groups.txt; 8 x 200k on the 10M map: 4437 vs 3960 with two).
+    // IKFoM four too (5.40k vs 5.13k with two); the iVox path two (1,520 vs 1,513 with four)
+    const int auto_groups = (P.fused || model == kModelIkfom) ? 4 : 2;
+    P.ngroups = std::max(1, std::min<int>(c->groups > 0 ? c->groups : auto_groups, n));
+    int64_t off = 0;
+    for (int gi = 0; gi < P.ngroups; gi++) {
+        BatchPlan::Group& G = P.g[gi];
+        G.first = (int32_t)((int64_t)n * gi / P.ngroups);
+        G.count = (int32_t)((int64_t)n * (gi + 1) / P.ngroups) - G.first;
+        G.max_nblk = 1;
+        G.max_n = 1;
+        G.off = off;
+        G.st = B.st[gi];
+        for (int32_t b = G.first; b < G.first + G.count; b++) {
+            const ScanBuf* s = get_scan_q(c, ids[b]);
+            G.max_nblk = std::max(G.max_nblk, (int)s->nblk);
+            G.max_n = std::max<int64_t>(G.max_n, s->n);
+            off += s->n;
+        }
+    }
+    return off;
+}
+
+// The host copies of the batch's slots and jobs.
+static void batch_fill(livo_ctx* c, const BatchPlan& P, const int32_t* ids, const livo_state* states,
+                       const livo_state* priors, const livo_ikfom_state* ik_states) {
+    HsJob* const hjobs = reinterpret_cast<HsJob*>(P.stage->h + (size_t)P.n * P.stride);
+    const int max_iter = c->params.max_iterations;
+    for (int32_t b = 0; b < P.n; b++) {
+        if (P.model == kModelIkfom) {
+            init_slot_ik(hslot(P, b), ik_states[b], max_iter);
+        } else {
+            init_slot(hslot(P, b), states[b], priors ? priors[b] : states[b], max_iter, kSlotLmBytes);
+        }
+        fill_job(hjobs[b], *get_scan_q(c, ids[b]), dslot(P, b));
+        if (P.wb) hjobs[b].host_slot = reinterpret_cast<uint4*>(P.stage->h_dev + (size_t)b * P.stride);
+    }
+}
+
+// This lane's replay counters (one per group).
+static unsigned* lane_rcount(livo_ctx* c, int L) { return c->d_replay_count + (size_t)L * kMaxGroups; }
+
+// Each group stages its own slots and jobs on its own stream and starts from
+// there: no fork from stream 0, so a group waits only for its own scans'
+// uploads and, in a pipelined farm, for its own stream's previous batch (a
+// queued batch's group g does not wait for the previous batch's group 0).
+// prev: the batch whose every group this one waits for (LIVO_LANE_SERIAL=1).
+static int stage_group(livo_ctx* c, int L, const BatchPlan& P, int gi, const int32_t* ids, const BatchLane* prev) {
+    static_assert(sizeof(HsJob) % 16 == 0 && sizeof(IekfSlot) % 16 == 0 && kLmStride % 16 == 0, "16-B word copies");
+    const BatchPlan::Group& G = P.g[gi];
+    const hipStream_t st = G.st;
+    for (int32_t b = G.first; b < G.first + G.count; b++) {
+        ScanBuf* s = get_scan_q(c, ids[b]);
+        // a scan whose asynchronous upload may still run: the group waits on the device
+        if (s->pending) HIP_TRY(hipStreamWaitEvent(st, s->ready, 0));
+        // IKFoM: its searches rewrite the neighbours without refitting the cached planes
+        if (P.model == kModelIkfom && s->n > 0) HIP_TRY(hipMemsetAsync(s->pstate, 0, (size_t)s->n, st));
+        // the unfused passes may read cached neighbours' coordinates (seeded rematch, IKFoM,
+        // an iVox query with no candidate keeps its record)
+        if (!P.fused) RC_TRY(ensure_nn_coords(c, s, st));
+    }
+    if (prev)
+        for (int q = 0; q < prev->plan.ngroups; q++) HIP_TRY(hipStreamWaitEvent(st, prev->done[q], 0));
+    const size_t s0 = (size_t)G.first * P.stride, sb = (size_t)G.count * P.stride;
+    const size_t j0 = (size_t)P.n * P.stride + (size_t)G.first * sizeof(HsJob), jb = (size_t)G.count * sizeof(HsJob);
+    if (P.kcopy) {
+        RC_TRY(launch_copy_ranges(P.stage->h_dev, P.stage->d, s0, sb, j0, jb, st));
+    } else {
+        HIP_TRY(hipMemcpyAsync(P.stage->d + s0, P.stage->h + s0, sb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(P.stage->d + j0, P.stage->h + j0, jb, hipMemcpyHostToDevice, st));
+    }
+    if (!P.fused) HIP_TRY(hipMemsetAsync(lane_rcount(c, L) + gi, 0, sizeof(unsigned), st));
+    if (P.iv) HIP_TRY(hipMemsetAsync(c->d_replay_count2 + gi, 0, sizeof(unsigned), st));
+    // profiling: each group's first search starts at ev[gi][0]
+    HIP_TRY(prof_record(P, kProfAny, c->ev[gi][0], st));
+    return LIVO_OK;
+}
+
+// A group's kernel parameters: its jobs and its slices of the lane's replay lists.
+static void group_params(livo_ctx* c, int L, const BatchPlan& P, int gi, KnnParams& kp, HsParams& hp) {
+    const BatchPlan::Group& G = P.g[gi];
+    HsJob* const jobs = reinterpret_cast<HsJob*>(P.stage->d + (size_t)P.n * P.stride) + G.first;
+    hp = make_hs_params(c);
+    hp.jobs = jobs;
+    kp = make_knn_params(c);
+    kp.jobs = jobs;
+    kp.replay_count = lane_rcount(c, L) + gi;
+    kp.replay_list = c->d_replay_list + (size_t)L * c->replay_cap + G.off;
+    kp.replay_count2 = P.iv ? c->d_replay_count2 + gi : nullptr;
+    kp.replay_list2 = P.iv ? c->d_replay_list2 + G.off : nullptr;
+    // the iVox overflow pass of each group has its own scratch slices (groups run concurrently)
+    if (kp.iv.scratch) kp.iv.scratch += (int64_t)gi * c->iv.big_threads * c->iv.big_slice;
+    // the last plane-pass block of each scan runs its solve (IKFoM: k_solve_ik, queue_unfused)
+    hp.solve = P.model == kModelIkfom ? 0 : 1;
+    hp.replay_count = kp.replay_count;
+    hp.replay_count2 = kp.replay_count2;
+}
+
+// The fused loop: one launch per evaluation and group (a launch whose scans all stopped exits at once).
+static int queue_fused(livo_ctx* c, const BatchPlan& P, const int32_t* ids, const KnnParams* kp, const HsParams* hp) {
+    // (rec_compact: the ikd-Tree backend's run searches on a static map, the only writer of hot-only records)
+    if (kp[0].rec_compact)
+        for (int32_t b = 0; b < P.n; b++) get_scan_q(c, ids[b])->nn_compact = true;
+    const int evals = c->params.max_iterations + 1;
+    for (int e = 0; e < evals; e++)
+        for (int gi = 0; gi < P.ngroups; gi++) {
+            const BatchPlan::Group& G = P.g[gi];
+            // level 2: ev[gi][e] before evaluation e, ev[gi][evals] after the last (finish_group)
+            if (e > 0) HIP_TRY(prof_record(P, kProfL2, c->ev[gi][e], G.st));
+            RC_TRY(launch_iekf_eval(kp[gi], hp[gi], G.count, G.max_n, e == 0, G.st));
+            if (e == 0) HIP_TRY(prof_record(P, kProfL1, c->ev[gi][1], G.st));
+        }
+    return LIVO_OK;
+}
+
+// The separate passes: per evaluation and group the search, the plane pass and the solve.
+static int queue_unfused(livo_ctx* c, const BatchPlan& P, const KnnParams* kp, const HsParams* hp) {
+    const int evals = c->params.max_iterations + 1;
+    const bool ik = P.model == kModelIkfom;
+    for (int e = 0; e < evals; e++)
+        for (int gi = 0; gi < P.ngroups; gi++) {
+            const BatchPlan::Group& G = P.g[gi];
+            if (e > 0) HIP_TRY(prof_record(P, kProfL2, c->ev[gi][3 * e], G.st));
+            // leaf-map search; rematch passes are bounded by the previous neighbours
+            // (the group's replay count was zeroed before the batch / by the last k_solve)
+            RC_TRY(backend_knn(c, kp[gi], G.count, G.max_n, e > 0, G.st));
+            HIP_TRY(prof_record(P, e == 0 ? kProfAny : kProfL2, c->ev[gi][3 * e + 1], G.st));
+            RC_TRY(ik ? launch_hshare_ik(hp[gi], G.count, G.max_nblk, e == 0, G.st)
+                      : launch_hshare(hp[gi], G.count, G.max_nblk, e == 0, G.st));
+            // IKFoM: the reduction, the measurement-free part of the update and the gain (k_solve_ik)
+            if (ik) RC_TRY(launch_solve_ik(hp[gi], G.count, G.st));
+        }
+    return LIVO_OK;
+}
+
+// Each group copies its own slots back on its own stream (no cross-stream
+// join before the copy) and records its end; the host then waits for every group.
+static int finish_group(livo_ctx* c, BatchLane& B, const BatchPlan& P, int gi) {
+    const BatchPlan::Group& G = P.g[gi];
+    const int last_ev = P.fused ? c->params.max_iterations + 1 : 3 * LIVO_MAX_EVALS;
+    HIP_TRY(prof_record(P, kProfL2, c->ev[gi][last_ev], G.st));
+    if (P.wb) {
+        // (written by the stopping solves)
+    } else if (P.kcopy) {
+        RC_TRY(launch_copy_words(dslot(P, G.first), P.stage->h_dev + (size_t)G.first * P.stride, P.stride * G.count,
+                                 G.st));
+    } else {
+        HIP_TRY(hipMemcpyAsync(&hslot(P, G.first), dslot(P, G.first), P.stride * G.count, hipMemcpyDeviceToHost, G.st));
+    }
+    // this batch's end on the group's stream (another lane's batch may queue behind it)
+    HIP_TRY(hipEventRecord(B.done[gi], G.st));
+    return LIVO_OK;
+}
+
+// Profiling level 2, around the batch on the main stream: its start and the
+// replay count of this batch only (every batch's replays add to the counter) ...
+static int prof_batch_begin(livo_ctx* c, const BatchPlan& P) {
+    if (P.prof < 2) return LIVO_OK;
+    HIP_TRY(hipEventRecord(c->b_start, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_replay_total, 0, 8, c->stream));
+    return LIVO_OK;
+}
+// ... and, once every group's searches have run (joined into the main stream),
+// the counter's read-back and the batch's end.
+static int prof_batch_end(livo_ctx* c, const BatchPlan& P) {
+    if (P.prof < 2) return LIVO_OK;
+    for (int gi = 1; gi < P.ngroups; gi++) {
+        HIP_TRY(hipEventRecord(c->xjoin[gi - 1], P.g[gi].st));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->xjoin[gi - 1], 0));
+    }
+    HIP_TRY(hipMemcpyAsync(&c->last_replays, c->d_replay_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_replay_total, 0, 8, c->stream));
+    HIP_TRY(hipEventRecord(c->b_end[c->b_par], c->stream));
+    return LIVO_OK;
+}
+
 static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int model, const livo_state* states,
                          const livo_state* priors, const livo_ikfom_state* ik_states, bool sync) {
     if (!c || n < 0 || (n > 0 && (!ids || (model == kModelIkfom ? !ik_states : !states)))) return LIVO_E_INVALID;
@@ -3296,280 +3509,122 @@ static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int 
     if (B.busy) return LIVO_E_BUSY;
     B.n = 0;
     if (n == 0) return LIVO_OK;
-    if (!map_ready(c)) return LIVO_E_NOMAP;
-    if (model == kModelIkfom && c->backend != LIVO_BACKEND_IKDTREE) return LIVO_E_INVALID;  // ikd-Tree h-model only
-    for (int32_t b = 0; b < n; b++)
-        if (!get_scan_q(c, ids[b])) return LIVO_E_NOSCAN;
-    {
-        // a scan's neighbour records, plane cache and partials are per scan: the
-        // same id twice in one batch would have two updates write them concurrently
-        std::vector<int32_t> sorted(ids, ids + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return LIVO_E_INVALID;
-        // nor may a scan be in two batches in flight
-        for (int l = 0; l < LIVO_MAX_INFLIGHT; l++)
-            if (l != L && c->lane[l].busy)
-                for (int32_t id : c->lane[l].ids)
-                    if (std::binary_search(sorted.begin(), sorted.end(), id)) return LIVO_E_INVALID;
-    }
-    const bool lm = model != kModelIkfom;
-    // the fused evaluation: search + replay + plane pass + solve in one launch
-    const bool fused = c->fused && model == kModelLaserMapping && c->backend == LIVO_BACKEND_IKDTREE &&
-                       c->knn_kind == 2;
-    // the unfused LaserMapping passes (iVox: per-context search scratch) run as
-    // synchronous batches only; IKFoM batches keep their staging and replay
-    // lists per lane (checked before any device work, so a refused submit
-    // leaves nothing queued)
-    if (!fused && lm && (L != 0 || !sync)) return LIVO_E_INVALID;
+    RC_TRY(batch_validate(c, L, n, ids, model, sync));
     if (set_device(c)) return LIVO_E_HIP;
-    int rc = lane_streams(c, L);
-    if (rc) return rc;
-    rc = lm ? ensure_lm(B, n) : ensure_ik(B, n);
-    if (rc) return rc;
-    // Slots and jobs: the IKFoM model uses whole slots (c->h_slots / d_slots);
-    // the LaserMapping model only the part before the IKFoM block, packed at
-    // kLmStride with the jobs behind them, so the batch crosses PCIe in one
-    // copy each way.  (A packed slot is addressed as an IekfSlot whose IKFoM
-    // block lies outside the buffer; the LaserMapping kernels never touch it.)
-    const size_t stride = lm ? kLmStride : sizeof(IekfSlot);
-    char* const hbase = lm ? B.h_lm : B.h_ik;
-    char* const dbase = lm ? B.d_lm : B.d_ik;
-    HsJob* const hjobs = reinterpret_cast<HsJob*>(hbase + (size_t)n * stride);
-    HsJob* const djobs = reinterpret_cast<HsJob*>(dbase + (size_t)n * stride);
-    auto hslot = [&](int32_t b) -> IekfSlot& { return *reinterpret_cast<IekfSlot*>(hbase + (size_t)b * stride); };
-    auto dslot = [&](int32_t b) { return reinterpret_cast<IekfSlot*>(dbase + (size_t)b * stride); };
-    const int max_iter = c->params.max_iterations;
-    // fused batches: the solve that stops a scan writes its slot into the
-    // host-mapped staging copy itself (LIVO_SLOT_WB=0: copies after the batch)
-    const bool wb = fused && lm && B.h_lm_dev && c->slot_wb;
-    int64_t total_n = 0;
-    for (int32_t b = 0; b < n; b++) {
-        ScanBuf* s = get_scan_q(c, ids[b]);
-        if (model == kModelIkfom) {
-            init_slot_ik(hslot(b), ik_states[b], max_iter);
-        } else {
-            init_slot(hslot(b), states[b], priors ? priors[b] : states[b], max_iter, kSlotLmBytes);
-        }
-        fill_job(hjobs[b], *s, dslot(b));
-        if (wb) hjobs[b].host_slot = reinterpret_cast<uint4*>(B.h_lm_dev + (size_t)b * stride);
-        total_n += s->n;
-    }
-    rc = ensure_replay(c, total_n);
-    if (rc) return rc;
-
-    // The batch in groups on separate streams: the latency-bound kernels of
-    // one group (18x18 solve, tie replay, launch gaps) overlap the
-    // throughput-bound k-NN / plane passes of the others.  Each group keeps
-    // its own replay list.
-    struct Group {
-        int32_t first, count;
-        int max_nblk;
-        int64_t max_n, off;
-        hipStream_t st;
-    };
-    Group g[kMaxGroups];
-    // default: four groups, one per hardware queue (round 4, 8 x 100k distinct
-    // scans, pipelined: 1 / 2 / 3 / 4 groups 18675 / 21170 / 22350 / 22984
-    // updates/s; 6 / 8 share the box's 4 queues and lose, profiles/r04_ab_groups.txt;
-    // 8 x 200k on the 10M map: 4437 vs 3960 with two): one group's
-    // latency-bound evaluations (no search: launch, reduction, solve) and its
-    // replay tail overlap the other groups' searches.  IKFoM four too (5.40k vs
-    // 5.13k with two); the iVox path two (1,520 vs 1,513 with four)
-    const int auto_groups = (fused || model == kModelIkfom) ? 4 : 2;
-    const int ngroups = std::max(1, std::min<int>(c->groups > 0 ? c->groups : auto_groups, n));
-    int64_t off = 0;
-    for (int gi = 0; gi < ngroups; gi++) {
-        g[gi].first = (int32_t)((int64_t)n * gi / ngroups);
-        g[gi].count = (int32_t)((int64_t)n * (gi + 1) / ngroups) - g[gi].first;
-        g[gi].max_nblk = 1;
-        g[gi].max_n = 1;
-        g[gi].off = off;
-        g[gi].st = B.st[gi];
-        for (int32_t b = g[gi].first; b < g[gi].first + g[gi].count; b++) {
-            const ScanBuf* s = get_scan_q(c, ids[b]);
-            g[gi].max_nblk = std::max(g[gi].max_nblk, (int)s->nblk);
-            g[gi].max_n = std::max<int64_t>(g[gi].max_n, s->n);
-            off += s->n;
-        }
-    }
-    const bool prof = sync && L == 0 && c->profiling && c->events_ready;  // 1: first-search events only
-    const bool full = prof && c->profiling >= 2;         // 2: every evaluation, the batch span and the gap
-    if (full) {
-        HIP_TRY(hipEventRecord(c->b_start, c->stream));
-        // the replay count of this batch only (every batch's replays add to it)
-        HIP_TRY(hipMemsetAsync(c->d_replay_total, 0, 8, c->stream));
-    }
-    // queued behind another lane's batch on shared streams: with LIVO_LANE_SERIAL=1
-    // start only once all of its groups are done (default: each group as soon as its
-    // own stream frees)
-    const BatchLane* prev = (!c->lane_own_streams && c->lane_serial && c->last_lane >= 0 && c->last_lane != L &&
-                             c->lane[c->last_lane].busy) ? &c->lane[c->last_lane] : nullptr;
+    RC_TRY(lane_streams(c, L));
+    RC_TRY(B.stage[model].ensure(stage_bytes(model, n)));
+    const int64_t total_n = batch_plan(c, L, n, ids, model, sync);
+    const BatchPlan& P = B.plan;
+    batch_fill(c, P, ids, states, priors, ik_states);
+    RC_TRY(ensure_replay(c, total_n));
+    RC_TRY(prof_batch_begin(c, P));
+    // queued behind another lane's batch: with LIVO_LANE_SERIAL=1 start only once
+    // all of its groups are done (default: each group as soon as its own stream frees)
+    const BatchLane* prev = (c->lane_serial && c->last_lane >= 0 && c->last_lane != L && c->lane[c->last_lane].busy)
+                                ? &c->lane[c->last_lane] : nullptr;
     c->last_lane = L;
-    // kernel copies for batches queued behind another on shared streams (a DMA
-    // copy there waits on an engine hand-off); LIVO_LANE_ZC=0: DMA copies always
-    const bool kcopy = (lm ? B.h_lm_dev != nullptr : B.h_ik_dev != nullptr) && (sync ? c->sync_zc : c->lane_zc);
-    static_assert(sizeof(HsJob) % 16 == 0 && sizeof(IekfSlot) % 16 == 0 && kLmStride % 16 == 0, "16-B word copies");
-    const char* const hsrc = lm ? (kcopy ? B.h_lm_dev : B.h_lm) : (kcopy ? B.h_ik_dev : B.h_ik);
-    const bool iv = c->backend == LIVO_BACKEND_IVOX && lm;  // (synchronous batches only: lane 0)
-    unsigned* const rcount = c->d_replay_count + (size_t)L * kMaxGroups;  // this lane's
-    unsigned long long* const rlist = c->d_replay_list + (size_t)L * c->replay_cap;
-    // Each group stages its own slots and jobs on its own stream and starts from
-    // there: no fork from stream 0, so a group waits only for its own scans'
-    // uploads and, in a pipelined farm, for its own stream's previous batch (a
-    // queued batch's group g no longer waits for the previous batch's group 0).
-    for (int gi = 0; gi < ngroups; gi++) {
-        const hipStream_t st = g[gi].st;
-        for (int32_t b = g[gi].first; b < g[gi].first + g[gi].count; b++) {
-            ScanBuf* s = get_scan_q(c, ids[b]);
-            // a scan whose asynchronous upload may still run: the group waits on the device
-            if (s->pending) HIP_TRY(hipStreamWaitEvent(st, s->ready, 0));
-            // IKFoM: its searches rewrite the neighbours without refitting the cached planes
-            if (model == kModelIkfom && s->n > 0) HIP_TRY(hipMemsetAsync(s->pstate, 0, (size_t)s->n, st));
-            // the unfused passes may read cached neighbours' coordinates (seeded rematch, IKFoM,
-            // an iVox query with no candidate keeps its record)
-            if (!fused) {
-                rc = ensure_nn_coords(c, s, st);
-                if (rc) return rc;
-            }
-        }
-        if (prev)
-            for (int q = 0; q < prev->ngroups; q++) HIP_TRY(hipStreamWaitEvent(st, prev->done[q], 0));
-        const size_t s0 = (size_t)g[gi].first * stride, sb = (size_t)g[gi].count * stride;
-        const size_t j0 = (size_t)n * stride + (size_t)g[gi].first * sizeof(HsJob), jb = (size_t)g[gi].count * sizeof(HsJob);
-        if (kcopy) {
-            rc = launch_copy_ranges(hsrc, dbase, s0, sb, j0, jb, st);
-            if (rc) return rc;
-        } else {
-            HIP_TRY(hipMemcpyAsync(dbase + s0, hsrc + s0, sb, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(dbase + j0, hsrc + j0, jb, hipMemcpyHostToDevice, st));
-        }
-        if (!fused) HIP_TRY(hipMemsetAsync(rcount + gi, 0, sizeof(unsigned), st));
-        if (iv) HIP_TRY(hipMemsetAsync(c->d_replay_count2 + gi, 0, sizeof(unsigned), st));
-        // profiling: each group's first search starts at ev[gi][0]
-        if (prof) HIP_TRY(hipEventRecord(c->ev[gi][0], st));
-    }
-    const int evals = max_iter + 1;
-    HsParams hp[kMaxGroups];
+    for (int gi = 0; gi < P.ngroups; gi++) RC_TRY(stage_group(c, L, P, gi, ids, prev));
     KnnParams kp[kMaxGroups];
-    // (rec_compact: the ikd-Tree backend's run searches on a static map, the only writer of hot-only records)
-    if (fused && make_knn_params(c).rec_compact)
-        for (int32_t b = 0; b < n; b++) get_scan_q(c, ids[b])->nn_compact = true;
-    for (int gi = 0; gi < ngroups; gi++) {
-        hp[gi] = make_hs_params(c);
-        hp[gi].jobs = djobs + g[gi].first;
-        kp[gi] = make_knn_params(c);
-        kp[gi].jobs = djobs + g[gi].first;
-        kp[gi].replay_count = rcount + gi;
-        kp[gi].replay_list = rlist + g[gi].off;
-        kp[gi].replay_count2 = iv ? c->d_replay_count2 + gi : nullptr;
-        kp[gi].replay_list2 = iv ? c->d_replay_list2 + g[gi].off : nullptr;
-        // the iVox overflow pass of each group has its own scratch slices (groups run concurrently)
-        if (kp[gi].iv.scratch) kp[gi].iv.scratch += (int64_t)gi * c->iv.big_threads * c->iv.big_slice;
-        hp[gi].solve = lm ? 1 : 0;  // the last plane-pass block of each scan runs its solve (IKFoM: k_solve_ik below)
-        hp[gi].replay_count = rcount + gi;
-        hp[gi].replay_count2 = kp[gi].replay_count2;
-    }
-    // one launch per evaluation (a launch whose scans all stopped exits at once)
-    for (int e = 0; e < evals; e++) {
-        for (int gi = 0; gi < ngroups && fused; gi++) {
-            hipStream_t st = g[gi].st;
-            // full: ev[gi][e] before evaluation e, ev[gi][evals] after the last
-            if (full && e > 0) HIP_TRY(hipEventRecord(c->ev[gi][e], st));
-            rc = launch_iekf_eval(kp[gi], hp[gi], g[gi].count, g[gi].max_n, e == 0, st);
-            if (rc) return rc;
-            if (prof && !full && e == 0) HIP_TRY(hipEventRecord(c->ev[gi][1], st));
-        }
-        for (int gi = 0; gi < ngroups && !fused; gi++) {
-            hipStream_t st = g[gi].st;
-            if (full && e > 0) HIP_TRY(hipEventRecord(c->ev[gi][3 * e], st));
-            // leaf-map search; rematch passes are bounded by the previous neighbours
-            // (the group's replay count was zeroed before the batch / by the last k_solve)
-            rc = backend_knn(c, kp[gi], g[gi].count, g[gi].max_n, e > 0, st);
-            if (rc) return rc;
-            if ((prof && e == 0) || full) HIP_TRY(hipEventRecord(c->ev[gi][3 * e + 1], st));
-            rc = model == kModelIkfom ? launch_hshare_ik(hp[gi], g[gi].count, g[gi].max_nblk, e == 0, st)
-                                      : launch_hshare(hp[gi], g[gi].count, g[gi].max_nblk, e == 0, st);
-            if (rc) return rc;
-            if (!lm) {
-                // IKFoM: the reduction, the measurement-free part of the update and
-                // the gain (k_solve_ik)
-                rc = launch_solve_ik(hp[gi], g[gi].count, st);
-                if (rc) return rc;
-            }
-        }
-    }
-    for (int gi = 0; gi < ngroups; gi++)
-        if (full) HIP_TRY(hipEventRecord(c->ev[gi][fused ? evals : 3 * LIVO_MAX_EVALS], g[gi].st));
-    // each group copies its own slots back on its own stream (no cross-stream
-    // join before the copy); the host then waits for every group's stream
-    for (int gi = 0; gi < ngroups; gi++) {
-        if (wb) {
-            // (written by the stopping solves)
-        } else if (kcopy) {
-            rc = launch_copy_words(dslot(g[gi].first), (lm ? B.h_lm_dev : B.h_ik_dev) + (size_t)g[gi].first * stride,
-                                   stride * g[gi].count, g[gi].st);
-            if (rc) return rc;
-        } else {
-            HIP_TRY(hipMemcpyAsync(&hslot(g[gi].first), dslot(g[gi].first), stride * g[gi].count,
-                                   hipMemcpyDeviceToHost, g[gi].st));
-        }
-        // this batch's end on the group's stream (another lane's batch may queue behind it)
-        HIP_TRY(hipEventRecord(B.done[gi], g[gi].st));
-    }
-    if (full) {
-        // the replay counter: every group's searches have run (joined into the main stream)
-        for (int gi = 1; gi < ngroups; gi++) {
-            HIP_TRY(hipEventRecord(c->xjoin[gi - 1], g[gi].st));
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->xjoin[gi - 1], 0));
-        }
-        HIP_TRY(hipMemcpyAsync(&c->last_replays, c->d_replay_total, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_replay_total, 0, 8, c->stream));
-        HIP_TRY(hipEventRecord(c->b_end[c->b_par], c->stream));
-    }
+    HsParams hp[kMaxGroups];
+    for (int gi = 0; gi < P.ngroups; gi++) group_params(c, L, P, gi, kp[gi], hp[gi]);
+    RC_TRY(P.fused ? queue_fused(c, P, ids, kp, hp) : queue_unfused(c, P, kp, hp));
+    for (int gi = 0; gi < P.ngroups; gi++) RC_TRY(finish_group(c, B, P, gi));
+    RC_TRY(prof_batch_end(c, P));
     B.busy = true;
     B.n = n;
-    B.model = model;
-    B.ngroups = ngroups;
     B.ids.assign(ids, ids + n);
-    for (int gi = 0; gi < ngroups; gi++) {
-        B.gfirst[gi] = g[gi].first;
-        B.gcount[gi] = g[gi].count;
-    }
     return LIVO_OK;
 }
 
+// The timings of a profiled batch from its events and slots (livo_last_timings).
+static void batch_timings(livo_ctx* c, const BatchPlan& P, const int32_t* ids, unsigned long long replays) {
+    const int32_t n = P.n;
+    const int ngroups = P.ngroups, evals = c->params.max_iterations + 1;
+    const bool full = P.prof >= 2;
+    livo_timings t{};
+    // first search of the whole batch: wall time from the earliest group's
+    // start to the latest group's end (the groups start on their own streams)
+    double lead = 0.0;  // how long before group 0 the earliest group started
+    for (int gi = 0; gi < ngroups; gi++) {
+        float ms = 0.f, m0 = 0.f;
+        (void)hipEventElapsedTime(&ms, c->ev[0][0], c->ev[gi][1]);
+        (void)hipEventElapsedTime(&m0, c->ev[0][0], c->ev[gi][0]);
+        t.knn_ms = std::max(t.knn_ms, (double)ms);
+        lead = std::max(lead, -(double)m0);
+    }
+    t.knn_ms += lead;
+    t.knn_launches = 1;
+    if (full && P.fused) {
+        // every evaluation launch: max over the concurrent groups
+        t.n_evals = std::min(evals, LIVO_MAX_EVALS);
+        for (int e = 0; e < t.n_evals; e++) {
+            // the evaluation's window over the concurrent groups (e = 0: the same
+            // window as knn_ms above, from the earliest group's start)
+            double m = 0.0;
+            for (int gi = 0; gi < ngroups; gi++) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, e == 0 ? c->ev[0][0] : c->ev[gi][e], c->ev[gi][e + 1]);
+                m = std::max(m, (double)ms);
+            }
+            if (e == 0) m = t.knn_ms;
+            t.eval_ms[e] = m;
+            int searched = 0;
+            for (int32_t b = 0; b < n; b++) searched += hslot(P, b).eval_search[e] != 0;
+            t.eval_searched[e] = searched;
+            if (e == 0) t.knn_ms = m;
+            else if (searched) t.rematch_knn_ms += m;
+            else t.plane_ms += m;
+        }
+    }
+    if (full) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->b_start, c->b_end[c->b_par]);
+        t.batch_ms = ms;
+        if (c->b_prev) {
+            (void)hipEventElapsedTime(&ms, c->b_end[c->b_par ^ 1], c->b_start);
+            t.gap_ms = ms;
+        }
+        c->b_prev = true;
+        c->b_par ^= 1;
+    }
+    for (int gi = 0; gi < ngroups && full && !P.fused; gi++)
+        for (int e = 0; e < evals; e++) {
+            float ms_k = 0.f, ms_h = 0.f;
+            if (e > 0) (void)hipEventElapsedTime(&ms_k, c->ev[gi][3 * e], c->ev[gi][3 * e + 1]);
+            const hipEvent_t end = (e + 1 < evals) ? c->ev[gi][3 * e + 3] : c->ev[gi][3 * LIVO_MAX_EVALS];
+            (void)hipEventElapsedTime(&ms_h, c->ev[gi][3 * e + 1], end);
+            t.rematch_knn_ms += ms_k;
+            t.plane_ms += ms_h;  // plane pass + the solve run by its last block
+        }
+    // the first evaluation searches for every point of every scan
+    for (int32_t b = 0; b < n; b++) {
+        t.knn_visits += (int64_t)hslot(P, b).visits[0];
+        t.knn_points += (int64_t)hslot(P, b).scanned[0];
+        t.knn_queries += c->scans[ids[b]].n;
+        t.effct_points += P.model == kModelIkfom ? hslot(P, b).ik.stats.effct_feat_num[0]
+                                                 : hslot(P, b).stats.effct_feat_num[0];
+    }
+    t.knn_replays = (int64_t)replays;
+    c->last = t;
+}
+
 static int batch_collect(livo_ctx* c, int L, livo_state* states, livo_iter_stats* stats,
-                         livo_ikfom_state* ik_states, livo_ikfom_stats* ik_stats, bool sync) {
+                         livo_ikfom_state* ik_states, livo_ikfom_stats* ik_stats) {
     BatchLane& B = c->lane[L];
-    const int32_t n = B.n;
-    if (n == 0) return LIVO_OK;
+    if (B.n == 0) return LIVO_OK;
     if (!B.busy) return LIVO_E_INVALID;
-    const std::vector<int32_t> idv = std::move(B.ids);
+    const BatchPlan& P = B.plan;
+    const std::vector<int32_t> ids = std::move(B.ids);
     B.ids.clear();
-    const int32_t* ids = idv.data();
-    const int model = B.model;
-    const int ngroups = B.ngroups;
-    const bool lm = model != kModelIkfom;
-    const size_t stride = lm ? kLmStride : sizeof(IekfSlot);
-    char* const hbase = lm ? B.h_lm : B.h_ik;
-    auto hslot = [&](int32_t b) -> IekfSlot& { return *reinterpret_cast<IekfSlot*>(hbase + (size_t)b * stride); };
-    const bool fused = c->fused && model == kModelLaserMapping && c->backend == LIVO_BACKEND_IKDTREE &&
-                       c->knn_kind == 2;
-    const int evals = c->params.max_iterations + 1;
-    const bool prof = sync && L == 0 && c->profiling && c->events_ready;
-    const bool full = prof && c->profiling >= 2;
-    struct { hipStream_t st; } g[kMaxGroups];
-    for (int gi = 0; gi < ngroups; gi++) g[gi].st = B.st[gi];
     B.busy = false;  // collected (or failed): the lane is free either way
     B.n = 0;
     // wait by polling: the batch is short, and a blocking wait's wake-up
     // latency was a visible part of the gap between two batches
-    for (int gi = ngroups - 1; gi >= 0; gi--) HIP_TRY(event_wait(B.done[gi]));
-    if (full) HIP_TRY(stream_wait(c->stream));  // the replay counter's read-back and the batch-end event
-    const unsigned long long replays = c->last_replays;
-    for (int32_t b = 0; b < n; b++) {
-        const IekfSlot& s = hslot(b);
-        if (model == kModelIkfom) {
+    for (int gi = P.ngroups - 1; gi >= 0; gi--) HIP_TRY(event_wait(B.done[gi]));
+    if (P.prof >= 2) HIP_TRY(stream_wait(c->stream));  // the replay counter's read-back and the batch-end event
+    for (int32_t b = 0; b < P.n; b++) {
+        const IekfSlot& s = hslot(P, b);
+        if (P.model == kModelIkfom) {
             ik_states[b] = s.ik.x;
             if (ik_stats) ik_stats[b] = s.ik.stats;
         } else {
@@ -3578,92 +3633,30 @@ static int batch_collect(livo_ctx* c, int L, livo_state* states, livo_iter_stats
         }
         c->scans[ids[b]].searched = true;
     }
-    if (prof) {
-        livo_timings t{};
-        // first search of the whole batch: wall time from the earliest group's
-        // start to the latest group's end (the groups start on their own streams)
-        double lead = 0.0;  // how long before group 0 the earliest group started
-        for (int gi = 0; gi < ngroups; gi++) {
-            float ms = 0.f, m0 = 0.f;
-            (void)hipEventElapsedTime(&ms, c->ev[0][0], c->ev[gi][1]);
-            (void)hipEventElapsedTime(&m0, c->ev[0][0], c->ev[gi][0]);
-            t.knn_ms = std::max(t.knn_ms, (double)ms);
-            lead = std::max(lead, -(double)m0);
-        }
-        t.knn_ms += lead;
-        t.knn_launches = 1;
-        if (full && fused) {
-            // every evaluation launch: max over the concurrent groups
-            t.n_evals = std::min(evals, LIVO_MAX_EVALS);
-            for (int e = 0; e < t.n_evals; e++) {
-                // the evaluation's window over the concurrent groups (e = 0: the same
-                // window as knn_ms above, from the earliest group's start)
-                double m = 0.0;
-                for (int gi = 0; gi < ngroups; gi++) {
-                    float ms = 0.f;
-                    (void)hipEventElapsedTime(&ms, e == 0 ? c->ev[0][0] : c->ev[gi][e], c->ev[gi][e + 1]);
-                    m = std::max(m, (double)ms);
-                }
-                if (e == 0) m = t.knn_ms;
-                t.eval_ms[e] = m;
-                int searched = 0;
-                for (int32_t b = 0; b < n; b++) searched += hslot(b).eval_search[e] != 0;
-                t.eval_searched[e] = searched;
-                if (e == 0) t.knn_ms = m;
-                else if (searched) t.rematch_knn_ms += m;
-                else t.plane_ms += m;
-            }
-        }
-        if (full) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, c->b_start, c->b_end[c->b_par]);
-            t.batch_ms = ms;
-            if (c->b_prev) {
-                (void)hipEventElapsedTime(&ms, c->b_end[c->b_par ^ 1], c->b_start);
-                t.gap_ms = ms;
-            }
-            c->b_prev = true;
-            c->b_par ^= 1;
-        }
-        for (int gi = 0; gi < ngroups && full && !fused; gi++)
-            for (int e = 0; e < evals; e++) {
-                float ms_k = 0.f, ms_h = 0.f;
-                if (e > 0) (void)hipEventElapsedTime(&ms_k, c->ev[gi][3 * e], c->ev[gi][3 * e + 1]);
-                const hipEvent_t end = (e + 1 < evals) ? c->ev[gi][3 * e + 3] : c->ev[gi][3 * LIVO_MAX_EVALS];
-                (void)hipEventElapsedTime(&ms_h, c->ev[gi][3 * e + 1], end);
-                t.rematch_knn_ms += ms_k;
-                t.plane_ms += ms_h;  // plane pass + the solve run by its last block
-            }
-        // the first evaluation searches for every point of every scan
-        for (int32_t b = 0; b < n; b++) {
-            t.knn_visits += (int64_t)hslot(b).visits[0];
-            t.knn_points += (int64_t)hslot(b).scanned[0];
-            t.knn_queries += c->scans[ids[b]].n;
-            t.effct_points += model == kModelIkfom ? hslot(b).ik.stats.effct_feat_num[0]
-                                                   : hslot(b).stats.effct_feat_num[0];
-        }
-        t.knn_replays = (int64_t)replays;
-        c->last = t;
-    }
+    if (P.prof) batch_timings(c, P, ids.data(), c->last_replays);
     return LIVO_OK;
+}
+
+// An enqueue that failed half-way: let the lane's queued work finish and free the lane.
+static void lane_abort(BatchLane& B) {
+    for (int k = 0; k < kMaxGroups && B.st[k]; k++) (void)hipStreamSynchronize(B.st[k]);
+    B.busy = false;
+    B.n = 0;
+    B.ids.clear();
+    B.ticket = -1;
 }
 
 static int batch_update(livo_ctx* c, int32_t n, const int32_t* ids, int model, livo_state* states,
                         const livo_state* priors, livo_iter_stats* stats, livo_ikfom_state* ik_states,
                         livo_ikfom_stats* ik_stats) {
     if (c && any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
-    int rc = batch_enqueue(c, 0, n, ids, model, states, priors, ik_states, true);
+    const int rc = batch_enqueue(c, 0, n, ids, model, states, priors, ik_states, true);
     if (rc) {
-        if (c) {  // an enqueue that failed half-way: let the lane's queued work finish
-            for (int k = 0; k < kMaxGroups && c->lane[0].st[k]; k++) (void)hipStreamSynchronize(c->lane[0].st[k]);
-            c->lane[0].busy = false;
-            c->lane[0].ids.clear();
-        }
+        if (c) lane_abort(c->lane[0]);
         return rc;
     }
-    return batch_collect(c, 0, states, stats, ik_states, ik_stats, true);
+    return batch_collect(c, 0, states, stats, ik_states, ik_stats);
 }
-
 
 int livo_iekf_update_batch(livo_ctx* c, int32_t n, const int32_t* ids, livo_state* states, const livo_state* priors,
                            livo_iter_stats* stats) {
@@ -3677,13 +3670,9 @@ static int batch_submit(livo_ctx* c, int32_t n, const int32_t* ids, int model, c
     for (int l = 0; l < LIVO_MAX_INFLIGHT && L < 0; l++)
         if (!c->lane[l].busy) L = l;
     if (L < 0) return LIVO_E_BUSY;
-    int rc = batch_enqueue(c, L, n, ids, model, states, priors, ik_states, false);
+    const int rc = batch_enqueue(c, L, n, ids, model, states, priors, ik_states, false);
     if (rc) {
-        BatchLane& B = c->lane[L];
-        for (int k = 0; k < kMaxGroups && B.st[k]; k++) (void)hipStreamSynchronize(B.st[k]);
-        B.busy = false;
-        B.n = 0;
-        B.ids.clear();
+        lane_abort(c->lane[L]);
         return rc;
     }
     c->lane[L].busy = true;  // (an empty batch too: its ticket is waited for like any other)
@@ -3704,14 +3693,14 @@ static int batch_wait(livo_ctx* c, int32_t ticket, int model, livo_state* states
     const int L = ticket % LIVO_MAX_INFLIGHT;
     BatchLane& B = c->lane[L];
     if (!B.busy || B.ticket != ticket) return LIVO_E_INVALID;
-    if (B.n > 0 && (B.model != model || (model == kModelIkfom ? !ik_states : !states))) return LIVO_E_INVALID;
+    if (B.n > 0 && (B.plan.model != model || (model == kModelIkfom ? !ik_states : !states))) return LIVO_E_INVALID;
     if (set_device(c)) return LIVO_E_HIP;
     B.ticket = -1;
     if (B.n == 0) {
         B.busy = false;
         return LIVO_OK;
     }
-    return batch_collect(c, L, states, stats, ik_states, ik_stats, false);
+    return batch_collect(c, L, states, stats, ik_states, ik_stats);
 }
 
 int livo_iekf_update_batch_wait(livo_ctx* c, int32_t ticket, livo_state* states, livo_iter_stats* stats) {
@@ -3825,7 +3814,7 @@ int livo_ivox_knn(livo_ctx* c, const float* q, int64_t n, int32_t max_num, doubl
     if (n == 0) return LIVO_OK;
     if (n > (int64_t)0x7FFFFFFF - kBlock) return LIVO_E_RANGE;
     if (set_device(c)) return LIVO_E_HIP;
-    int rc = ensure_slots(c, 1);
+    int rc = ensure_slot(c);
     if (rc) return rc;
     const size_t qb = (size_t)n * 4 * sizeof(float), rb = (size_t)n * sizeof(NNRec);
     rc = ensure_scratch(c, qb + rb + 256);
@@ -3930,7 +3919,7 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
     const int64_t N = s->n;
     if (counts) counts[0] = counts[1] = 0;
     if (N == 0) return LIVO_OK;
-    int rc = ensure_slots(c, 1);
+    int rc = ensure_slot(c);
     if (rc) return rc;
     // scratch: ordered 2N x 16 B, flags 2N x 4, pos 2N x 4, cat N
     const size_t ob = (size_t)N * 32, fb = (size_t)N * 8, cb = (size_t)N;
