@@ -31,6 +31,7 @@ SOURCES = [
     ("ivox_kernels.hip", True),
     ("frontend_kernels.hip", True),
     ("vio_kernels.hip", True),
+    ("rgb_kernels.hip", True),
     ("ikd_incr_kernels.hip", True),
     ("prims.hip", True),
     ("livo_capi.cpp", False),

@@ -1,0 +1,129 @@
+// cam_model.h — the camera arithmetic shared by the VIO update (vio_kernels.hip)
+// and the cloud colouring (rgb_kernels.hip): the frame pose from a state, vikit's
+// pinhole world2cam, and one point's colour as publish_frame_world_rgb computes
+// it.  Everything compiles for host and device (SEL_HD, as ball_cells in
+// livo_internal.h), so tests/native/rgb_point_check.cpp runs the same code on
+// the CPU.  Numerics as the kernels: -ffp-contract=off, the reference's float /
+// double expression order.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "stl_select.h"  // SEL_HD
+
+namespace livo {
+
+// new_frame_->T_f_w_ from the state (lidar_selection.cpp:900-901):
+// Rcw = Rci * Rwi^T, Pcw = -Rci * Rwi^T * Pwi + Pci.  Row-major.
+SEL_HD void cam_pose(const double* Rci, const double* Pci, const double* Rwi, const double* Pwi, double* Rcw,
+                     double* Pcw) {
+    double RwiT[9];
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) RwiT[a * 3 + b] = Rwi[b * 3 + a];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            Rcw[i * 3 + j] = (Rci[i * 3 + 0] * RwiT[0 * 3 + j] + Rci[i * 3 + 1] * RwiT[1 * 3 + j]) +
+                             Rci[i * 3 + 2] * RwiT[2 * 3 + j];
+    for (int k = 0; k < 3; k++)
+        Pcw[k] = -((Rcw[k * 3 + 0] * Pwi[0] + Rcw[k * 3 + 1] * Pwi[1]) + Rcw[k * 3 + 2] * Pwi[2]) + Pci[k];
+}
+
+// Frame::w2f: pf = Rcw * p_w + Pcw, row sums left to right.
+SEL_HD void cam_w2f(const double* Rcw, const double* Pcw, const double* pw, double* pf) {
+    for (int k = 0; k < 3; k++)
+        pf[k] = ((Rcw[k * 3 + 0] * pw[0] + Rcw[k * 3 + 1] * pw[1]) + Rcw[k * 3 + 2] * pw[2]) + Pcw[k];
+}
+
+// vikit PinholeCamera::world2cam(xyz_c), the distortion branch included.  Cam:
+// anything with fx, fy, cx, cy, d[5] and distortion (VioParams, RgbCam).
+template <class Cam>
+SEL_HD void vio_world2cam(const Cam& P, const double* xyz, double* px) {
+    const double u = xyz[0] / xyz[2], v = xyz[1] / xyz[2];  // project2d
+    if (!P.distortion) {
+        px[0] = P.fx * u + P.cx;
+        px[1] = P.fy * v + P.cy;
+        return;
+    }
+    const double x = u, y = v;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
+    const double cdist = 1 + P.d[0] * r2 + P.d[1] * r4 + P.d[4] * r6;
+    const double xd = x * cdist + P.d[2] * a1 + P.d[3] * a2;
+    const double yd = y * cdist + P.d[2] * a3 + P.d[3] * a1;
+    px[0] = xd * P.fx + P.cx;
+    px[1] = yd * P.fy + P.cy;
+}
+
+// The camera of one livo_cloud_colorize call.
+struct RgbCam {
+    double Rcw[9], Pcw[3];
+    double fx, fy, cx, cy, d[5];
+    int32_t distortion;  // vikit distortion_ = |d0| > 1e-7
+    int32_t w, h;
+};
+
+enum RgbFate : int { kRgbKept = 0, kRgbBehind = 1, kRgbOutOfFrame = 2 };
+
+// Six image bytes from flat offset o (two neighbouring BGR pixels).  Inside the
+// buffer they are fetched as one 4-byte and one 2-byte read; a byte outside
+// [0, nbytes) reads as 0 and sets edge.
+SEL_HD void rgb_span(const uint8_t* img, int64_t nbytes, int64_t o, float* I, bool& edge) {
+    if (o >= 0 && o + 6 <= nbytes) {
+        uint32_t a;
+        uint16_t b;
+        memcpy(&a, img + o, 4);
+        memcpy(&b, img + o + 4, 2);
+        I[0] = (float)(a & 255u);
+        I[1] = (float)((a >> 8) & 255u);
+        I[2] = (float)((a >> 16) & 255u);
+        I[3] = (float)(a >> 24);
+        I[4] = (float)(b & 255u);
+        I[5] = (float)(b >> 8);
+        return;
+    }
+    for (int k = 0; k < 6; k++) {
+        const bool in = o + k >= 0 && o + k < nbytes;
+        I[k] = in ? (float)img[o + k] : 0.0f;
+        edge = edge || !in;
+    }
+}
+
+// One point of publish_frame_world_rgb (laser_mapping.cpp:1361-1381) from its
+// world coordinates as the published cloud holds them (floats): w2f, the
+// p_cam.z > 0 test (a NaN fails it), w2c, isInFrame(pc.cast<int>(), 0) taken in
+// double (the same answers wherever the cast is defined), then
+// LidarSelector::getpixel (lidar_selection.cpp:1004-1022) on the 8-bit BGR
+// image as a flat byte array of 3 * w * h bytes: the row wraps of u in (-1, 0)
+// and [w - 1, w) read the neighbouring row as the reference does; taps outside
+// the buffer (undefined there) read 0 and set edge.  rgba: r | g << 8 | b << 16
+// | 255 << 24, the channels truncated as pointRGB.r = pixel[2] does.
+SEL_HD int rgb_point(const RgbCam& C, const uint8_t* img, float wx, float wy, float wz, uint32_t& rgba, bool& edge) {
+    rgba = 0u;
+    edge = false;
+    const double pw[3] = {(double)wx, (double)wy, (double)wz};  // V3D p_w(p.x, p.y, p.z)
+    double pf[3], pc[2];
+    cam_w2f(C.Rcw, C.Pcw, pw, pf);
+    if (!(pf[2] > 0)) return kRgbBehind;
+    vio_world2cam(C, pf, pc);
+    if (!(pc[0] > -1.0 && pc[0] < (double)C.w && pc[1] > -1.0 && pc[1] < (double)C.h)) return kRgbOutOfFrame;
+    const float u_ref = (float)pc[0], v_ref = (float)pc[1];
+    const int u_ref_i = (int)floorf(u_ref), v_ref_i = (int)floorf(v_ref);
+    const float su = u_ref - (float)u_ref_i, sv = v_ref - (float)v_ref_i;
+    const float w_tl = (float)((1.0 - su) * (1.0 - sv)), w_tr = (float)(su * (1.0 - sv)),
+                w_bl = (float)((1.0 - su) * sv), w_br = su * sv;
+    const int64_t row = 3 * (int64_t)C.w, nbytes = row * C.h;
+    const int64_t o = ((int64_t)v_ref_i * C.w + u_ref_i) * 3;
+    float T[6], B[6];  // the taps of the upper and the lower row: (tl, tr) and (bl, br), B G R each
+    rgb_span(img, nbytes, o, T, edge);
+    rgb_span(img, nbytes, o + row, B, edge);
+    uint32_t ch[3];
+    for (int c = 0; c < 3; c++) {
+        const float v = ((w_tl * T[c] + w_tr * T[c + 3]) + w_bl * B[c]) + w_br * B[c + 3];
+        ch[c] = (uint32_t)(int)v & 255u;
+    }
+    rgba = ch[2] | (ch[1] << 8) | (ch[0] << 16) | (255u << 24);
+    return kRgbKept;
+}
+
+}  // namespace livo

@@ -303,6 +303,9 @@ struct livo_ctx {
     int64_t fe_n = 0;
     void* vio_buf = nullptr;           // VIO frame (image, points, partials, slot)
     size_t vio_bytes = 0;
+    uint8_t* rgb_img = nullptr;        // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
+    size_t rgb_cap = 0;
+    int32_t rgb_w = 0, rgb_h = 0;      // its size (0: none)
     void* prim_tmp = nullptr;          // rocPRIM scratch (sorts, scans)
     size_t prim_bytes = 0;
     // scans
@@ -1911,6 +1914,7 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->fe_buf) (void)hipFree(c->fe_buf);
     if (c->prim_tmp) (void)hipFree(c->prim_tmp);
     if (c->vio_buf) (void)hipFree(c->vio_buf);
+    dev_free(c->rgb_img);
     dev_free(c->nodes);
     dev_free(c->lnodes);
     dev_free(c->lpts);
@@ -4418,6 +4422,104 @@ int livo_frame_to_world(livo_ctx* c, int32_t scan_id, const livo_state* state, l
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return LIVO_OK;
+}
+
+int livo_cloud_colorize(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                        const uint8_t* bgr, int32_t width, int32_t height, livo_rgb_point* out, int32_t* src_index,
+                        int64_t cap, int64_t* n_out, livo_rgb_stats* stats) {
+    if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
+    if (width <= 0 || height <= 0 || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
+    if (!bgr && (!c->rgb_img || c->rgb_w != width || c->rgb_h != height)) return LIVO_E_INVALID;
+    // the source cloud, as livo_frame_to_world selects it
+    RgbParams R{};
+    int64_t n;
+    if (scan_id < 0) {
+        R.src = c->fe_raw;
+        n = c->fe_raw ? c->fe_n : 0;
+        R.stride = 5;
+    } else {
+        ScanBuf* s = get_scan(c, scan_id);
+        if (!s) return LIVO_E_NOSCAN;
+        R.src = s->pts;
+        n = s->n;
+        R.stride = 4;
+        R.iperm = s->d_iperm;  // the caller's point order
+    }
+    if (n > (int64_t)0x7FFFFFFF - kRgbBlock) return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    const size_t img_bytes = (size_t)3 * (size_t)width * (size_t)height;
+    if (bgr) {
+        c->rgb_w = c->rgb_h = 0;  // (no image to reuse if the upload fails)
+        if (img_bytes > c->rgb_cap) {
+            dev_free(c->rgb_img);
+            c->rgb_cap = 0;
+            if (dev_alloc(&c->rgb_img, img_bytes)) return LIVO_E_OOM;
+            c->rgb_cap = img_bytes;
+        }
+        HIP_TRY(hipMemcpyAsync(c->rgb_img, bgr, img_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    unsigned long long ctr[kRgbCtrN] = {0, 0, 0, 0};
+    if (n > 0) {
+        const bool compact = out || src_index;
+        const int64_t nblk = (n + kRgbBlock - 1) / kRgbBlock;
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t b_rec = al((size_t)n * sizeof(livo_rgb_point)), b_idx = al((size_t)n * 4), b_keep = al((size_t)n),
+                     b_blk = al((size_t)nblk * 4), b_ctr = al(sizeof(ctr));
+        RC_TRY(ensure_scratch(c, 2 * b_rec + b_idx + b_keep + 2 * b_blk + b_ctr));
+        char* q = (char*)c->scratch;
+        R.rec = (livo_rgb_point*)q; q += b_rec;
+        livo_rgb_point* d_out = (livo_rgb_point*)q; q += b_rec;
+        int32_t* d_idx = (int32_t*)q; q += b_idx;
+        R.keep = (uint8_t*)q; q += b_keep;
+        R.blk_cnt = (uint32_t*)q; q += b_blk;
+        uint32_t* d_off = (uint32_t*)q; q += b_blk;
+        R.blk_off = d_off;
+        R.ctr = (unsigned long long*)q;
+        R.n = (int32_t)n;
+        std::memcpy(R.W.rot, state->rot, sizeof(R.W.rot));
+        std::memcpy(R.W.pos, state->pos, sizeof(R.W.pos));
+        std::memcpy(R.W.R_LI, c->params.R_LI, sizeof(R.W.R_LI));
+        std::memcpy(R.W.t_LI, c->params.t_LI, sizeof(R.W.t_LI));
+        cam_pose(p->R_ci, p->P_ci, state->rot, state->pos, R.cam.Rcw, R.cam.Pcw);  // once per call
+        R.cam.fx = p->cam.fx; R.cam.fy = p->cam.fy; R.cam.cx = p->cam.cx; R.cam.cy = p->cam.cy;
+        std::memcpy(R.cam.d, p->cam.d, sizeof(R.cam.d));
+        R.cam.distortion = std::fabs(p->cam.d[0]) > 0.0000001 ? 1 : 0;  // vikit: distortion_ = |d0| > 1e-7
+        R.cam.w = width;
+        R.cam.h = height;
+        R.img = c->rgb_img;
+        R.out = out ? d_out : nullptr;
+        R.src_index = src_index ? d_idx : nullptr;
+        HIP_TRY(hipMemsetAsync(R.ctr, 0, sizeof(ctr), c->stream));
+        RC_TRY(launch_rgb_points(R, c->stream));
+        if (compact) {
+            RC_TRY(ivox_scan(c, R.blk_cnt, d_off, nblk));
+            RC_TRY(launch_rgb_scatter(R, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (bgr) {
+        c->rgb_w = width;
+        c->rgb_h = height;
+    }
+    const int64_t kept = (int64_t)ctr[kRgbCtrKept];
+    *n_out = kept;
+    if (stats) {
+        stats->n_in = n;
+        stats->n_out = kept;
+        stats->behind = (int64_t)ctr[kRgbCtrBehind];
+        stats->out_of_frame = (int64_t)ctr[kRgbCtrOutOfFrame];
+        stats->edge_reads = (int64_t)ctr[kRgbCtrEdge];
+    }
+    if ((out || src_index) && cap < kept) return LIVO_E_RANGE;
+    if (kept > 0 && (out || src_index)) {
+        if (out)
+            HIP_TRY(hipMemcpyAsync(out, R.out, (size_t)kept * sizeof(livo_rgb_point), hipMemcpyDeviceToHost, c->stream));
+        if (src_index)
+            HIP_TRY(hipMemcpyAsync(src_index, R.src_index, (size_t)kept * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     return LIVO_OK;
 }
 

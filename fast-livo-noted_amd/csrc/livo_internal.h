@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "cam_model.h"
 #include "livo.h"
 #include "stl_select.h"
 
@@ -586,6 +587,28 @@ struct WorldParams {
 // RGBpointBodyToWorld of n points (stride floats each, x y z [intensity]) -> n x 5 floats.
 int launch_to_world(const float* src, int64_t n, int stride, const int32_t* perm, const WorldParams& W, float* out5,
                     void* stream);
+// publish_frame_world_rgb (rgb_kernels.hip): the cloud of launch_to_world,
+// projected into the camera frame and coloured from the BGR image, the kept
+// points compacted in the cloud's order.
+constexpr int kRgbBlock = 256;
+enum { kRgbCtrBehind = 0, kRgbCtrOutOfFrame = 1, kRgbCtrEdge = 2, kRgbCtrKept = 3, kRgbCtrN = 4 };
+struct RgbParams {
+    const float* src;         // n points, stride floats each (x, y, z, ...), stored order
+    const int32_t* iperm;     // cloud index -> stored position (null: the same)
+    int32_t n, stride;
+    WorldParams W;
+    RgbCam cam;
+    const uint8_t* img;       // 3 * cam.w * cam.h bytes, B G R interleaved
+    livo_rgb_point* rec;      // n: every point's record, cloud order
+    uint8_t* keep;            // n: 1 kept
+    uint32_t* blk_cnt;        // per block of kRgbBlock points: kept
+    const uint32_t* blk_off;  // their exclusive scan (the scatter)
+    unsigned long long* ctr;  // kRgbCtrN counters, zeroed by the caller
+    livo_rgb_point* out;      // compacted records
+    int32_t* src_index;       // and their cloud indices
+};
+int launch_rgb_points(const RgbParams& p, void* stream);
+int launch_rgb_scatter(const RgbParams& p, void* stream);
 // laserCloudOri / corr_normvect compaction in the caller's order (stored-order sel / normvec / points).
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream);
 int launch_ori_scatter(const float* pts4, const float* normvec, const uint8_t* sel, const int32_t* perm,

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 
+#include "cam_model.h"
 #include "device_common.h"
 #include "device_linalg.h"
 #include "livo_internal.h"
@@ -41,23 +42,6 @@ __global__ void k_vio_begin(VioParams P, int level) {
         s->ctrl.level_error[2 - level] = 1e10f;  // UpdateState returns total_residual if nothing updates
         s->ticket = 0u;
     }
-}
-
-__device__ __forceinline__ void vio_world2cam(const VioParams& P, const double* xyz, double* px) {
-    const double u = xyz[0] / xyz[2], v = xyz[1] / xyz[2];  // project2d
-    if (!P.distortion) {
-        px[0] = P.fx * u + P.cx;
-        px[1] = P.fy * v + P.cy;
-        return;
-    }
-    const double x = u, y = v;
-    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-    const double cdist = 1 + P.d[0] * r2 + P.d[1] * r4 + P.d[4] * r6;
-    const double xd = x * cdist + P.d[2] * a1 + P.d[3] * a2;
-    const double yd = y * cdist + P.d[2] * a3 + P.d[3] * a1;
-    px[0] = xd * P.fx + P.cx;
-    px[1] = yd * P.fy + P.cy;
 }
 
 __device__ __forceinline__ void row3_mat(const double* r, const double* M, double* o) {
@@ -256,17 +240,9 @@ __global__ __launch_bounds__(256) void k_vio_iter(VioParams P) {
     for (int k = 0; k < 27; k++) acc[k] = 0.0;
     if (i < P.n) {
         const livo_state& st = slot->state;
-        double RwiT[9], Rcw[9], Pcw[3], pf[3], pc[2];
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++) RwiT[a * 3 + b] = st.rot[b * 3 + a];
-        mat3_mul(P.Rci, RwiT, Rcw);  // Rcw = Jdp_dt
-#pragma unroll
-        for (int k = 0; k < 3; k++) Pcw[k] = -((Rcw[k * 3 + 0] * st.pos[0] + Rcw[k * 3 + 1] * st.pos[1]) + Rcw[k * 3 + 2] * st.pos[2]) + P.Pci[k];
-        const double* pw = P.pos + 3 * (size_t)i;
-#pragma unroll
-        for (int k = 0; k < 3; k++) pf[k] = ((Rcw[k * 3 + 0] * pw[0] + Rcw[k * 3 + 1] * pw[1]) + Rcw[k * 3 + 2] * pw[2]) + Pcw[k];
+        double Rcw[9], Pcw[3], pf[3], pc[2];
+        cam_pose(P.Rci, P.Pci, st.rot, st.pos, Rcw, Pcw);  // Rcw = Jdp_dt
+        cam_w2f(Rcw, Pcw, P.pos + 3 * (size_t)i, pf);
         vio_world2cam(P, pf, pc);
         const double zi = 1. / pf[2], zi2 = zi * zi;
         const double Jdpi[6] = {P.fx * zi, 0.0, -P.fx * pf[0] * zi2, 0.0, P.fy * zi, -P.fy * pf[1] * zi2};

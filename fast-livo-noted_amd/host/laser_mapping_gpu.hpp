@@ -191,6 +191,29 @@ public:
         return st;
     }
 
+    // publish_frame_world_rgb() (laser_mapping.cpp:1351-1381) up to the publisher: the
+    // cloud of pcl_wait_pub at `state` (dense_map_en: the last set_scan_raw frame at full
+    // resolution, else the current feats_down_body) projected into the camera of
+    // `vio` (cam, R_ci, P_ci) and coloured from img_rgb (lidar_selector->img_rgb: 8-bit
+    // B, G, R, row stride 3 * width).  Fills laserCloudWorldRGB with the kept points in
+    // the cloud's order; img_rgb == nullptr reuses the image of the previous call (the
+    // frame's image colours the dense and the downsampled cloud with one upload).
+    livo_rgb_stats publish_frame_world_rgb(const livo_vio_params& vio, const uint8_t* img_rgb, int32_t width,
+                                           int32_t height, std::vector<livo_rgb_point>& laserCloudWorldRGB,
+                                           bool dense_map_en = true) {
+        if (!dense_map_en && scan_id_ < 0) throw Error("publish_frame_world_rgb", LIVO_E_NOSCAN);
+        const int32_t id = dense_map_en ? -1 : scan_id_;
+        int64_t n = 0;
+        check(livo_frame_to_world(ctx_, id, &state, nullptr, 0, &n), "livo_frame_to_world");  // the cloud's size
+        laserCloudWorldRGB.resize((size_t)n);
+        livo_rgb_stats st{};
+        check(livo_cloud_colorize(ctx_, id, &state, &vio, img_rgb, width, height, laserCloudWorldRGB.data(), nullptr,
+                                  n, &n, &st),
+              "livo_cloud_colorize");
+        laserCloudWorldRGB.resize((size_t)n);
+        return st;
+    }
+
     livo_ctx* ctx() const { return ctx_; }
     const livo_params& params() const { return params_; }
 

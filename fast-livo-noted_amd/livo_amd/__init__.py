@@ -9,6 +9,7 @@ path:
     IVox (AddPoints / GetClosestPoint)   -> Context.ivox_init / ivox_add_points / ivox_knn
     LaserMapping::map_incremental        -> Context.map_incremental
     IEKF loop of LaserMapping::Run       -> Context.iekf_update(_batch)
+    LaserMapping::publish_frame_world_rgb -> Context.colorize
 
 There is no CPU fallback: loading fails loudly if the HIP library is missing,
 and every compute call raises LivoError when the GPU path fails.
@@ -149,6 +150,33 @@ class VioStats(C.Structure):
                 ("cov_updated", C.c_int32), ("n_meas", C.c_int64), ("out_of_frame", C.c_int64)]
 
 
+class RgbPoint(C.Structure):
+    """livo_rgb_point: one point of the coloured world cloud (PointXYZRGB's x, y, z, r, g, b)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float),
+                ("r", C.c_uint8), ("g", C.c_uint8), ("b", C.c_uint8), ("a", C.c_uint8)]
+
+
+RGB_POINT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32),
+                            ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("a", np.uint8)])
+
+
+class RgbStats(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_out", C.c_int64), ("behind", C.c_int64), ("out_of_frame", C.c_int64),
+                ("edge_reads", C.c_int64)]
+
+
+def vio_params(cam: dict, Rci, Pci) -> VioParams:
+    """livo_vio_params from a camera dict (fx, fy, cx, cy, d, width, height) and the extrinsics."""
+    p = VioParams()
+    _check("livo_vio_params_default", load().livo_vio_params_default(C.byref(p)))
+    p.cam.fx, p.cam.fy, p.cam.cx, p.cam.cy = cam["fx"], cam["fy"], cam["cx"], cam["cy"]
+    p.cam.d[:] = list(cam["d"]) + [0.0] * (5 - len(cam["d"]))
+    p.cam.width, p.cam.height = cam["width"], cam["height"]
+    p.R_ci[:] = np.asarray(Rci, np.float64).reshape(9).tolist()
+    p.P_ci[:] = np.asarray(Pci, np.float64).reshape(3).tolist()
+    return p
+
+
 class MapAddStats(C.Structure):
     _fields_ = [("events", C.c_int64), ("added", C.c_int64), ("deleted", C.c_int64), ("ambiguous", C.c_int64),
                 ("deferred", C.c_int64), ("map_points", C.c_int64)]
@@ -203,6 +231,8 @@ SIGNATURES = {
     "livo_map_dump": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "livo_map_last_add_stats": (C.c_int, [_P, C.POINTER(MapAddStats)]),
     "livo_frame_to_world": (C.c_int, [_P, C.c_int32, C.POINTER(State), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "livo_cloud_colorize": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.POINTER(VioParams), _P, C.c_int32, C.c_int32,
+                                      _P, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(RgbStats)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -448,6 +478,33 @@ class Context:
         _check("livo_frame_to_world", self._L.livo_frame_to_world(self.h, sid, C.byref(st), _ptr(out), n.value,
                                                                   C.byref(n)))
         return out
+
+    def colorize(self, state: dict, image_bgr, vio_params: VioParams, scan_id: int = -1):
+        """publish_frame_world_rgb's coloured cloud (livo_cloud_colorize): the cloud of frame_to_world(state,
+        scan_id) in the camera of vio_params (cam, R_ci, P_ci) at `state`, the points in the image kept in
+        order with their bilinear colour.  image_bgr: (height, width, 3) uint8, B G R; None reuses the image
+        of the previous call.  Returns (points: RGB_POINT_DTYPE array, src_index: int32, stats: dict)."""
+        st = state_to_c(state)
+        img = None
+        if image_bgr is not None:
+            img = np.ascontiguousarray(image_bgr, np.uint8)
+            if img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError("image_bgr must be (height, width, 3)")
+            w, h = img.shape[1], img.shape[0]
+        else:
+            w, h = vio_params.cam.width, vio_params.cam.height
+        n = C.c_int64()
+        # the size of the source cloud bounds the result: one call, one upload
+        _check("livo_frame_to_world", self._L.livo_frame_to_world(self.h, scan_id, C.byref(st), None, 0, C.byref(n)))
+        cap = n.value
+        pts = np.zeros(cap, RGB_POINT_DTYPE)
+        idx = np.zeros(cap, np.int32)
+        rs = RgbStats()
+        _check("livo_cloud_colorize", self._L.livo_cloud_colorize(
+            self.h, scan_id, C.byref(st), C.byref(vio_params), _ptr(img), w, h, _ptr(pts), _ptr(idx), cap,
+            C.byref(n), C.byref(rs)))
+        stats = {f: int(getattr(rs, f)) for f, _ in RgbStats._fields_}
+        return pts[:n.value].copy(), idx[:n.value].copy(), stats
 
     def iekf_update(self, sid: int, state: dict, prior: dict | None = None):
         st = state_to_c(state)

@@ -28,6 +28,8 @@
  *   livo_scan_preprocess ← ImuProcess::UndistortPcl (per point) + downSizeFilterSurf
  *                                                   src/IMU_Processing.cpp:340-378,
  *                                                   src/laser_mapping.cpp:129-130
+ *   livo_cloud_colorize ← LaserMapping::publish_frame_world_rgb (the coloured cloud)
+ *                                                   src/laser_mapping.cpp:1351-1381
  *
  * Conventions
  *   - plain pointers and sizes only; no C++ or torch types cross the ABI;
@@ -52,11 +54,12 @@
 extern "C" {
 #endif
 
-/* 5: livo_ivox_info grew add_passes (round 4).
+/* 7: livo_cloud_colorize added (nothing else changed).
+ * 5: livo_ivox_info grew add_passes (round 4).
  * 4: livo_timings grew the per-evaluation fields (eval_ms ... gap_ms), LIVO_E_BUSY
  *    and the submit / wait pair were added (round 3); a binary built against 3
  *    passes a smaller livo_timings. */
-#define LIVO_ABI_VERSION 6
+#define LIVO_ABI_VERSION 7
 #define LIVO_DIM_STATE 18        /* DIM_STATE, include/common_lib.h:32 */
 #define LIVO_NUM_MATCH_POINTS 5  /* NUM_MATCH_POINTS, include/common_lib.h:37 */
 #define LIVO_MAX_EVALS 16        /* max h_share/solve evaluations per scan update */
@@ -500,6 +503,38 @@ int livo_map_last_add_stats(livo_ctx* ctx, livo_map_add_stats* out);
  * NULL to query the count, else cap >= *n (LIVO_E_RANGE otherwise). */
 int livo_frame_to_world(livo_ctx* ctx, int32_t scan_id, const livo_state* state, livo_raw_point* out, int64_t cap,
                         int64_t* n);
+/* LaserMapping::publish_frame_world_rgb (src/laser_mapping.cpp:1351-1381): the
+ * cloud of livo_frame_to_world (same scan_id, same error codes, x, y, z bit for
+ * bit) projected into the camera frame of `state` (Rcw = Rci Rwi^T, Pcw = -Rcw
+ * Pwi + Pci, lidar_selection.cpp:900-901; of p only cam, R_ci and P_ci are
+ * read), the points in front of the camera and inside the image kept in the
+ * cloud's order, each with the bilinear sample of LidarSelector::getpixel
+ * (src/lidar_selection.cpp:1004-1022).
+ * bgr: 8-bit, interleaved B, G, R, row stride 3 * width; width / height must
+ * equal p->cam.width / height (LIVO_E_INVALID).  bgr == NULL reuses the image
+ * the previous successful call on this context uploaded (LIVO_E_INVALID if
+ * there is none or its size differs).  getpixel indexes the image as a flat
+ * byte array: u in (-1, 0) or [width - 1, width) reads the neighbouring row,
+ * as the reference does; a tap outside the buffer (undefined there) reads 0
+ * and the point counts in edge_reads.
+ * *n = points kept (set on LIVO_OK and LIVO_E_RANGE).  out and src_index (the
+ * kept point's position in the source cloud) may each be NULL; if one is not
+ * and cap < *n: LIVO_E_RANGE, nothing written (cap >= n_in always suffices).
+ * stats may be NULL. */
+typedef struct livo_rgb_point {
+    float x, y, z;
+    uint8_t r, g, b, a; /* a = 255 */
+} livo_rgb_point;
+typedef struct livo_rgb_stats {
+    int64_t n_in;         /* points of the source cloud                                   */
+    int64_t n_out;        /* points kept (= *n)                                           */
+    int64_t behind;       /* dropped: p_cam.z > 0 is false                                */
+    int64_t out_of_frame; /* dropped: in front of the camera, isInFrame(.., 0) false      */
+    int64_t edge_reads;   /* kept points with at least one tap outside the image buffer   */
+} livo_rgb_stats;
+int livo_cloud_colorize(livo_ctx* ctx, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                        const uint8_t* bgr, int32_t width, int32_t height, livo_rgb_point* out, int32_t* src_index,
+                        int64_t cap, int64_t* n, livo_rgb_stats* stats);
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
