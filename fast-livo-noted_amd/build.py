@@ -32,6 +32,7 @@ SOURCES = [
     ("frontend_kernels.hip", True),
     ("vio_kernels.hip", True),
     ("rgb_kernels.hip", True),
+    ("vis_kernels.hip", True),
     ("ikd_incr_kernels.hip", True),
     ("prims.hip", True),
     ("livo_capi.cpp", False),

@@ -1,10 +1,11 @@
-// cam_model.h — the camera arithmetic shared by the VIO update (vio_kernels.hip)
-// and the cloud colouring (rgb_kernels.hip): the frame pose from a state, vikit's
-// pinhole world2cam, and one point's colour as publish_frame_world_rgb computes
-// it.  Everything compiles for host and device (SEL_HD, as ball_cells in
-// livo_internal.h), so tests/native/rgb_point_check.cpp runs the same code on
-// the CPU.  Numerics as the kernels: -ffp-contract=off, the reference's float /
-// double expression order.
+// cam_model.h — the camera arithmetic shared by the VIO update (vio_kernels.hip),
+// the cloud colouring (rgb_kernels.hip) and the visual point selection
+// (vis_kernels.hip): the frame pose from a state, vikit's pinhole world2cam, one
+// point's colour as publish_frame_world_rgb computes it, and addSparseMap's
+// score, patch and voxel key.  Everything compiles for host and device (SEL_HD,
+// as ball_cells in livo_internal.h), so tests/native/rgb_point_check.cpp and
+// vis_point_check.cpp run the same code on the CPU.  Numerics as the kernels:
+// -ffp-contract=off, the reference's float / double expression order.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -124,6 +125,121 @@ SEL_HD int rgb_point(const RgbCam& C, const uint8_t* img, float wx, float wy, fl
     }
     rgba = ch[2] | (ch[1] << 8) | (ch[0] << 16) | (255u << 24);
     return kRgbKept;
+}
+
+// Ten image bytes from flat offset o of an 8-bit gray image, fetched as the four
+// aligned 4-byte words that hold them (img 4-byte aligned, [o & ~3, (o & ~3) + 16)
+// inside the buffer).
+SEL_HD void vis_row10(const uint8_t* img, int64_t o, int* B) {
+    const int64_t a = o & ~(int64_t)3;
+    uint32_t d[4];
+    memcpy(d, __builtin_assume_aligned(img + a, 4), 16);
+    const int s = (int)(o - a) * 8;
+    uint64_t lo = (uint64_t)d[0] | ((uint64_t)d[1] << 32), hi = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
+    if (s) {
+        lo = (lo >> s) | (hi << (64 - s));
+        hi >>= s;
+    }
+    for (int k = 0; k < 8; k++) B[k] = (int)((lo >> (8 * k)) & 255u);
+    B[8] = (int)(hi & 255u);
+    B[9] = (int)((hi >> 8) & 255u);
+}
+
+// vikit's vk::shiTomasiScore(img, u, v) on an 8-bit gray image of w x h, row
+// stride w: the smaller eigenvalue of the gradient matrix over the 8 x 8 box
+// rows [v-4, v+4), columns [u-4, u+4), central differences, each sum divided by
+// 2 * 64.  0 if the box is not inside the image by one pixel.  The sums are
+// integers below 2^24 (exact in the reference's floats in any order); the rest
+// is float, one rounding per operation, with the final 0.5 * (...) in double as
+// the reference's `0.5 *` promotes it.  The discriminant cannot round below
+// zero here: s is exact (the sums stay below 2^24), s * s >= 4 dXX dYY, and
+// rounding is monotonic.
+SEL_HD float vis_score(const uint8_t* img, int w, int h, int u, int v) {
+    if (u - 4 < 1 || u + 4 >= w - 1 || v - 4 < 1 || v + 4 >= h - 1) return 0.0f;
+    int R0[10], R1[10], R2[10];  // rows y - 1, y, y + 1; columns u - 5 .. u + 4
+    const int64_t o = (int64_t)(v - 5) * w + (u - 5);
+    vis_row10(img, o, R0);
+    vis_row10(img, o + w, R1);
+    int sxx = 0, syy = 0, sxy = 0;
+    for (int r = 0; r < 8; r++) {
+        vis_row10(img, o + (int64_t)(r + 2) * w, R2);
+        for (int k = 1; k < 9; k++) {
+            const int dx = R1[k + 1] - R1[k - 1], dy = R2[k] - R0[k];
+            sxx += dx * dx;
+            syy += dy * dy;
+            sxy += dx * dy;
+        }
+        for (int k = 0; k < 10; k++) {
+            R0[k] = R1[k];
+            R1[k] = R2[k];
+        }
+    }
+    const float dXX = (float)sxx / 128.0f, dYY = (float)syy / 128.0f, dXY = (float)sxy / 128.0f;
+    const float s = dXX + dYY;
+    const float t = s * s - 4.0f * (dXX * dYY - dXY * dXY);
+    const float r = sqrtf(t);
+    return (float)(0.5 * (double)(s - r));
+}
+
+// One value of LidarSelector::getpatch (lidar_selection.cpp:117-138): element k =
+// x * ps + y of the level's ps x ps patch around pixel pc, x the row.  The
+// reference's mixed precision: the anchor floorf((float)(pc / scale)) * scale, the
+// sub-pixel offsets in float, w_tl / w_tr / w_bl through `1.0 - ...` in double
+// and rounded to float, w_br in float, the four taps summed in float left to
+// right.  Every tap must be inside the image: it is for a pc inside
+// addSparseMap's border (ps / 2 + 1) * 8.
+SEL_HD float vis_getpatch(const uint8_t* img, int w, const double* pc, int ps, int level, int k) {
+    const float u_ref = (float)pc[0], v_ref = (float)pc[1];
+    const int scale = 1 << level, half = ps / 2;
+    const int u_ref_i = (int)(floorf((float)(pc[0] / scale)) * (float)scale);
+    const int v_ref_i = (int)(floorf((float)(pc[1] / scale)) * (float)scale);
+    const float su = (u_ref - (float)u_ref_i) / (float)scale, sv = (v_ref - (float)v_ref_i) / (float)scale;
+    const float w_tl = (float)((1.0 - su) * (1.0 - sv)), w_tr = (float)(su * (1.0 - sv)),
+                w_bl = (float)((1.0 - su) * sv), w_br = su * sv;
+    const int x = k / ps, y = k - x * ps;
+    const uint8_t* p = img + (int64_t)(v_ref_i - half * scale + x * scale) * w + (u_ref_i - half * scale + y * scale);
+    return ((w_tl * (float)p[0] + w_tr * (float)p[scale]) + w_bl * (float)p[(int64_t)scale * w]) +
+           w_br * (float)p[(int64_t)scale * w + scale];
+}
+
+// addSparseMap's grid (lidar_selection.cpp:140-165, reset_grid): cells of
+// grid_size pixels, grid_n_height = height / grid_size of them per column,
+// length = grid_n_width * grid_n_height in all; border = (ps / 2 + 1) * 8.
+struct VisGrid {
+    int32_t grid_size, grid_n_height, length, border, ps;
+};
+
+enum VisFate : int { kVisOutOfFrame = 0, kVisInFrame = 1, kVisOverflow = 2 };
+
+// One cloud point of addSparseMap's first loop up to its grid index: w2c with no
+// p_cam.z test (behind: inside the frame with p_cam.z > 0 false), isInFrame(
+// pc.cast<int>(), border) taken in double (a NaN fails it), then index =
+// (int)(pc.x / grid_size) * grid_n_height + (int)(pc.y / grid_size), which
+// aliases into the next column where height - border > grid_n_height * grid_size;
+// kVisOverflow: index >= length, the reference's out-of-bounds write.
+SEL_HD int vis_project(const RgbCam& C, const VisGrid& G, float wx, float wy, float wz, double* pc, bool& behind,
+                       int& index) {
+    const double pw[3] = {(double)wx, (double)wy, (double)wz};  // V3D pt(p.x, p.y, p.z)
+    double pf[3];
+    cam_w2f(C.Rcw, C.Pcw, pw, pf);
+    vio_world2cam(C, pf, pc);
+    behind = false;
+    index = -1;
+    const double b = (double)G.border;
+    if (!(pc[0] >= b && pc[0] < (double)(C.w - G.border) && pc[1] >= b && pc[1] < (double)(C.h - G.border)))
+        return kVisOutOfFrame;
+    behind = !(pf[2] > 0);
+    index = (int)(pc[0] / G.grid_size) * G.grid_n_height + (int)(pc[1] / G.grid_size);
+    return index >= G.length ? kVisOverflow : kVisInFrame;
+}
+
+// One coordinate of AddPoint's VOXEL_KEY (lidar_selection.cpp:195-208), 0.5 m
+// voxels: the quotient stored as float, a negative one lowered by 1.0 (in
+// double, stored as float again), then truncated: -1.0 m gives -3, not floor's -2.
+SEL_HD int64_t vis_voxel_key(float pw) {
+    float loc = (float)((double)pw / 0.5);
+    if (loc < 0) loc = (float)((double)loc - 1.0);
+    return (int64_t)loc;
 }
 
 }  // namespace livo

@@ -306,6 +306,11 @@ struct livo_ctx {
     uint8_t* rgb_img = nullptr;        // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
     size_t rgb_cap = 0;
     int32_t rgb_w = 0, rgb_h = 0;      // its size (0: none)
+    uint8_t* vis_img = nullptr;        // livo_vio_select: the last uploaded gray image (reused by gray == NULL)
+    size_t vis_cap = 0;
+    int32_t vis_w = 0, vis_h = 0;      // its size (0: none)
+    void* vis_buf = nullptr;           // ... and its cell table, flags, slots, counters, records and patches
+    size_t vis_bytes = 0;
     void* prim_tmp = nullptr;          // rocPRIM scratch (sorts, scans)
     size_t prim_bytes = 0;
     // scans
@@ -1915,6 +1920,8 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->prim_tmp) (void)hipFree(c->prim_tmp);
     if (c->vio_buf) (void)hipFree(c->vio_buf);
     dev_free(c->rgb_img);
+    dev_free(c->vis_img);
+    if (c->vis_buf) (void)hipFree(c->vis_buf);
     dev_free(c->nodes);
     dev_free(c->lnodes);
     dev_free(c->lpts);
@@ -4518,6 +4525,119 @@ int livo_cloud_colorize(livo_ctx* c, int32_t scan_id, const livo_state* state, c
             HIP_TRY(hipMemcpyAsync(out, R.out, (size_t)kept * sizeof(livo_rgb_point), hipMemcpyDeviceToHost, c->stream));
         if (src_index)
             HIP_TRY(hipMemcpyAsync(src_index, R.src_index, (size_t)kept * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return LIVO_OK;
+}
+
+int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                    int32_t grid_size, const uint8_t* gray, int32_t width, int32_t height, livo_vis_point* out,
+                    float* patches, int64_t cap, int64_t* n_out, livo_vis_stats* stats) {
+    if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
+    if (grid_size < 1 || p->patch_size < 1 || p->patch_size > 8 || cap < 0) return LIVO_E_INVALID;
+    if (width <= 0 || height <= 0 || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
+    if (out ? !patches : cap != 0) return LIVO_E_INVALID;
+    VisParams V{};
+    V.grid.ps = p->patch_size;
+    V.grid.border = (p->patch_size / 2 + 1) * 8;
+    V.grid.grid_size = grid_size;
+    // one cell at least inside the border, in both directions
+    if ((int64_t)width - 2 * V.grid.border < grid_size || (int64_t)height - 2 * V.grid.border < grid_size)
+        return LIVO_E_INVALID;
+    V.grid.grid_n_height = height / grid_size;
+    const int64_t length = (int64_t)(width / grid_size) * V.grid.grid_n_height;
+    if (length > (int64_t)0x7FFFFFFF - kVisBlock) return LIVO_E_RANGE;
+    V.grid.length = (int32_t)length;
+    if (!gray && (!c->vis_img || c->vis_w != width || c->vis_h != height)) return LIVO_E_INVALID;
+    // the source cloud, as livo_frame_to_world selects it
+    int64_t n;
+    if (scan_id < 0) {
+        V.src = c->fe_raw;
+        n = c->fe_raw ? c->fe_n : 0;
+        V.stride = 5;
+    } else {
+        ScanBuf* s = get_scan(c, scan_id);
+        if (!s) return LIVO_E_NOSCAN;
+        V.src = s->pts;
+        n = s->n;
+        V.stride = 4;
+        V.iperm = s->d_iperm;  // the caller's point order
+    }
+    if (n > (int64_t)0x7FFFFFFF - kVisBlock) return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    const size_t img_bytes = (size_t)width * (size_t)height;
+    if (gray) {
+        c->vis_w = c->vis_h = 0;  // (no image to reuse if the upload fails)
+        if (img_bytes > c->vis_cap) {
+            dev_free(c->vis_img);
+            c->vis_cap = 0;
+            if (dev_alloc(&c->vis_img, img_bytes)) return LIVO_E_OOM;
+            c->vis_cap = img_bytes;
+        }
+        HIP_TRY(hipMemcpyAsync(c->vis_img, gray, img_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    const int pst3 = 3 * p->patch_size * p->patch_size;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_tab = al((size_t)length * 8), b_u32 = al((size_t)length * 4), b_ctr = al(kVisCtrN * 8),
+                 b_rec = al((size_t)length * sizeof(livo_vis_point)), b_pat = al((size_t)length * pst3 * 4);
+    const size_t total = b_tab + b_ctr + 2 * b_u32 + b_rec + b_pat;
+    if (total > c->vis_bytes) {
+        if (c->vis_buf) (void)hipFree(c->vis_buf);
+        c->vis_buf = nullptr;
+        c->vis_bytes = 0;
+        if (hipMalloc(&c->vis_buf, total) != hipSuccess) return LIVO_E_OOM;
+        c->vis_bytes = total;
+    }
+    char* q = (char*)c->vis_buf;
+    V.table = (unsigned long long*)q; q += b_tab;
+    V.ctr = (unsigned long long*)q; q += b_ctr;  // (behind the table: one clear for both)
+    V.flag = (uint32_t*)q; q += b_u32;
+    uint32_t* d_slot = (uint32_t*)q; q += b_u32;
+    V.slot = d_slot;
+    V.out = (livo_vis_point*)q; q += b_rec;
+    V.patches = (float*)q;
+    V.n = (int32_t)n;
+    std::memcpy(V.W.rot, state->rot, sizeof(V.W.rot));
+    std::memcpy(V.W.pos, state->pos, sizeof(V.W.pos));
+    std::memcpy(V.W.R_LI, c->params.R_LI, sizeof(V.W.R_LI));
+    std::memcpy(V.W.t_LI, c->params.t_LI, sizeof(V.W.t_LI));
+    cam_pose(p->R_ci, p->P_ci, state->rot, state->pos, V.cam.Rcw, V.cam.Pcw);  // once per call
+    V.cam.fx = p->cam.fx; V.cam.fy = p->cam.fy; V.cam.cx = p->cam.cx; V.cam.cy = p->cam.cy;
+    std::memcpy(V.cam.d, p->cam.d, sizeof(V.cam.d));
+    V.cam.distortion = std::fabs(p->cam.d[0]) > 0.0000001 ? 1 : 0;  // vikit: distortion_ = |d0| > 1e-7
+    V.cam.w = width;
+    V.cam.h = height;
+    V.img = c->vis_img;
+    unsigned long long ctr[kVisCtrN] = {0, 0, 0, 0};
+    if (n > 0) {
+        HIP_TRY(hipMemsetAsync(V.table, 0, b_tab + b_ctr, c->stream));
+        RC_TRY(launch_vis_score(V, c->stream));
+        RC_TRY(launch_vis_flags(V, c->stream));
+        if (out) {  // (the table bounds the result: the records are written before their count is known)
+            RC_TRY(ivox_scan(c, V.flag, d_slot, length));
+            RC_TRY(launch_vis_emit(V, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(ctr, V.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (gray) {
+        c->vis_w = width;
+        c->vis_h = height;
+    }
+    const int64_t sel = (int64_t)ctr[kVisCtrOut];
+    *n_out = sel;
+    if (stats) {
+        stats->n_in = n;
+        stats->in_frame = (int64_t)ctr[kVisCtrInFrame];
+        stats->behind_in_frame = (int64_t)ctr[kVisCtrBehind];
+        stats->cell_overflow = (int64_t)ctr[kVisCtrOverflow];
+        stats->n_out = sel;
+        stats->n_cells = length;
+    }
+    if (out && cap < sel) return LIVO_E_CAPACITY;
+    if (out && sel > 0) {
+        HIP_TRY(hipMemcpyAsync(out, V.out, (size_t)sel * sizeof(livo_vis_point), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(patches, V.patches, (size_t)sel * pst3 * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return LIVO_OK;

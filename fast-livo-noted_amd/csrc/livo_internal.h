@@ -609,6 +609,29 @@ struct RgbParams {
 };
 int launch_rgb_points(const RgbParams& p, void* stream);
 int launch_rgb_scatter(const RgbParams& p, void* stream);
+// LidarSelector::addSparseMap (vis_kernels.hip): the cloud of launch_to_world
+// scored in the gray image, the best point of each grid cell kept, its record
+// and patch pyramid written in ascending cell order.
+constexpr int kVisBlock = 256;
+enum { kVisCtrInFrame = 0, kVisCtrBehind = 1, kVisCtrOverflow = 2, kVisCtrOut = 3, kVisCtrN = 4 };
+struct VisParams {
+    const float* src;         // n points, stride floats each (x, y, z, ...), stored order
+    const int32_t* iperm;     // cloud index -> stored position (null: the same)
+    int32_t n, stride;
+    WorldParams W;
+    RgbCam cam;
+    VisGrid grid;
+    const uint8_t* img;       // cam.w * cam.h bytes, gray
+    unsigned long long* table;  // grid.length cell winners: score bits << 32 | ~cloud index; 0: empty
+    uint32_t* flag;           // grid.length: 1 occupied
+    const uint32_t* slot;     // their exclusive scan (the emit)
+    unsigned long long* ctr;  // kVisCtrN counters, zeroed by the caller
+    livo_vis_point* out;      // selected records, ascending cell index
+    float* patches;           // 3 * ps^2 floats each
+};
+int launch_vis_score(const VisParams& p, void* stream);
+int launch_vis_flags(const VisParams& p, void* stream);
+int launch_vis_emit(const VisParams& p, void* stream);
 // laserCloudOri / corr_normvect compaction in the caller's order (stored-order sel / normvec / points).
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream);
 int launch_ori_scatter(const float* pts4, const float* normvec, const uint8_t* sel, const int32_t* perm,

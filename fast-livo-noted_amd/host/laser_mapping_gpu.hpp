@@ -214,6 +214,33 @@ public:
         return st;
     }
 
+    // lidar_selector->addSparseMap(img, pg) (lidar_selection.cpp:140-193): pg is the same
+    // cloud publish_frame_world_rgb takes (dense_map_en: the last set_scan_raw frame at
+    // full resolution, else the current feats_down_body) at `state`, img the 8-bit gray
+    // image (row stride width; nullptr reuses the image of the previous call).  Fills
+    // `points` with the best-scored point of each grid_size cell, in ascending cell
+    // order, and `patches` with their level 0, 1, 2 patches (3 * patch_size^2 floats a
+    // point, Feature::patch layout) as livo_vio_update reads them; what the reference
+    // files in feat_map is points[k].voxel -> (points[k], patches of k).
+    livo_vis_stats addSparseMap(const livo_vio_params& vio, const uint8_t* img, int32_t width, int32_t height,
+                                int32_t grid_size, std::vector<livo_vis_point>& points, std::vector<float>& patches,
+                                bool dense_map_en = true) {
+        if (!dense_map_en && scan_id_ < 0) throw Error("addSparseMap", LIVO_E_NOSCAN);
+        const int32_t id = dense_map_en ? -1 : scan_id_;
+        int64_t n = 0;
+        livo_vis_stats st{};
+        check(livo_vio_select(ctx_, id, &state, &vio, grid_size, img, width, height, nullptr, nullptr, 0, &n, &st),
+              "livo_vio_select");  // the sizing call (it uploads the image)
+        const size_t per = (size_t)3 * (size_t)vio.patch_size * (size_t)vio.patch_size;
+        points.resize((size_t)n);
+        patches.resize((size_t)n * per);
+        if (n > 0)
+            check(livo_vio_select(ctx_, id, &state, &vio, grid_size, nullptr, width, height, points.data(),
+                                  patches.data(), n, &n, &st),
+                  "livo_vio_select");
+        return st;
+    }
+
     livo_ctx* ctx() const { return ctx_; }
     const livo_params& params() const { return params_; }
 

@@ -10,6 +10,7 @@ path:
     LaserMapping::map_incremental        -> Context.map_incremental
     IEKF loop of LaserMapping::Run       -> Context.iekf_update(_batch)
     LaserMapping::publish_frame_world_rgb -> Context.colorize
+    LidarSelector::addSparseMap          -> Context.vio_select
 
 There is no CPU fallback: loading fails loudly if the HIP library is missing,
 and every compute call raises LivoError when the GPU path fails.
@@ -165,6 +166,23 @@ class RgbStats(C.Structure):
                 ("edge_reads", C.c_int64)]
 
 
+class VisPoint(C.Structure):
+    """livo_vis_point: one new visual map point of addSparseMap (64 bytes)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("score", C.c_float),
+                ("u", C.c_double), ("v", C.c_double), ("src_index", C.c_int32), ("cell", C.c_int32),
+                ("voxel", C.c_int64 * 3)]
+
+
+VIS_POINT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32), ("score", np.float32),
+                            ("u", np.float64), ("v", np.float64), ("src_index", np.int32), ("cell", np.int32),
+                            ("voxel", np.int64, (3,))])
+
+
+class VisStats(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("in_frame", C.c_int64), ("behind_in_frame", C.c_int64),
+                ("cell_overflow", C.c_int64), ("n_out", C.c_int64), ("n_cells", C.c_int64)]
+
+
 def vio_params(cam: dict, Rci, Pci) -> VioParams:
     """livo_vio_params from a camera dict (fx, fy, cx, cy, d, width, height) and the extrinsics."""
     p = VioParams()
@@ -233,6 +251,8 @@ SIGNATURES = {
     "livo_frame_to_world": (C.c_int, [_P, C.c_int32, C.POINTER(State), _P, C.c_int64, C.POINTER(C.c_int64)]),
     "livo_cloud_colorize": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.POINTER(VioParams), _P, C.c_int32, C.c_int32,
                                       _P, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(RgbStats)]),
+    "livo_vio_select": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.POINTER(VioParams), C.c_int32, _P, C.c_int32,
+                                  C.c_int32, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(VisStats)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -766,6 +786,38 @@ class Context:
         stats = {"iterations": list(st.iterations), "updates": list(st.updates), "last_error": list(st.last_error),
                  "cov_updated": st.cov_updated, "n_meas": st.n_meas, "out_of_frame": st.out_of_frame}
         return state_from_c(s), stats, err[:n]
+
+    def vio_select(self, state: dict, gray, vio_params: VioParams, grid_size: int, scan_id: int = -1):
+        """LidarSelector::addSparseMap (livo_vio_select): of the cloud of frame_to_world(state, scan_id), the
+        best shiTomasi-scored point of every grid_size cell of the gray image in the camera of vio_params
+        (cam, R_ci, P_ci, patch_size) at `state`, with its level 0..2 patches.  gray: (height, width) uint8;
+        None reuses the image of the previous call.  Returns (points: VIS_POINT_DTYPE array in ascending
+        cell order, patches: (n, 3 * patch_size^2) float32 as vio_update reads them, stats: dict)."""
+        st = state_to_c(state)
+        img = None
+        if gray is not None:
+            img = np.ascontiguousarray(gray, np.uint8)
+            if img.ndim != 2:
+                raise ValueError("gray must be (height, width)")
+            w, h = img.shape[1], img.shape[0]
+        else:
+            w, h = vio_params.cam.width, vio_params.cam.height
+        n = C.c_int64()
+        vs = VisStats()
+        # the sizing call uploads the image; the real one reuses it
+        _check("livo_vio_select", self._L.livo_vio_select(
+            self.h, scan_id, C.byref(st), C.byref(vio_params), grid_size, _ptr(img), w, h, None, None, 0,
+            C.byref(n), C.byref(vs)))
+        cap = n.value
+        pst3 = 3 * vio_params.patch_size * vio_params.patch_size
+        pts = np.zeros(cap, VIS_POINT_DTYPE)
+        pat = np.zeros((cap, pst3), np.float32)
+        if cap > 0:
+            _check("livo_vio_select", self._L.livo_vio_select(
+                self.h, scan_id, C.byref(st), C.byref(vio_params), grid_size, None, w, h, _ptr(pts), _ptr(pat), cap,
+                C.byref(n), C.byref(vs)))
+        stats = {f: int(getattr(vs, f)) for f, _ in VisStats._fields_}
+        return pts[:n.value], pat[:n.value], stats
 
     def scan_inherit_neighbors(self, dst: int, src: int):
         _check("livo_scan_inherit_neighbors", self._L.livo_scan_inherit_neighbors(self.h, dst, src))

@@ -30,6 +30,8 @@
  *                                                   src/laser_mapping.cpp:129-130
  *   livo_cloud_colorize ← LaserMapping::publish_frame_world_rgb (the coloured cloud)
  *                                                   src/laser_mapping.cpp:1351-1381
+ *   livo_vio_select     ← LidarSelector::addSparseMap (a frame's new visual map points)
+ *                                                   src/lidar_selection.cpp:117-221
  *
  * Conventions
  *   - plain pointers and sizes only; no C++ or torch types cross the ABI;
@@ -54,12 +56,13 @@
 extern "C" {
 #endif
 
-/* 7: livo_cloud_colorize added (nothing else changed).
+/* 8: livo_vio_select added (nothing else changed).
+ * 7: livo_cloud_colorize added (nothing else changed).
  * 5: livo_ivox_info grew add_passes (round 4).
  * 4: livo_timings grew the per-evaluation fields (eval_ms ... gap_ms), LIVO_E_BUSY
  *    and the submit / wait pair were added (round 3); a binary built against 3
  *    passes a smaller livo_timings. */
-#define LIVO_ABI_VERSION 7
+#define LIVO_ABI_VERSION 8
 #define LIVO_DIM_STATE 18        /* DIM_STATE, include/common_lib.h:32 */
 #define LIVO_NUM_MATCH_POINTS 5  /* NUM_MATCH_POINTS, include/common_lib.h:37 */
 #define LIVO_MAX_EVALS 16        /* max h_share/solve evaluations per scan update */
@@ -72,7 +75,7 @@ enum {
     LIVO_E_NOSCAN = -4,    /* unknown / released scan id */
     LIVO_E_OOM = -5,       /* device allocation failed */
     LIVO_E_RANGE = -6,     /* size beyond the supported range */
-    LIVO_E_CAPACITY = -7,  /* capacity exceeded (reserved) */
+    LIVO_E_CAPACITY = -7,  /* capacity exceeded (livo_vio_select: cap below the result) */
     LIVO_E_BUSY = -8       /* batches in flight (livo_iekf_update_batch_submit) */
 };
 
@@ -535,6 +538,51 @@ typedef struct livo_rgb_stats {
 int livo_cloud_colorize(livo_ctx* ctx, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
                         const uint8_t* bgr, int32_t width, int32_t height, livo_rgb_point* out, int32_t* src_index,
                         int64_t cap, int64_t* n, livo_rgb_stats* stats);
+/* LidarSelector::addSparseMap (src/lidar_selection.cpp:140-193, with getpatch
+ * :117-138 and AddPoint's key :195-208): a frame's new visual map points.  The
+ * cloud of livo_frame_to_world (same scan_id, x, y, z bit for bit; of p only
+ * cam, R_ci, P_ci and patch_size are read) is projected into the gray image at
+ * `state` with no p_cam.z test, as the reference has none; the points inside
+ * the border (patch_size / 2 + 1) * 8 are scored with vikit's shiTomasiScore at
+ * the truncated pixel, and of every cell of grid_size pixels (index =
+ * (int)(u / grid_size) * (height / grid_size) + (int)(v / grid_size), which
+ * aliases into the next column where height is no multiple of grid_size) the
+ * point of the greatest positive score is selected, the lowest cloud index
+ * among equals (`cur_value > map_value[index]`, in cloud order).  Selected
+ * points come in ascending cell index, each with its level 0, 1, 2 patches in
+ * Feature::patch layout, patch_size^2 * level + x * patch_size + y, as
+ * livo_vio_update reads them (search level 0).  Feature::f is not produced.
+ * gray: 8-bit, row stride width; width / height must equal p->cam.width /
+ * height.  The image is kept in a buffer of this entry point's own
+ * (livo_vio_update's and livo_cloud_colorize's are not touched); gray == NULL
+ * reuses the image of the previous successful call (LIVO_E_INVALID if there
+ * is none or its size differs).  LIVO_E_INVALID too for grid_size < 1,
+ * patch_size outside 1..8, and a frame whose area inside the border is
+ * narrower or lower than one cell.
+ * *n = selected points (set on LIVO_OK and LIVO_E_CAPACITY).  out == NULL
+ * with cap == 0 returns *n and the stats only; otherwise out (cap records) and
+ * patches (cap x 3 x patch_size^2 floats) are both needed, and cap < *n
+ * returns LIVO_E_CAPACITY with nothing written (n_cells always suffices).
+ * stats may be NULL.  Two calls on the same input give the same bytes. */
+typedef struct livo_vis_point {      /* 64 bytes */
+    float   x, y, z;                 /* the cloud's world point (the bits of livo_frame_to_world)   */
+    float   score;                   /* shiTomasiScore at (int)u, (int)v                             */
+    double  u, v;                    /* new_frame_->w2c(pt)                                           */
+    int32_t src_index;               /* index into the source cloud                                  */
+    int32_t cell;                    /* grid index i of addSparseMap's second loop                    */
+    int64_t voxel[3];                /* AddPoint's VOXEL_KEY                                          */
+} livo_vis_point;
+typedef struct livo_vis_stats {
+    int64_t n_in;                    /* points of the source cloud                                    */
+    int64_t in_frame;                /* passed isInFrame(pc.cast<int>(), (patch_size_half+1)*8)       */
+    int64_t behind_in_frame;         /* of those: p_cam.z <= 0 or NaN (the reference has no z test here) */
+    int64_t cell_overflow;           /* of those: index >= length (an out-of-bounds write in the reference) */
+    int64_t n_out;                   /* selected points = cells of TYPE_POINTCLOUD                     */
+    int64_t n_cells;                 /* length = (width/grid_size) * (height/grid_size)               */
+} livo_vis_stats;
+int livo_vio_select(livo_ctx* ctx, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                    int32_t grid_size, const uint8_t* gray, int32_t width, int32_t height,
+                    livo_vis_point* out, float* patches, int64_t cap, int64_t* n, livo_vis_stats* stats);
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
