@@ -432,6 +432,42 @@ def make_vio_frame(n_points: int, frame_id: int = 0, patch_size: int = 4, rot_de
     return frame, st, truth
 
 
+def crop_vio_frame(frame: dict, x0: int, y0: int, x1: int, y1: int) -> dict:
+    """The frame seen through the window image[y0:y1, x0:x1]: the principal point
+    moves with the window, the points and their patches (sampled from the full
+    image at the true pose) stay, so points near or beyond the new border read
+    clamped pixels in the update."""
+    out = dict(frame)
+    out["image"] = np.ascontiguousarray(frame["image"][y0:y1, x0:x1])
+    cam = dict(frame["cam"])
+    cam["cx"], cam["cy"] = cam["cx"] - x0, cam["cy"] - y0
+    cam["height"], cam["width"] = out["image"].shape
+    out["cam"] = cam
+    return out
+
+
+def tile_vio_frame(frame: dict, n: int, seed: int) -> dict:
+    """An n-point frame from the rows of a smaller one, repeated and shuffled
+    (make_vio_frame samples its patches in a Python loop)."""
+    rng = np.random.default_rng(seed)
+    idx = rng.permutation(np.arange(n) % len(frame["pos"]))
+    out = dict(frame)
+    for k in ("pos", "levels", "patches"):
+        out[k] = np.ascontiguousarray(frame[k][idx])
+    return out
+
+
+def mirror_vio_points(frame: dict, pose: dict, every: int = 16) -> dict:
+    """Every `every`-th point mirrored through the centre of the camera at `pose`
+    (c = p + R R_ciᵀ (−P_ci)): it lies behind the camera and still projects to a
+    finite pixel, its patch unchanged."""
+    c = pose["pos"] + pose["rot"] @ (frame["Rci"].T @ -frame["Pci"])
+    out = dict(frame)
+    out["pos"] = frame["pos"].copy()
+    out["pos"][::every] = 2.0 * c - out["pos"][::every]
+    return out
+
+
 def boundary_points(rng, ds: float, n: int, span: int = 40) -> np.ndarray:
     """(n, 3) float32 points within a few ulps of ikd-Tree downsample box faces j * ds
     (ikd_Tree.cpp:392-397), where float rounding makes neighbouring boxes overlap or

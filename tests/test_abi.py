@@ -166,3 +166,80 @@ def test_ivox_abi_layouts_and_args(tmp_path, built):
     assert L.livo_map_incremental(None, 0, None, 0.5, 1, None, None) == -1
     assert L.livo_scan_inherit_neighbors(None, 0, 0) == -1
     assert b"capacity" in L.livo_error_string(-7)
+
+
+# ------------------------------------------------------ livo_vio_update ----
+def _vio_call(frame, state):
+    """The arguments of one livo_vio_update call, by name, and a function that makes it."""
+    import livo_amd
+    import numpy as np
+    a = {"p": livo_amd.vio_params(frame["cam"], frame["Rci"], frame["Pci"]),
+         "image": np.ascontiguousarray(frame["image"], np.uint8),
+         "pos": np.ascontiguousarray(frame["pos"], np.float64),
+         "levels": np.ascontiguousarray(frame["levels"], np.int32),
+         "patches": np.ascontiguousarray(frame["patches"], np.float32),
+         "state": livo_amd.state_to_c(state), "prior": None}
+    a["p"].patch_size = frame["patch_size"]
+    a["width"], a["height"], a["n"] = a["image"].shape[1], a["image"].shape[0], len(a["pos"])
+
+    def call(ctx, **over):
+        b = dict(a, **over)
+        st = livo_amd.State.from_buffer_copy(bytes(a["state"]))
+        err = np.zeros(max(b["n"], 1), np.float32)
+        stats = livo_amd.VioStats()
+        ptr = livo_amd._ptr
+        rc = livo_amd.load().livo_vio_update(
+            ctx.h, C.byref(b["p"]), ptr(b["image"]), b["width"], b["height"], ptr(b["pos"]), ptr(b["levels"]),
+            ptr(b["patches"]), b["n"], C.byref(st), C.byref(b["prior"]) if b["prior"] is not None else None,
+            ptr(err), C.byref(stats))
+        return rc, bytes(st), bytes(stats), err.tobytes()
+    return a, call
+
+
+def _vio_p(a, **fields):
+    import livo_amd
+    p = livo_amd.VioParams.from_buffer_copy(bytes(a["p"]))
+    for k, v in fields.items():
+        setattr(p, k, v)
+    return p
+
+
+@pytest.mark.gpu
+def test_vio_update_rejects_bad_arguments(gpu_ctx):
+    """Every argument check of livo_vio_update answers LIVO_E_INVALID and leaves *state as it was."""
+    from livo_amd import synth
+    fr, st, _ = synth.make_vio_frame(10, 6)
+    a, call = _vio_call(fr, st)
+    n = a["n"]
+    assert n >= 2
+    lev_lo, lev_hi = a["levels"].copy(), a["levels"].copy()
+    lev_lo[n - 1], lev_hi[0] = -1, 9
+    bad = {"patch_size 0": {"p": _vio_p(a, patch_size=0)}, "patch_size 9": {"p": _vio_p(a, patch_size=9)},
+           "level -1": {"levels": lev_lo}, "level 9": {"levels": lev_hi},
+           "img_point_cov 0": {"p": _vio_p(a, img_point_cov=0.0)},
+           "img_point_cov NaN": {"p": _vio_p(a, img_point_cov=float("nan"))},
+           "max_iterations -1": {"p": _vio_p(a, max_iterations=-1)},
+           "width 0": {"width": 0}, "null image": {"image": None}, "null pos": {"pos": None}}
+    before = bytes(a["state"])
+    for name, over in bad.items():
+        rc, state, _, _ = call(gpu_ctx, **over)
+        assert rc == -1, name  # LIVO_E_INVALID
+        assert state == before, name
+    # the unchanged arguments are accepted, and move the state
+    rc, state, _, _ = call(gpu_ctx)
+    assert rc == 0 and state != before
+
+
+@pytest.mark.gpu
+def test_vio_update_null_prior_is_the_state(gpu_ctx):
+    """prior == NULL is prior = state, byte for byte (state, stats and patch errors)."""
+    import livo_amd
+    from livo_amd import synth
+    fr, st, _ = synth.make_vio_frame(300, 6)
+    a, call = _vio_call(fr, st)
+    got_null = call(gpu_ctx)
+    got_state = call(gpu_ctx, prior=livo_amd.state_to_c(st))
+    assert got_null[0] == 0 and got_null == got_state
+    # and a prior that differs from the state is used
+    moved = dict(st, pos=st["pos"] + 0.01)
+    assert call(gpu_ctx, prior=livo_amd.state_to_c(moved))[1] != got_null[1]
