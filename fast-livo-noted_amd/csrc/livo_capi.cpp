@@ -3513,6 +3513,15 @@ static int prof_batch_end(livo_ctx* c, const BatchPlan& P) {
     return LIVO_OK;
 }
 
+// A batch that was queued only in part, or whose end was not seen: its scans' neighbour
+// records are no search's whole answer (the fused first search leaves the records that the
+// second search rewrites unwritten, so some may still be an earlier update's).  They are
+// searched again before anything reads them (livo_scan_neighbors: LIVO_E_NOSCAN).
+static void batch_records_invalid(livo_ctx* c, int32_t n, const int32_t* ids) {
+    for (int32_t b = 0; b < n; b++)
+        if (ScanBuf* s = get_scan_q(c, ids[b])) s->searched = false;
+}
+
 static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int model, const livo_state* states,
                          const livo_state* priors, const livo_ikfom_state* ik_states, bool sync) {
     if (!c || n < 0 || (n > 0 && (!ids || (model == kModelIkfom ? !ik_states : !states)))) return LIVO_E_INVALID;
@@ -3534,13 +3543,19 @@ static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int 
     const BatchLane* prev = (c->lane_serial && c->last_lane >= 0 && c->last_lane != L && c->lane[c->last_lane].busy)
                                 ? &c->lane[c->last_lane] : nullptr;
     c->last_lane = L;
-    for (int gi = 0; gi < P.ngroups; gi++) RC_TRY(stage_group(c, L, P, gi, ids, prev));
-    KnnParams kp[kMaxGroups];
-    HsParams hp[kMaxGroups];
-    for (int gi = 0; gi < P.ngroups; gi++) group_params(c, L, P, gi, kp[gi], hp[gi]);
-    RC_TRY(P.fused ? queue_fused(c, P, ids, kp, hp) : queue_unfused(c, P, kp, hp));
-    for (int gi = 0; gi < P.ngroups; gi++) RC_TRY(finish_group(c, B, P, gi));
-    RC_TRY(prof_batch_end(c, P));
+    for (int gi = 0; gi < P.ngroups; gi++) RC_TRY(stage_group(c, L, P, gi, ids, prev));  // (copies: no record touched yet)
+    const int rc = [&]() -> int {
+        KnnParams kp[kMaxGroups];
+        HsParams hp[kMaxGroups];
+        for (int gi = 0; gi < P.ngroups; gi++) group_params(c, L, P, gi, kp[gi], hp[gi]);
+        RC_TRY(P.fused ? queue_fused(c, P, ids, kp, hp) : queue_unfused(c, P, kp, hp));
+        for (int gi = 0; gi < P.ngroups; gi++) RC_TRY(finish_group(c, B, P, gi));
+        return prof_batch_end(c, P);
+    }();
+    if (rc) {
+        batch_records_invalid(c, n, ids);
+        return rc;
+    }
     B.busy = true;
     B.n = n;
     B.ids.assign(ids, ids + n);
@@ -3631,8 +3646,15 @@ static int batch_collect(livo_ctx* c, int L, livo_state* states, livo_iter_stats
     B.n = 0;
     // wait by polling: the batch is short, and a blocking wait's wake-up
     // latency was a visible part of the gap between two batches
-    for (int gi = P.ngroups - 1; gi >= 0; gi--) HIP_TRY(event_wait(B.done[gi]));
-    if (P.prof >= 2) HIP_TRY(stream_wait(c->stream));  // the replay counter's read-back and the batch-end event
+    const int rc = [&]() -> int {
+        for (int gi = P.ngroups - 1; gi >= 0; gi--) HIP_TRY(event_wait(B.done[gi]));
+        if (P.prof >= 2) HIP_TRY(stream_wait(c->stream));  // the replay counter's read-back and the batch-end event
+        return LIVO_OK;
+    }();
+    if (rc) {
+        batch_records_invalid(c, P.n, ids.data());
+        return rc;
+    }
     for (int32_t b = 0; b < P.n; b++) {
         const IekfSlot& s = hslot(P, b);
         if (P.model == kModelIkfom) {

@@ -866,14 +866,24 @@ __device__ unsigned long long g_amb_reason[8];
 // lane l's half at l * 4 + ((k + (l >> 2)) & 3), so that 16 consecutive lanes'
 // 16-B writes of one part cover all 64 banks.
 __device__ __forceinline__ int rec_stage_slot(int l, int k) { return l * 4 + ((k + (l >> 2)) & 3); }
+// Whether a lane's record of a search is read before the scan's next search rewrites it:
+// a flagged query's replay reads its record back, and a full list beyond the sqdist gate
+// leaves plane state 0 (fit_plane), which the next evaluation fits from the record.
+// (A short list, d5 = +inf, counts too: that costs a store, never a missing record.)
+__device__ __forceinline__ bool rec_needed(bool amb, float d5, float max_sqd) { return amb || !(d5 <= max_sqd); }
 template <bool DELTA = false, bool NBR = false>  // NBR: nbr takes the neighbours
 // stage: the wave's LDS record stage, which takes the record's hot half (with
 // stage_flag's kRecNoXyz; the caller stores it and, for a full record, the cold
 // half from nbr); nullptr: the full record goes straight to job.nn.
+// dead (wave-uniform): no other reader than rec_needed's will see this search's records
+// (iekf_eval_body), so the stage is left alone unless some lane of the wave needs its
+// record.  staged: whether this lane wrote the stage -- the one decision; the caller
+// stores the stage of a wave in which any lane did.
 __device__ __forceinline__ bool lq_finish(LeafQuery& q, const KnnParams& P, const HsJob& job, unsigned bjob,
                                           int i, const float4* __restrict__ lpts, bool overrun, bool enqueue = true,
                                           const float4* __restrict__ dpts = nullptr, float4* nbr = nullptr,
-                                          float4* stage = nullptr, int stage_flag = 0) {
+                                          float4* stage = nullptr, int stage_flag = 0, bool dead = false,
+                                          float max_sqd = 0.0f, bool* staged = nullptr) {
     const int cnt = (int)min<int64_t>(P.lM, (int64_t)kNN);
     float4 a[kNN];
 #pragma unroll
@@ -944,11 +954,14 @@ __device__ __forceinline__ bool lq_finish(LeafQuery& q, const KnnParams& P, cons
     }
     const int flag = amb ? 4 : (tie ? 16 : 0);
     if (stage) {
-        float4 h[4];
-        rec_pack_hot(h, d, idx, key, cnt, flag | (stage_flag & (int)kRecNoXyz));
-        const int sl = threadIdx.x & 63;
+        if (!dead || __ballot(rec_needed(amb, d[kNN - 1], max_sqd))) {
+            float4 h[4];
+            rec_pack_hot(h, d, idx, key, cnt, flag | (stage_flag & (int)kRecNoXyz));
+            const int sl = threadIdx.x & 63;
 #pragma unroll
-        for (int k = 0; k < 4; k++) stage[rec_stage_slot(sl, k)] = h[k];
+            for (int k = 0; k < 4; k++) stage[rec_stage_slot(sl, k)] = h[k];
+            if (staged) *staged = true;
+        }
     } else {
         rec_store_full(job.nn + i, nb, idx, cnt, flag);
     }
@@ -3179,6 +3192,21 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
     bool prefit = false;  // the plane of this evaluation fitted in the search branch
     if (slot->ctrl.stop) return;  // block-uniform
     const int search = FIRST ? 1 : slot->ctrl.search_en;
+    // The first search's records are dead when the scan is sure to search again before
+    // anything but this launch reads them: the loop's solve follows
+    // (no livo_h_share, whose caller reads them), from the loop's start, with
+    // NUM_MAX_ITERATIONS >= 2 and room for all its evaluations -- solve_scan then stops
+    // no scan before its second search -- and no debug output.  Block-uniform, from
+    // kernel parameters and the control block read above.
+    bool dead = false;
+#ifndef LIVO_EVAL_PROF
+    if constexpr (FIRST && kStatic) {
+        const IekfCtrl& c = slot->ctrl;
+        dead = P.rec_compact && E.h.solve && !E.h.dbg.normvec && !E.h.dbg.world && !E.h.dbg.sel &&
+               c.max_iter >= 2 && c.max_iter + 1 <= LIVO_MAX_EVALS && c.iter_count == -1 && c.rematch_num == 0 &&
+               c.n_evals == 0;
+    }
+#endif
     const PoseRef pose{slot->state.rot, slot->state.pos};
 #ifdef LIVO_EVAL_PROF
     const int tl_e = min(slot->ctrl.n_evals, LIVO_MAX_EVALS - 1);
@@ -3277,6 +3305,7 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
             float4 nb[kNN];
 #pragma unroll
             for (int k = 0; k < kNN; k++) nb[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            bool staged = false;  // lq_finish wrote this lane's half record to the stage
             if (valid) {
                 // candidates: grid positions (the runs, the cell walk); on the incremental map's runs
                 // positions in its base set rpts, or kRunPos | positions in its delta set dpts
@@ -3284,11 +3313,15 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
                 const int sflag = compact ? (int)kRecNoXyz : 0;
                 if (dyn)
                     amb = lq_finish<true, true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(walked ? P.gpts : P.rpts),
-                                          !certified, false, reinterpret_cast<const float4*>(P.dpts), nb, stage, sflag);
+                                          !certified, false, reinterpret_cast<const float4*>(P.dpts), nb, stage, sflag, false, 0.0f,
+                                          &staged);
                 else
                     amb = lq_finish<false, true>(q, P, job, bjob, i, reinterpret_cast<const float4*>(P.gpts), !certified,
-                                                 false, nullptr, nb, stage, sflag);
+                                                 false, nullptr, nb, stage, sflag, dead, E.h.max_sqd, &staged);
             }
+            // (wave-uniform) the wave's stage holds records: always, but for a wave of dead
+            // records in which no lane reads its own back (lq_finish decides, once)
+            const bool rec_live = __ballot(staged) != 0;
             {
                 // the wave's 64 half records leave as one coalesced run of 64-B pieces
                 // (the AoS record stores put each lane's 16 B in its own 128-B line: 64
@@ -3307,7 +3340,7 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
                         if (base + rec < job.n) dst[rec * 8 + half * 4 + part] = st[rec_stage_slot(rec, part)];
                     }
                 };
-                flush(0);
+                if (rec_live) flush(0);
                 if (!compact) {
                     float4 c[4];
                     rec_pack_cold(c, nb);

@@ -220,7 +220,9 @@ int livo_scan_release(livo_ctx* ctx, int32_t scan_id);
  * point from the last search on it (Nearest_Points, laser_mapping.h:165, in
  * Nearest_Search's ascending PointType_CMP order, ikd_Tree.cpp:350-380).
  * idx: N x 5 map indices (-1 pad); sqdist: N x 5 (+inf pad); either may be NULL.
- * LIVO_E_NOSCAN if the scan was never searched. */
+ * LIVO_E_NOSCAN if the scan was never searched, or if the last batched update
+ * on it failed with LIVO_E_HIP after some of its launches were queued (its
+ * records are then no single search's answer, see livo_iekf_update_batch). */
 int livo_scan_neighbors(livo_ctx* ctx, int32_t scan_id, int32_t* idx, float* sqdist);
 
 /* One h_share_model evaluation on a resident scan at the given state.
@@ -237,7 +239,12 @@ int livo_iekf_update(livo_ctx* ctx, int32_t scan_id, livo_state* state, const li
 
 /* n independent scan updates in one batched pass (states/priors/stats arrays of n).
  * The ids must be distinct (LIVO_E_INVALID otherwise): a scan's neighbour cache
- * belongs to one update at a time. */
+ * belongs to one update at a time.  An update that fails on the device side
+ * (LIVO_E_HIP from a launch, a copy or the wait for its end; submit / wait
+ * alike) leaves its scans without a neighbour cache, as if never searched:
+ * the first search of an update stores only the records that the update's
+ * second search does not rewrite.  An update refused before anything is
+ * queued (bad arguments, LIVO_E_BUSY) leaves the caches as they were. */
 int livo_iekf_update_batch(livo_ctx* ctx, int32_t n, const int32_t* scan_ids, livo_state* states,
                            const livo_state* priors, livo_iter_stats* stats);
 
