@@ -257,13 +257,21 @@ def ikfom_cov() -> np.ndarray:
     return np.diag(d)
 
 
-def make_ikfom_state(scan_id: int = 0, rot_deg: float = 1.0, trans_m: float = 0.1) -> dict:
+def make_ikfom_state(scan_id: int = 0, rot_deg: float = 1.0, trans_m: float = 0.1, offset_R=None, grav=None) -> dict:
     """state_ikfom of the same perturbed pose as make_state (identity extrinsic rotation,
-    offset_T = T_LI, gravity on the S2 of length 9.809)."""
+    offset_T = T_LI, gravity on the S2 of length 9.809).  offset_R: another extrinsic quaternion
+    (w, x, y, z); grav: another gravity vector, scaled to the S2 length if it is not on it."""
     st = make_state(scan_id, rot_deg, trans_m)
-    return {"pos": st["pos"], "rot": rot_to_quat(st["rot"]), "offset_R": np.array([1.0, 0.0, 0.0, 0.0]),
-            "offset_T": T_LI.copy(), "vel": np.zeros(3), "bg": np.zeros(3), "ba": np.zeros(3),
-            "grav": np.array([0.0, 0.0, -S2_LEN]), "cov": ikfom_cov()}
+    out = {"pos": st["pos"], "rot": rot_to_quat(st["rot"]), "offset_R": np.array([1.0, 0.0, 0.0, 0.0]),
+           "offset_T": T_LI.copy(), "vel": np.zeros(3), "bg": np.zeros(3), "ba": np.zeros(3),
+           "grav": np.array([0.0, 0.0, -S2_LEN]), "cov": ikfom_cov()}
+    if offset_R is not None:
+        q = np.asarray(offset_R, np.float64)
+        out["offset_R"] = q / np.linalg.norm(q)
+    if grav is not None:
+        g = np.asarray(grav, np.float64)
+        out["grav"] = g.copy() if np.linalg.norm(g) == S2_LEN else g / np.linalg.norm(g) * S2_LEN
+    return out
 
 
 _CACHE_DIR = os.environ.get("LIVO_SYNTH_CACHE", "/tmp/livo_synth_cache")

@@ -249,12 +249,22 @@ def test_mtk_A_matrix_is_left_jacobian():
     assert np.allclose(oracle.mtk(2, [0.0, 0.0, 0.0], [0.0]).reshape(3, 3), np.eye(3))
 
 
+def _tilted_state(scan_id):
+    """make_ikfom_state off its trivial points: offset_R 20 degrees about a skew axis, gravity in a
+    generic direction (all six S2_Bx entries non-zero); the state of tests/test_ikfom_reference.py."""
+    import ikfom_ref
+    from livo_amd import synth
+    return synth.make_ikfom_state(scan_id, offset_R=ikfom_ref.quat_about(ikfom_ref.TILT_AXIS, 20.0),
+                                  grav=ikfom_ref.grav_of("generic"))
+
+
 def test_mtk_s2_roundtrip_and_length():
+    import ikfom_ref
     import oracle
     from livo_amd import synth
     rng = np.random.default_rng(4)
-    for _ in range(20):
-        g = rng.normal(size=3)
+    gs = [rng.normal(size=3) for _ in range(20)] + [ikfom_ref.grav_of(k) for k in ("generic", "pole", "down")]
+    for g in gs:
         g = g / np.linalg.norm(g) * synth.S2_LEN
         d = rng.normal(size=2) * 0.3
         g2 = oracle.mtk(0, g, d)
@@ -265,9 +275,9 @@ def test_mtk_s2_roundtrip_and_length():
 def test_ikfom_state_boxplus_boxminus_roundtrip():
     import oracle
     from livo_amd import synth
-    st = synth.make_ikfom_state(2)
-    dx = np.random.default_rng(5).normal(size=23) * 0.05
-    assert np.allclose(oracle.mtk(3, st, dx), dx, rtol=0, atol=1e-12)
+    for st in (synth.make_ikfom_state(2), _tilted_state(2)):
+        dx = np.random.default_rng(5).normal(size=23) * 0.05
+        assert np.allclose(oracle.mtk(3, st, dx), dx, rtol=0, atol=1e-12)
 
 
 def _ikfom_dx0_numpy(tree, map_xyz, body, st, lpc=0.001):
@@ -275,8 +285,8 @@ def _ikfom_dx0_numpy(tree, map_xyz, body, st, lpc=0.001):
     dx = P_inv[:, :12] H^T h, information form), from the oracle's k-NN and plane fit."""
     import oracle
     from livo_amd import synth
-    R = synth.quat_to_rot(st["rot"])
-    pI = body.astype(np.float64) + st["offset_T"]
+    R, Ro = synth.quat_to_rot(st["rot"]), synth.quat_to_rot(st["offset_R"])
+    pI = body.astype(np.float64) @ Ro.T + st["offset_T"]
     world = (pI @ R.T + st["pos"]).astype(np.float32)
     idx, d, _ = tree.knn(world)
     rows, hs = [], []
@@ -288,12 +298,12 @@ def _ikfom_dx0_numpy(tree, map_xyz, body, st, lpc=0.001):
             continue
         pd2 = np.float32(pa[0] * world[i, 0] + pa[1] * world[i, 1] + pa[2] * world[i, 2] + pa[3])
         s = 1 - 0.9 * abs(float(pd2)) / math.sqrt(np.linalg.norm(body[i].astype(np.float64)))
-        if not (np.float32(s) > 0.9 and abs(float(pd2)) <= 2.0):
+        if not (float(np.float32(s)) > 0.9 and abs(float(pd2)) <= 2.0):
             continue
         n = pa[:3].astype(np.float64)
         C = R.T @ n
         A = _hat(pI[i]) @ C
-        B = _hat(body[i].astype(np.float64)) @ C   # offset_R = identity
+        B = _hat(body[i].astype(np.float64)) @ Ro.T @ C   # point_be_crossmat * offset_R.conjugate() * C
         rows.append(np.concatenate([n, A, B, C]))
         hs.append(-float(pd2))
     H, h = np.array(rows).reshape(-1, 12), np.array(hs)
@@ -311,6 +321,23 @@ def test_ikfom_first_update_matches_numpy(tree100k, map100k):
     dx, m = _ikfom_dx0_numpy(tree100k, map100k, body, st)
     assert stats["effct_feat_num"][0] == m
     assert np.linalg.norm(stats["dx"][0] - dx) <= 1e-8 * np.linalg.norm(dx)
+
+
+def test_ikfom_first_update_matches_numpy_tilted_extrinsic(tree100k, map100k):
+    """The same with offset_R 20 degrees about a skew axis and generic gravity: the world point and
+    the B row depend on offset_R and its conjugate.  The scan is the one a LiDAR mounted that way
+    sees (ikfom_ref.body_for), so it still lands on the map."""
+    import ikfom_ref
+    from livo_amd import synth
+    st = _tilted_state(7)
+    body = ikfom_ref.body_for(synth.make_scan(4000, 7)[0], st["offset_R"])
+    _, stats = tree100k.ikfom_update(body, st, max_iter=0)
+    dx, m = _ikfom_dx0_numpy(tree100k, map100k, body, st)
+    assert stats["effct_feat_num"][0] == m > 3000
+    assert np.linalg.norm(stats["dx"][0] - dx) <= 1e-8 * np.linalg.norm(dx)
+    B = np.array([_hat(b.astype(np.float64)) @ synth.quat_to_rot(st["offset_R"]) @ np.ones(3) for b in body[:50]])
+    Bc = np.array([_hat(b.astype(np.float64)) @ synth.quat_to_rot(st["offset_R"]).T @ np.ones(3) for b in body[:50]])
+    assert np.abs(B - Bc).max() > 1.0  # a missing conjugate is metres in the B rows, not rounding
 
 
 def test_ikfom_update_reduces_pose_error(tree100k):
