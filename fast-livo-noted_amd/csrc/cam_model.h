@@ -1,16 +1,19 @@
-// cam_model.h — the camera arithmetic shared by the VIO update (vio_kernels.hip),
-// the cloud colouring (rgb_kernels.hip) and the visual point selection
-// (vis_kernels.hip): the frame pose from a state, vikit's pinhole world2cam, one
-// point's colour as publish_frame_world_rgb computes it, and addSparseMap's
-// score, patch and voxel key.  Everything compiles for host and device (SEL_HD,
-// as ball_cells in livo_internal.h), so tests/native/rgb_point_check.cpp and
-// vis_point_check.cpp run the same code on the CPU.  Numerics as the kernels:
-// -ffp-contract=off, the reference's float / double expression order.
+// cam_model.h — the camera shared by the VIO update (vio_kernels.hip), the cloud
+// colouring (rgb_kernels.hip) and the visual point selection (vis_kernels.hip):
+// the intrinsics (CamIntrinsics) and the camera of one frame (FrameCam), each
+// filled in one place from the C ABI's structs (cam_intrinsics, frame_cam); the
+// frame pose from a state, vikit's pinhole world2cam, one point's colour as
+// publish_frame_world_rgb computes it, and addSparseMap's score, patch and voxel
+// key.  Everything compiles for host and device (SEL_HD, as ball_cells in
+// livo_internal.h), so tests/native/rgb_point_check.cpp and vis_point_check.cpp
+// run the same code on the CPU.  Numerics as the kernels: -ffp-contract=off, the
+// reference's float / double expression order.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
+#include "livo.h"
 #include "stl_select.h"  // SEL_HD
 
 namespace livo {
@@ -36,10 +39,35 @@ SEL_HD void cam_w2f(const double* Rcw, const double* Pcw, const double* pw, doub
         pf[k] = ((Rcw[k * 3 + 0] * pw[0] + Rcw[k * 3 + 1] * pw[1]) + Rcw[k * 3 + 2] * pw[2]) + Pcw[k];
 }
 
-// vikit PinholeCamera::world2cam(xyz_c), the distortion branch included.  Cam:
-// anything with fx, fy, cx, cy, d[5] and distortion (VioParams, RgbCam).
-template <class Cam>
-SEL_HD void vio_world2cam(const Cam& P, const double* xyz, double* px) {
+// A pinhole camera at an image size (vikit PinholeCamera).
+struct CamIntrinsics {
+    double fx, fy, cx, cy, d[5];
+    int32_t distortion;
+    int32_t w, h;
+};
+// The camera of one frame: the intrinsics and new_frame_->T_f_w_.
+struct FrameCam : CamIntrinsics {
+    double Rcw[9], Pcw[3];
+};
+
+SEL_HD CamIntrinsics cam_intrinsics(const livo_cam& cam, int32_t w, int32_t h) {
+    CamIntrinsics K;
+    K.fx = cam.fx; K.fy = cam.fy; K.cx = cam.cx; K.cy = cam.cy;
+    for (int k = 0; k < 5; k++) K.d[k] = cam.d[k];
+    K.distortion = fabs(cam.d[0]) > 0.0000001 ? 1 : 0;  // vikit: distortion_ = |d0| > 1e-7
+    K.w = w;
+    K.h = h;
+    return K;
+}
+// The camera of p (its cam at cam.width x cam.height, R_ci, P_ci) at a state.
+SEL_HD FrameCam frame_cam(const livo_vio_params& p, const livo_state& s) {
+    FrameCam C{cam_intrinsics(p.cam, p.cam.width, p.cam.height)};
+    cam_pose(p.R_ci, p.P_ci, s.rot, s.pos, C.Rcw, C.Pcw);
+    return C;
+}
+
+// vikit PinholeCamera::world2cam(xyz_c), the distortion branch included.
+SEL_HD void vio_world2cam(const CamIntrinsics& P, const double* xyz, double* px) {
     const double u = xyz[0] / xyz[2], v = xyz[1] / xyz[2];  // project2d
     if (!P.distortion) {
         px[0] = P.fx * u + P.cx;
@@ -55,14 +83,6 @@ SEL_HD void vio_world2cam(const Cam& P, const double* xyz, double* px) {
     px[0] = xd * P.fx + P.cx;
     px[1] = yd * P.fy + P.cy;
 }
-
-// The camera of one livo_cloud_colorize call.
-struct RgbCam {
-    double Rcw[9], Pcw[3];
-    double fx, fy, cx, cy, d[5];
-    int32_t distortion;  // vikit distortion_ = |d0| > 1e-7
-    int32_t w, h;
-};
 
 enum RgbFate : int { kRgbKept = 0, kRgbBehind = 1, kRgbOutOfFrame = 2 };
 
@@ -99,7 +119,7 @@ SEL_HD void rgb_span(const uint8_t* img, int64_t nbytes, int64_t o, float* I, bo
 // and [w - 1, w) read the neighbouring row as the reference does; taps outside
 // the buffer (undefined there) read 0 and set edge.  rgba: r | g << 8 | b << 16
 // | 255 << 24, the channels truncated as pointRGB.r = pixel[2] does.
-SEL_HD int rgb_point(const RgbCam& C, const uint8_t* img, float wx, float wy, float wz, uint32_t& rgba, bool& edge) {
+SEL_HD int rgb_point(const FrameCam& C, const uint8_t* img, float wx, float wy, float wz, uint32_t& rgba, bool& edge) {
     rgba = 0u;
     edge = false;
     const double pw[3] = {(double)wx, (double)wy, (double)wz};  // V3D p_w(p.x, p.y, p.z)
@@ -217,7 +237,7 @@ enum VisFate : int { kVisOutOfFrame = 0, kVisInFrame = 1, kVisOverflow = 2 };
 // (int)(pc.x / grid_size) * grid_n_height + (int)(pc.y / grid_size), which
 // aliases into the next column where height - border > grid_n_height * grid_size;
 // kVisOverflow: index >= length, the reference's out-of-bounds write.
-SEL_HD int vis_project(const RgbCam& C, const VisGrid& G, float wx, float wy, float wz, double* pc, bool& behind,
+SEL_HD int vis_project(const FrameCam& C, const VisGrid& G, float wx, float wy, float wz, double* pc, bool& behind,
                        int& index) {
     const double pw[3] = {(double)wx, (double)wy, (double)wz};  // V3D pt(p.x, p.y, p.z)
     double pf[3];

@@ -121,6 +121,33 @@ __device__ __forceinline__ void world_point(const double* R, const double* pos, 
     wy = (float)(((R[3] * ix + R[4] * iy) + R[5] * iz) + pos[1]);
     wz = (float)(((R[6] * ix + R[7] * iy) + R[8] * iz) + pos[2]);
 }
+// The world point of cloud index i (the caller's point order), exactly as
+// k_to_world stores it.
+__device__ __forceinline__ void cloud_world_point(const CloudSrc& S, const WorldParams& W, int i, float& wx, float& wy,
+                                                  float& wz) {
+    const int64_t k = S.iperm ? (int64_t)S.iperm[i] : (int64_t)i;
+    const float* p = S.src + S.stride * k;
+    world_point(W.rot, W.pos, W.R_LI, W.t_LI, p[0], p[1], p[2], wx, wy, wz);
+}
+
+// The block's count of each of K per-thread predicates, returned on thread k
+// for predicate k (0 on the other threads): a ballot and popcount per wave, an
+// LDS row per wave, one __syncthreads.  Every thread of a block of kWaves
+// whole waves calls it, once per kernel.  Integer counts: no order to keep.
+template <int kWaves, int K>
+__device__ __forceinline__ uint32_t block_tally(const bool (&pred)[K]) {
+    __shared__ uint32_t cnt[kWaves][K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const unsigned long long m = __ballot(pred[k]);
+        if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6][k] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    uint32_t v = 0;
+    if (threadIdx.x < K)
+        for (int w = 0; w < kWaves; w++) v += cnt[w][threadIdx.x];
+    return v;
+}
 
 // XCD-aware block order for a 1-D grid of nb blocks per scan: blocks are dealt
 // round-robin over the 8 XCDs, so give each XCD one contiguous run of (scan,

@@ -345,20 +345,21 @@ __global__ void k_fe_gather_seg(const float* __restrict__ pts, FeSegs S, const u
 // RGBpointBodyToWorld (laser_mapping.cpp:647-660) over laserCloudFullRes
 // (:258-265): p_w = rot (R_LI p_b + t_LI) + pos in double, stored as float;
 // intensity copied (column 3 of a 5-float source, 0 for a 4-float scan),
-// curvature 0 (a fresh PointType).  perm: source position -> output index.
-__global__ void k_to_world(const float* __restrict__ src, int64_t n, int stride, const int32_t* __restrict__ perm,
-                           WorldParams W, float* __restrict__ out5) {
+// curvature 0 (a fresh PointType).  Walks the cloud in stored order (coalesced
+// reads) and scatters through S.perm: stored position -> output index.
+__global__ void k_to_world(CloudSrc S, WorldParams W, float* __restrict__ out5) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const float* p = src + stride * k;
+    if (k >= S.n) return;
+    const float* p = S.src + S.stride * k;
     float wx, wy, wz;
     world_point(W.rot, W.pos, W.R_LI, W.t_LI, p[0], p[1], p[2], wx, wy, wz);
-    const int64_t o = perm ? (int64_t)perm[k] : k;
+    const float intensity = S.stride >= 5 ? p[3] : 0.0f;  // (read before the stores: S's pointers carry no __restrict__)
+    const int64_t o = S.perm ? (int64_t)S.perm[k] : k;
     float* q = out5 + 5 * o;
     q[0] = wx;
     q[1] = wy;
     q[2] = wz;
-    q[3] = stride >= 5 ? p[3] : 0.0f;
+    q[3] = intensity;
     q[4] = 0.0f;
 }
 
@@ -471,9 +472,8 @@ int launch_fe_gather_seg(const float* pts, const FeSegs& S, int n_scans, int64_t
                        (hipStream_t)stream, pts, S, sorted);
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
-int launch_to_world(const float* src, int64_t n, int stride, const int32_t* perm, const WorldParams& W, float* out5,
-                    void* stream) {
-    FE_LAUNCH(k_to_world, n, src, n, stride, perm, W, out5);
+int launch_to_world(const CloudSrc& S, const WorldParams& W, float* out5, void* stream) {
+    FE_LAUNCH(k_to_world, S.n, S, W, out5);
 }
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream) {
     FE_LAUNCH(k_ori_flags, n, sel, perm, n, flags);

@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "carve.h"
 #include "livo_internal.h"
 
 using namespace livo;
@@ -62,6 +63,36 @@ template <typename T>
 static void dev_free(T*& p) {
     if (p) (void)hipFree((void*)p);
     p = nullptr;
+}
+
+// A grow-only device buffer of `need` bytes: kept if it is large enough, else
+// freed and allocated again (its contents are not carried over).
+static int ensure_dev_bytes(void** p, size_t* have, size_t need) {
+    if (need <= *have) return LIVO_OK;
+    if (*p) (void)hipFree(*p);  // (the caller has drained the stream that used it)
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(p, need) != hipSuccess) return LIVO_E_OOM;
+    *have = need;
+    return LIVO_OK;
+}
+
+// An image kept on the device for the later calls that pass none (w = h = 0: none).
+struct DevImage {
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    int32_t w = 0, h = 0;
+};
+static bool image_reusable(const DevImage& m, int32_t w, int32_t h) { return m.p && m.w == w && m.h == h; }
+// Enqueues the upload of a host image.  There is no image to reuse from here on:
+// the caller sets w and h once its stream synchronise has succeeded.
+static int image_stage(DevImage& m, const uint8_t* host, size_t bytes, hipStream_t st) {
+    m.w = m.h = 0;
+    void* p = m.p;
+    const int rc = ensure_dev_bytes(&p, &m.cap, bytes);
+    m.p = (uint8_t*)p;
+    if (rc) return rc;
+    return hipMemcpyAsync(m.p, host, bytes, hipMemcpyHostToDevice, st) == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 
 static void free_scan_buf(ScanBuf& s) {
@@ -303,12 +334,8 @@ struct livo_ctx {
     int64_t fe_n = 0;
     void* vio_buf = nullptr;           // VIO frame (image, points, partials, slot)
     size_t vio_bytes = 0;
-    uint8_t* rgb_img = nullptr;        // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
-    size_t rgb_cap = 0;
-    int32_t rgb_w = 0, rgb_h = 0;      // its size (0: none)
-    uint8_t* vis_img = nullptr;        // livo_vio_select: the last uploaded gray image (reused by gray == NULL)
-    size_t vis_cap = 0;
-    int32_t vis_w = 0, vis_h = 0;      // its size (0: none)
+    DevImage bgr_img;                  // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
+    DevImage gray_img;                 // livo_vio_select: the last uploaded gray image (reused by gray == NULL)
     void* vis_buf = nullptr;           // ... and its cell table, flags, slots, counters, records and patches
     size_t vis_bytes = 0;
     void* prim_tmp = nullptr;          // rocPRIM scratch (sorts, scans)
@@ -425,13 +452,7 @@ static int set_device(livo_ctx* c) {
 }
 
 static int ensure_scratch(livo_ctx* c, size_t bytes) {
-    if (bytes <= c->scratch_bytes) return LIVO_OK;
-    if (c->scratch) (void)hipFree(c->scratch);
-    c->scratch = nullptr;
-    c->scratch_bytes = 0;
-    if (hipMalloc(&c->scratch, bytes) != hipSuccess) return LIVO_E_OOM;
-    c->scratch_bytes = bytes;
-    return LIVO_OK;
+    return ensure_dev_bytes(&c->scratch, &c->scratch_bytes, bytes);
 }
 
 // The single-scan entry points' slot and job (livo_knn, livo_h_share, livo_ivox_knn,
@@ -822,13 +843,7 @@ static int ivox_ensure_src(livo_ctx* c, int64_t n) {
 }
 
 static int ensure_prim(livo_ctx* c, size_t bytes) {
-    if (bytes <= c->prim_bytes) return LIVO_OK;
-    if (c->prim_tmp) (void)hipFree(c->prim_tmp);
-    c->prim_tmp = nullptr;
-    c->prim_bytes = 0;
-    if (hipMalloc(&c->prim_tmp, bytes) != hipSuccess) return LIVO_E_OOM;
-    c->prim_bytes = bytes;
-    return LIVO_OK;
+    return ensure_dev_bytes(&c->prim_tmp, &c->prim_bytes, bytes);
 }
 
 // Exclusive scan of n u32 through rocPRIM (out != in).
@@ -1919,8 +1934,8 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->fe_buf) (void)hipFree(c->fe_buf);
     if (c->prim_tmp) (void)hipFree(c->prim_tmp);
     if (c->vio_buf) (void)hipFree(c->vio_buf);
-    dev_free(c->rgb_img);
-    dev_free(c->vis_img);
+    dev_free(c->bgr_img.p);
+    dev_free(c->gray_img.p);
     if (c->vis_buf) (void)hipFree(c->vis_buf);
     dev_free(c->nodes);
     dev_free(c->lnodes);
@@ -2579,13 +2594,7 @@ static void release_scan_buf(livo_ctx* c, ScanBuf& s) {
 // (livo_scan_upload) the packed source points.
 static size_t up_tmp_bytes(int64_t N) { return (size_t)N * (4 + 4 + 4 + 4) + 256; }
 static int ensure_up_tmp(livo_ctx* c, size_t bytes) {
-    if (bytes <= c->up_tmp_bytes) return LIVO_OK;
-    if (c->up_tmp) (void)hipFree(c->up_tmp);  // (synchronous: no upload is in flight)
-    c->up_tmp = nullptr;
-    c->up_tmp_bytes = 0;
-    if (hipMalloc(&c->up_tmp, bytes) != hipSuccess) return LIVO_E_OOM;
-    c->up_tmp_bytes = bytes;
-    return LIVO_OK;
+    return ensure_dev_bytes(&c->up_tmp, &c->up_tmp_bytes, bytes);  // (synchronous: no upload is in flight)
 }
 
 // Where a scan is built: the stream, the sort scratch (keys, sorted keys, iota,
@@ -2597,15 +2606,6 @@ struct UpTarget {
     void** prim;
     size_t* prim_bytes;
 };
-static int ensure_dev_bytes(void** p, size_t* have, size_t need) {
-    if (need <= *have) return LIVO_OK;
-    if (*p) (void)hipFree(*p);  // (the caller has drained the stream that used it)
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, need) != hipSuccess) return LIVO_E_OOM;
-    *have = need;
-    return LIVO_OK;
-}
 
 // Morton-order N device points (x, y, z at d_src + stride * i floats) into the
 // scan buffers s on U.st: the same keys and stable order as a host sort.  Only
@@ -4049,39 +4049,31 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
     // one has been processed completely
     c->fe_raw = nullptr;
     c->fe_n = 0;
-    // scratch: raw 20n, poses, seg 2x4n, keys/iota/skeys/svals 4x4n, flags/vid 2x4n, starts 4(n+1), down 20n
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nb = (size_t)std::max<int64_t>(n, 1);
-    const size_t b_raw = al(nb * 20), b_pose = al((size_t)std::max(n_poses, 1) * 22 * 8), b4 = al(nb * 4),
-                 b_st = al((nb + 1) * 4);
-    const size_t total = b_raw + b_pose + 8 * b4 + b_st + b_raw + 256;
-    if (total > c->fe_bytes) {
-        if (c->fe_buf) (void)hipFree(c->fe_buf);
-        c->fe_buf = nullptr;
-        c->fe_bytes = 0;
-        if (hipMalloc(&c->fe_buf, total) != hipSuccess) return LIVO_E_OOM;
-        c->fe_bytes = total;
-    }
-    char* p = (char*)c->fe_buf;
     FrontParams F{};
-    F.raw = (float*)p; p += b_raw;
-    double* d_poses = (double*)p; p += b_pose;
-    int32_t* seg = (int32_t*)p; p += b4;
-    F.seg = seg;
-    F.seg_rev = (int32_t*)p; p += b4;
-    F.keys = (uint32_t*)p; p += b4;
-    F.iota = (uint32_t*)p; p += b4;
-    uint32_t* skeys = (uint32_t*)p; p += b4;
-    uint32_t* svals = (uint32_t*)p; p += b4;
-    F.flags = (uint32_t*)p; p += b4;
-    F.vid = (uint32_t*)p; p += b4;
-    F.starts = (uint32_t*)p; p += b_st;
-    F.down = (float*)p; p += b_raw;
-    unsigned* mm = (unsigned*)p;
-    F.skeys = skeys;
-    F.svals = svals;
+    double* d_poses;
+    int32_t* seg;
+    uint32_t *skeys, *svals;
+    unsigned* mm;  // the bounds (launch_fe_minmax)
+    const size_t nb = (size_t)std::max<int64_t>(n, 1);
+    auto layout = [&](Carve k) {
+        F.raw = k.take<float>(nb * 5);
+        F.poses = d_poses = k.take<double>((size_t)std::max(n_poses, 1) * 22);
+        F.seg = seg = k.take<int32_t>(nb);
+        F.seg_rev = k.take<int32_t>(nb);
+        F.keys = k.take<uint32_t>(nb);
+        F.iota = k.take<uint32_t>(nb);
+        F.skeys = skeys = k.take<uint32_t>(nb);
+        F.svals = svals = k.take<uint32_t>(nb);
+        F.flags = k.take<uint32_t>(nb);
+        F.vid = k.take<uint32_t>(nb);
+        F.starts = k.take<uint32_t>(nb + 1);
+        F.down = k.take<float>(nb * 5);
+        mm = k.take<unsigned>(6);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&c->fe_buf, &c->fe_bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)c->fe_buf});
     F.n = n;
-    F.poses = d_poses;
     F.np = n_poses;
     std::memcpy(F.R_LI, c->params.R_LI, sizeof(F.R_LI));
     std::memcpy(F.t_LI, c->params.t_LI, sizeof(F.t_LI));
@@ -4223,28 +4215,24 @@ int livo_vio_update(livo_ctx* c, const livo_vio_params* p, const uint8_t* image,
     if (set_device(c)) return LIVO_E_HIP;
     const int pst = p->patch_size * p->patch_size;
     const int nblk = (int)std::max<int64_t>(1, (n + 255) / 256);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_img = al((size_t)width * height), b_pos = al((size_t)std::max<int64_t>(n, 1) * 24),
-                 b_lev = al((size_t)std::max<int64_t>(n, 1) * 4),
-                 b_pat = al((size_t)std::max<int64_t>(n, 1) * 3 * pst * 4),
-                 b_par = al((size_t)nblk * kVioCols * 8), b_err = al((size_t)std::max<int64_t>(n, 1) * 4),
-                 b_slot = al(sizeof(VioSlot));
-    const size_t total = b_img + b_pos + b_lev + b_pat + b_par + b_err + b_slot;
-    if (total > c->vio_bytes) {
-        if (c->vio_buf) (void)hipFree(c->vio_buf);
-        c->vio_buf = nullptr;
-        c->vio_bytes = 0;
-        if (hipMalloc(&c->vio_buf, total) != hipSuccess) return LIVO_E_OOM;
-        c->vio_bytes = total;
-    }
-    char* q = (char*)c->vio_buf;
-    uint8_t* d_img = (uint8_t*)q; q += b_img;
-    double* d_pos = (double*)q; q += b_pos;
-    int32_t* d_lev = (int32_t*)q; q += b_lev;
-    float* d_pat = (float*)q; q += b_pat;
-    double* d_par = (double*)q; q += b_par;
-    float* d_err = (float*)q; q += b_err;
-    VioSlot* d_slot = (VioSlot*)q;
+    uint8_t* d_img;
+    double *d_pos, *d_par;
+    int32_t* d_lev;
+    float *d_pat, *d_err;
+    VioSlot* d_slot;
+    const size_t nb = (size_t)std::max<int64_t>(n, 1);
+    auto layout = [&](Carve k) {
+        d_img = k.take<uint8_t>((size_t)width * height);
+        d_pos = k.take<double>(nb * 3);
+        d_lev = k.take<int32_t>(nb);
+        d_pat = k.take<float>(nb * 3 * pst);
+        d_par = k.take<double>((size_t)nblk * kVioCols);
+        d_err = k.take<float>(nb);
+        d_slot = k.take<VioSlot>(1);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&c->vio_buf, &c->vio_bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)c->vio_buf});
     VioSlot hs;
     std::memset(&hs, 0, sizeof(hs));
     hs.state = *state;
@@ -4259,11 +4247,7 @@ int livo_vio_update(livo_ctx* c, const livo_vio_params* p, const uint8_t* image,
     if (n > 0) HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)n * 4, c->stream));  // errors: 0 until an iteration runs
     VioParams P{};
     P.img = d_img;
-    P.w = width;
-    P.h = height;
-    P.fx = p->cam.fx; P.fy = p->cam.fy; P.cx = p->cam.cx; P.cy = p->cam.cy;
-    std::memcpy(P.d, p->cam.d, sizeof(P.d));
-    P.distortion = std::fabs(p->cam.d[0]) > 0.0000001 ? 1 : 0;  // vikit: distortion_ = |d0| > 1e-7
+    P.cam = cam_intrinsics(p->cam, width, height);
     P.n = (int32_t)n;
     P.ps = p->patch_size;
     P.pos = d_pos;
@@ -4416,38 +4400,50 @@ int livo_map_last_add_stats(livo_ctx* c, livo_map_add_stats* out) {
     return LIVO_OK;
 }
 
+// The cloud of the frame stages: the last preprocessed frame at full resolution
+// (scan_id < 0; n = 0 while there is none) or a resident scan, with the
+// permutations between its stored order and the caller's point order.
+static int frame_cloud(livo_ctx* c, int32_t scan_id, CloudSrc* S) {
+    *S = CloudSrc{};
+    if (scan_id < 0) {
+        S->src = c->fe_raw;
+        S->n = c->fe_raw ? c->fe_n : 0;
+        S->stride = 5;
+        return LIVO_OK;
+    }
+    ScanBuf* s = get_scan(c, scan_id);
+    if (!s) return LIVO_E_NOSCAN;
+    S->src = s->pts;
+    S->perm = s->d_perm;
+    S->iperm = s->d_iperm;
+    S->n = s->n;
+    S->stride = 4;
+    return LIVO_OK;
+}
+
+static WorldParams world_params(const livo_ctx* c, const livo_state& state) {
+    WorldParams W;
+    std::memcpy(W.rot, state.rot, sizeof(W.rot));
+    std::memcpy(W.pos, state.pos, sizeof(W.pos));
+    std::memcpy(W.R_LI, c->params.R_LI, sizeof(W.R_LI));
+    std::memcpy(W.t_LI, c->params.t_LI, sizeof(W.t_LI));
+    return W;
+}
+
 int livo_frame_to_world(livo_ctx* c, int32_t scan_id, const livo_state* state, livo_raw_point* out, int64_t cap,
                         int64_t* n_out) {
     if (!c || !state || !n_out) return LIVO_E_INVALID;
-    const float* src;
-    int64_t n;
-    int stride;
-    const int32_t* perm = nullptr;
-    if (scan_id < 0) {
-        src = c->fe_raw;
-        n = c->fe_raw ? c->fe_n : 0;
-        stride = 5;
-    } else {
-        ScanBuf* s = get_scan(c, scan_id);
-        if (!s) return LIVO_E_NOSCAN;
-        src = s->pts;
-        n = s->n;
-        stride = 4;
-        perm = s->d_perm;
-    }
+    CloudSrc S;
+    RC_TRY(frame_cloud(c, scan_id, &S));
+    const int64_t n = S.n;
     *n_out = n;
     if (!out || n == 0) return LIVO_OK;
     if (cap < n) return LIVO_E_RANGE;
     if (set_device(c)) return LIVO_E_HIP;
-    WorldParams W;
-    std::memcpy(W.rot, state->rot, sizeof(W.rot));
-    std::memcpy(W.pos, state->pos, sizeof(W.pos));
-    std::memcpy(W.R_LI, c->params.R_LI, sizeof(W.R_LI));
-    std::memcpy(W.t_LI, c->params.t_LI, sizeof(W.t_LI));
     int rc = ensure_scratch(c, (size_t)n * 5 * sizeof(float));
     if (rc) return rc;
     float* d_out = (float*)c->scratch;
-    rc = launch_to_world(src, n, stride, perm, W, d_out, c->stream);
+    rc = launch_to_world(S, world_params(c, *state), d_out, c->stream);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4459,64 +4455,35 @@ int livo_cloud_colorize(livo_ctx* c, int32_t scan_id, const livo_state* state, c
                         int64_t cap, int64_t* n_out, livo_rgb_stats* stats) {
     if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
     if (width <= 0 || height <= 0 || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
-    if (!bgr && (!c->rgb_img || c->rgb_w != width || c->rgb_h != height)) return LIVO_E_INVALID;
-    // the source cloud, as livo_frame_to_world selects it
+    if (!bgr && !image_reusable(c->bgr_img, width, height)) return LIVO_E_INVALID;
     RgbParams R{};
-    int64_t n;
-    if (scan_id < 0) {
-        R.src = c->fe_raw;
-        n = c->fe_raw ? c->fe_n : 0;
-        R.stride = 5;
-    } else {
-        ScanBuf* s = get_scan(c, scan_id);
-        if (!s) return LIVO_E_NOSCAN;
-        R.src = s->pts;
-        n = s->n;
-        R.stride = 4;
-        R.iperm = s->d_iperm;  // the caller's point order
-    }
+    RC_TRY(frame_cloud(c, scan_id, &R.cloud));  // in the caller's point order (iperm)
+    const int64_t n = R.cloud.n;
     if (n > (int64_t)0x7FFFFFFF - kRgbBlock) return LIVO_E_RANGE;
     if (set_device(c)) return LIVO_E_HIP;
-    const size_t img_bytes = (size_t)3 * (size_t)width * (size_t)height;
-    if (bgr) {
-        c->rgb_w = c->rgb_h = 0;  // (no image to reuse if the upload fails)
-        if (img_bytes > c->rgb_cap) {
-            dev_free(c->rgb_img);
-            c->rgb_cap = 0;
-            if (dev_alloc(&c->rgb_img, img_bytes)) return LIVO_E_OOM;
-            c->rgb_cap = img_bytes;
-        }
-        HIP_TRY(hipMemcpyAsync(c->rgb_img, bgr, img_bytes, hipMemcpyHostToDevice, c->stream));
-    }
+    if (bgr) RC_TRY(image_stage(c->bgr_img, bgr, (size_t)3 * (size_t)width * (size_t)height, c->stream));
     unsigned long long ctr[kRgbCtrN] = {0, 0, 0, 0};
     if (n > 0) {
         const bool compact = out || src_index;
         const int64_t nblk = (n + kRgbBlock - 1) / kRgbBlock;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t b_rec = al((size_t)n * sizeof(livo_rgb_point)), b_idx = al((size_t)n * 4), b_keep = al((size_t)n),
-                     b_blk = al((size_t)nblk * 4), b_ctr = al(sizeof(ctr));
-        RC_TRY(ensure_scratch(c, 2 * b_rec + b_idx + b_keep + 2 * b_blk + b_ctr));
-        char* q = (char*)c->scratch;
-        R.rec = (livo_rgb_point*)q; q += b_rec;
-        livo_rgb_point* d_out = (livo_rgb_point*)q; q += b_rec;
-        int32_t* d_idx = (int32_t*)q; q += b_idx;
-        R.keep = (uint8_t*)q; q += b_keep;
-        R.blk_cnt = (uint32_t*)q; q += b_blk;
-        uint32_t* d_off = (uint32_t*)q; q += b_blk;
-        R.blk_off = d_off;
-        R.ctr = (unsigned long long*)q;
-        R.n = (int32_t)n;
-        std::memcpy(R.W.rot, state->rot, sizeof(R.W.rot));
-        std::memcpy(R.W.pos, state->pos, sizeof(R.W.pos));
-        std::memcpy(R.W.R_LI, c->params.R_LI, sizeof(R.W.R_LI));
-        std::memcpy(R.W.t_LI, c->params.t_LI, sizeof(R.W.t_LI));
-        cam_pose(p->R_ci, p->P_ci, state->rot, state->pos, R.cam.Rcw, R.cam.Pcw);  // once per call
-        R.cam.fx = p->cam.fx; R.cam.fy = p->cam.fy; R.cam.cx = p->cam.cx; R.cam.cy = p->cam.cy;
-        std::memcpy(R.cam.d, p->cam.d, sizeof(R.cam.d));
-        R.cam.distortion = std::fabs(p->cam.d[0]) > 0.0000001 ? 1 : 0;  // vikit: distortion_ = |d0| > 1e-7
-        R.cam.w = width;
-        R.cam.h = height;
-        R.img = c->rgb_img;
+        livo_rgb_point* d_out;
+        int32_t* d_idx;
+        uint32_t* d_off;
+        auto layout = [&](Carve k) {
+            R.rec = k.take<livo_rgb_point>((size_t)n);
+            d_out = k.take<livo_rgb_point>((size_t)n);
+            d_idx = k.take<int32_t>((size_t)n);
+            R.keep = k.take<uint8_t>((size_t)n);
+            R.blk_cnt = k.take<uint32_t>((size_t)nblk);
+            R.blk_off = d_off = k.take<uint32_t>((size_t)nblk);
+            R.ctr = k.take<unsigned long long>(kRgbCtrN);
+            return k.total();
+        };
+        RC_TRY(ensure_scratch(c, layout(Carve{nullptr})));
+        layout(Carve{(char*)c->scratch});
+        R.W = world_params(c, *state);
+        R.cam = frame_cam(*p, *state);  // once per call
+        R.img = c->bgr_img.p;
         R.out = out ? d_out : nullptr;
         R.src_index = src_index ? d_idx : nullptr;
         HIP_TRY(hipMemsetAsync(R.ctr, 0, sizeof(ctr), c->stream));
@@ -4528,9 +4495,9 @@ int livo_cloud_colorize(livo_ctx* c, int32_t scan_id, const livo_state* state, c
         HIP_TRY(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (bgr) {
-        c->rgb_w = width;
-        c->rgb_h = height;
+    if (bgr) {  // the upload is done: later calls may reuse it
+        c->bgr_img.w = width;
+        c->bgr_img.h = height;
     }
     const int64_t kept = (int64_t)ctr[kRgbCtrKept];
     *n_out = kept;
@@ -4570,69 +4537,31 @@ int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const
     const int64_t length = (int64_t)(width / grid_size) * V.grid.grid_n_height;
     if (length > (int64_t)0x7FFFFFFF - kVisBlock) return LIVO_E_RANGE;
     V.grid.length = (int32_t)length;
-    if (!gray && (!c->vis_img || c->vis_w != width || c->vis_h != height)) return LIVO_E_INVALID;
-    // the source cloud, as livo_frame_to_world selects it
-    int64_t n;
-    if (scan_id < 0) {
-        V.src = c->fe_raw;
-        n = c->fe_raw ? c->fe_n : 0;
-        V.stride = 5;
-    } else {
-        ScanBuf* s = get_scan(c, scan_id);
-        if (!s) return LIVO_E_NOSCAN;
-        V.src = s->pts;
-        n = s->n;
-        V.stride = 4;
-        V.iperm = s->d_iperm;  // the caller's point order
-    }
+    if (!gray && !image_reusable(c->gray_img, width, height)) return LIVO_E_INVALID;
+    RC_TRY(frame_cloud(c, scan_id, &V.cloud));  // in the caller's point order (iperm)
+    const int64_t n = V.cloud.n;
     if (n > (int64_t)0x7FFFFFFF - kVisBlock) return LIVO_E_RANGE;
     if (set_device(c)) return LIVO_E_HIP;
-    const size_t img_bytes = (size_t)width * (size_t)height;
-    if (gray) {
-        c->vis_w = c->vis_h = 0;  // (no image to reuse if the upload fails)
-        if (img_bytes > c->vis_cap) {
-            dev_free(c->vis_img);
-            c->vis_cap = 0;
-            if (dev_alloc(&c->vis_img, img_bytes)) return LIVO_E_OOM;
-            c->vis_cap = img_bytes;
-        }
-        HIP_TRY(hipMemcpyAsync(c->vis_img, gray, img_bytes, hipMemcpyHostToDevice, c->stream));
-    }
+    if (gray) RC_TRY(image_stage(c->gray_img, gray, (size_t)width * (size_t)height, c->stream));
     const int pst3 = 3 * p->patch_size * p->patch_size;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_tab = al((size_t)length * 8), b_u32 = al((size_t)length * 4), b_ctr = al(kVisCtrN * 8),
-                 b_rec = al((size_t)length * sizeof(livo_vis_point)), b_pat = al((size_t)length * pst3 * 4);
-    const size_t total = b_tab + b_ctr + 2 * b_u32 + b_rec + b_pat;
-    if (total > c->vis_bytes) {
-        if (c->vis_buf) (void)hipFree(c->vis_buf);
-        c->vis_buf = nullptr;
-        c->vis_bytes = 0;
-        if (hipMalloc(&c->vis_buf, total) != hipSuccess) return LIVO_E_OOM;
-        c->vis_bytes = total;
-    }
-    char* q = (char*)c->vis_buf;
-    V.table = (unsigned long long*)q; q += b_tab;
-    V.ctr = (unsigned long long*)q; q += b_ctr;  // (behind the table: one clear for both)
-    V.flag = (uint32_t*)q; q += b_u32;
-    uint32_t* d_slot = (uint32_t*)q; q += b_u32;
-    V.slot = d_slot;
-    V.out = (livo_vis_point*)q; q += b_rec;
-    V.patches = (float*)q;
-    V.n = (int32_t)n;
-    std::memcpy(V.W.rot, state->rot, sizeof(V.W.rot));
-    std::memcpy(V.W.pos, state->pos, sizeof(V.W.pos));
-    std::memcpy(V.W.R_LI, c->params.R_LI, sizeof(V.W.R_LI));
-    std::memcpy(V.W.t_LI, c->params.t_LI, sizeof(V.W.t_LI));
-    cam_pose(p->R_ci, p->P_ci, state->rot, state->pos, V.cam.Rcw, V.cam.Pcw);  // once per call
-    V.cam.fx = p->cam.fx; V.cam.fy = p->cam.fy; V.cam.cx = p->cam.cx; V.cam.cy = p->cam.cy;
-    std::memcpy(V.cam.d, p->cam.d, sizeof(V.cam.d));
-    V.cam.distortion = std::fabs(p->cam.d[0]) > 0.0000001 ? 1 : 0;  // vikit: distortion_ = |d0| > 1e-7
-    V.cam.w = width;
-    V.cam.h = height;
-    V.img = c->vis_img;
+    uint32_t* d_slot;
+    auto layout = [&](Carve k) {
+        V.table = k.take<unsigned long long>((size_t)length);
+        V.ctr = k.take<unsigned long long>(kVisCtrN);  // (behind the table: one clear for both)
+        V.flag = k.take<uint32_t>((size_t)length);
+        V.slot = d_slot = k.take<uint32_t>((size_t)length);
+        V.out = k.take<livo_vis_point>((size_t)length);
+        V.patches = k.take<float>((size_t)length * pst3);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&c->vis_buf, &c->vis_bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)c->vis_buf});
+    V.W = world_params(c, *state);
+    V.cam = frame_cam(*p, *state);  // once per call
+    V.img = c->gray_img.p;
     unsigned long long ctr[kVisCtrN] = {0, 0, 0, 0};
     if (n > 0) {
-        HIP_TRY(hipMemsetAsync(V.table, 0, b_tab + b_ctr, c->stream));
+        HIP_TRY(hipMemsetAsync(V.table, 0, (size_t)((char*)(V.ctr + kVisCtrN) - (char*)V.table), c->stream));
         RC_TRY(launch_vis_score(V, c->stream));
         RC_TRY(launch_vis_flags(V, c->stream));
         if (out) {  // (the table bounds the result: the records are written before their count is known)
@@ -4642,9 +4571,9 @@ int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const
         HIP_TRY(hipMemcpyAsync(ctr, V.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (gray) {
-        c->vis_w = width;
-        c->vis_h = height;
+    if (gray) {  // the upload is done: later calls may reuse it
+        c->gray_img.w = width;
+        c->gray_img.h = height;
     }
     const int64_t sel = (int64_t)ctr[kVisCtrOut];
     *n_out = sel;

@@ -584,20 +584,25 @@ int launch_fe_gather(const float* pts, int64_t n, int stride, const uint32_t* pe
 struct WorldParams {
     double rot[9], pos[3], R_LI[9], t_LI[3];
 };
-// RGBpointBodyToWorld of n points (stride floats each, x y z [intensity]) -> n x 5 floats.
-int launch_to_world(const float* src, int64_t n, int stride, const int32_t* perm, const WorldParams& W, float* out5,
-                    void* stream);
+// The cloud of a frame stage: the last preprocessed frame or a resident scan.
+struct CloudSrc {
+    const float* src;      // n points, stride floats each (x, y, z, ...), stored order
+    const int32_t* perm;   // stored position -> cloud index (null: the same)
+    const int32_t* iperm;  // cloud index -> stored position (null: the same)
+    int64_t n;
+    int32_t stride;
+};
+// RGBpointBodyToWorld of the cloud (x y z [intensity]) -> n x 5 floats, cloud order.
+int launch_to_world(const CloudSrc& S, const WorldParams& W, float* out5, void* stream);
 // publish_frame_world_rgb (rgb_kernels.hip): the cloud of launch_to_world,
 // projected into the camera frame and coloured from the BGR image, the kept
 // points compacted in the cloud's order.
 constexpr int kRgbBlock = 256;
 enum { kRgbCtrBehind = 0, kRgbCtrOutOfFrame = 1, kRgbCtrEdge = 2, kRgbCtrKept = 3, kRgbCtrN = 4 };
 struct RgbParams {
-    const float* src;         // n points, stride floats each (x, y, z, ...), stored order
-    const int32_t* iperm;     // cloud index -> stored position (null: the same)
-    int32_t n, stride;
+    CloudSrc cloud;           // n < 2^31 - kRgbBlock
     WorldParams W;
-    RgbCam cam;
+    FrameCam cam;
     const uint8_t* img;       // 3 * cam.w * cam.h bytes, B G R interleaved
     livo_rgb_point* rec;      // n: every point's record, cloud order
     uint8_t* keep;            // n: 1 kept
@@ -615,11 +620,9 @@ int launch_rgb_scatter(const RgbParams& p, void* stream);
 constexpr int kVisBlock = 256;
 enum { kVisCtrInFrame = 0, kVisCtrBehind = 1, kVisCtrOverflow = 2, kVisCtrOut = 3, kVisCtrN = 4 };
 struct VisParams {
-    const float* src;         // n points, stride floats each (x, y, z, ...), stored order
-    const int32_t* iperm;     // cloud index -> stored position (null: the same)
-    int32_t n, stride;
+    CloudSrc cloud;           // n < 2^31 - kVisBlock
     WorldParams W;
-    RgbCam cam;
+    FrameCam cam;
     VisGrid grid;
     const uint8_t* img;       // cam.w * cam.h bytes, gray
     unsigned long long* table;  // grid.length cell winners: score bits << 32 | ~cloud index; 0: empty
@@ -668,10 +671,8 @@ struct alignas(16) VioSlot {
 };
 constexpr int kVioCols = 28;  // per-block partial: 21 HTH upper-tri + 6 HTz (+ 1 spare)
 struct VioParams {
-    const uint8_t* img;
-    int32_t w, h;
-    double fx, fy, cx, cy, d[5];
-    int32_t distortion;     // vikit distortion_ = |d0| > 1e-7
+    const uint8_t* img;     // cam.w * cam.h bytes, gray
+    CamIntrinsics cam;
     int32_t n, ps;
     const double* pos;      // n x 3
     const int32_t* levels;  // n

@@ -2,12 +2,13 @@
 // LaserMapping::publish_frame_world_rgb, src/laser_mapping.cpp:1351-1381.
 //
 //   k_rgb_points   one cloud point per thread, in the cloud's order: the world
-//                  point exactly as k_to_world stores it (world_point), then
-//                  rgb_point (cam_model.h): camera frame, p_cam.z > 0, pinhole
-//                  projection, isInFrame, getpixel.  Stores the 16-B record and
-//                  the keep flag, the block's kept count, and adds the block's
-//                  drop / edge / kept counts to the call's counters (integer
-//                  adds: the sums do not depend on their order).
+//                  point exactly as k_to_world stores it (cloud_world_point,
+//                  device_common.h), then rgb_point (cam_model.h): camera
+//                  frame, p_cam.z > 0, pinhole projection, isInFrame, getpixel.
+//                  Stores the 16-B record and the keep flag, the block's kept
+//                  count, and adds the block's drop / edge / kept counts
+//                  (block_tally) to the call's counters (integer adds: the
+//                  sums do not depend on their order).
 //   k_rgb_scatter  behind an exclusive scan of the blocks' counts: a kept
 //                  point's place is its block's offset + the kept points of
 //                  the waves before its own + those of the lanes before it
@@ -34,33 +35,21 @@ __device__ __forceinline__ int lanes_below(unsigned long long m) {
 
 __global__ __launch_bounds__(kRgbBlock) void k_rgb_points(RgbParams P) {
     const int i = blockIdx.x * kRgbBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int fate = -1;  // (no point)
     bool edge = false;
-    if (i < P.n) {
-        const int64_t k = P.iperm ? (int64_t)P.iperm[i] : (int64_t)i;
-        const float* p = P.src + P.stride * k;
+    if (i < (int)P.cloud.n) {
         float wx, wy, wz;
-        world_point(P.W.rot, P.W.pos, P.W.R_LI, P.W.t_LI, p[0], p[1], p[2], wx, wy, wz);
+        cloud_world_point(P.cloud, P.W, i, wx, wy, wz);
         uint32_t rgba;
         fate = rgb_point(P.cam, P.img, wx, wy, wz, rgba, edge);
         if (fate == kRgbKept)
             reinterpret_cast<float4*>(P.rec)[i] = make_float4(wx, wy, wz, __uint_as_float(rgba));
         P.keep[i] = fate == kRgbKept ? 1 : 0;
     }
-    __shared__ uint32_t cnt[kRgbWaves][kRgbCtrN];
-    const unsigned long long mk = __ballot(fate == kRgbKept), mb = __ballot(fate == kRgbBehind),
-                             mo = __ballot(fate == kRgbOutOfFrame), me = __ballot(edge);
-    if (lane == 0) {
-        cnt[w][kRgbCtrBehind] = (uint32_t)__popcll(mb);
-        cnt[w][kRgbCtrOutOfFrame] = (uint32_t)__popcll(mo);
-        cnt[w][kRgbCtrEdge] = (uint32_t)__popcll(me);
-        cnt[w][kRgbCtrKept] = (uint32_t)__popcll(mk);
-    }
-    __syncthreads();
+    static_assert(kRgbCtrBehind == 0 && kRgbCtrOutOfFrame == 1 && kRgbCtrEdge == 2 && kRgbCtrKept == 3, "the order");
+    const bool pred[kRgbCtrN] = {fate == kRgbBehind, fate == kRgbOutOfFrame, edge, fate == kRgbKept};
+    const uint32_t v = block_tally<kRgbWaves>(pred);
     if (threadIdx.x < kRgbCtrN) {
-        uint32_t v = 0;
-        for (int ww = 0; ww < kRgbWaves; ww++) v += cnt[ww][threadIdx.x];
         if (threadIdx.x == kRgbCtrKept) P.blk_cnt[blockIdx.x] = v;
         if (v) atomicAdd(P.ctr + threadIdx.x, (unsigned long long)v);
     }
@@ -69,7 +58,7 @@ __global__ __launch_bounds__(kRgbBlock) void k_rgb_points(RgbParams P) {
 __global__ __launch_bounds__(kRgbBlock) void k_rgb_scatter(RgbParams P) {
     const int i = blockIdx.x * kRgbBlock + threadIdx.x;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const bool kept = i < P.n && P.keep[i] != 0;
+    const bool kept = i < (int)P.cloud.n && P.keep[i] != 0;
     __shared__ uint32_t wcnt[kRgbWaves];
     const unsigned long long mk = __ballot(kept);
     if (lane == 0) wcnt[w] = (uint32_t)__popcll(mk);
@@ -81,16 +70,16 @@ __global__ __launch_bounds__(kRgbBlock) void k_rgb_scatter(RgbParams P) {
     if (P.src_index) P.src_index[pos] = i;
 }
 
-static inline unsigned rgb_blocks(int32_t n) { return (unsigned)((n + kRgbBlock - 1) / kRgbBlock); }
+static inline unsigned rgb_blocks(int64_t n) { return (unsigned)((n + kRgbBlock - 1) / kRgbBlock); }
 
 int launch_rgb_points(const RgbParams& p, void* stream) {
-    if (p.n <= 0) return LIVO_OK;
-    hipLaunchKernelGGL(k_rgb_points, dim3(rgb_blocks(p.n)), dim3(kRgbBlock), 0, (hipStream_t)stream, p);
+    if (p.cloud.n <= 0) return LIVO_OK;
+    hipLaunchKernelGGL(k_rgb_points, dim3(rgb_blocks(p.cloud.n)), dim3(kRgbBlock), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 int launch_rgb_scatter(const RgbParams& p, void* stream) {
-    if (p.n <= 0) return LIVO_OK;
-    hipLaunchKernelGGL(k_rgb_scatter, dim3(rgb_blocks(p.n)), dim3(kRgbBlock), 0, (hipStream_t)stream, p);
+    if (p.cloud.n <= 0) return LIVO_OK;
+    hipLaunchKernelGGL(k_rgb_scatter, dim3(rgb_blocks(p.cloud.n)), dim3(kRgbBlock), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 

@@ -234,7 +234,8 @@ __global__ __launch_bounds__(256) void k_vio_iter(VioParams P) {
     if (slot->ctrl.end) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = blockIdx.x * 256 + tid;
-    const int level = P.level, ps = P.ps, pst = ps * ps, ph = ps / 2, width = P.w;
+    const CamIntrinsics& K = P.cam;
+    const int level = P.level, ps = P.ps, pst = ps * ps, ph = ps / 2, width = K.w;
     double acc[27];
 #pragma unroll
     for (int k = 0; k < 27; k++) acc[k] = 0.0;
@@ -243,9 +244,9 @@ __global__ __launch_bounds__(256) void k_vio_iter(VioParams P) {
         double Rcw[9], Pcw[3], pf[3], pc[2];
         cam_pose(P.Rci, P.Pci, st.rot, st.pos, Rcw, Pcw);  // Rcw = Jdp_dt
         cam_w2f(Rcw, Pcw, P.pos + 3 * (size_t)i, pf);
-        vio_world2cam(P, pf, pc);
+        vio_world2cam(K, pf, pc);
         const double zi = 1. / pf[2], zi2 = zi * zi;
-        const double Jdpi[6] = {P.fx * zi, 0.0, -P.fx * pf[0] * zi2, 0.0, P.fy * zi, -P.fy * pf[1] * zi2};
+        const double Jdpi[6] = {K.fx * zi, 0.0, -K.fx * pf[0] * zi2, 0.0, K.fy * zi, -K.fy * pf[1] * zi2};
         const double p_hat[9] = {0.0, -pf[2], pf[1], pf[2], 0.0, -pf[0], -pf[1], pf[0], 0.0};
         const int scale = 1 << (level + P.levels[i]);
         const float u_ref = (float)pc[0], v_ref = (float)pc[1];
@@ -261,11 +262,11 @@ __global__ __launch_bounds__(256) void k_vio_iter(VioParams P) {
             for (int y = 0; y < ps; ++y) {
                 const int col0 = u_ref_i - ph * scale + y * scale;
                 const int s = scale;
-                oof += (row0 - s < 0 || row0 + 2 * s >= P.h || col0 - s < 0 || col0 + 2 * s >= P.w) ? 1u : 0u;
+                oof += (row0 - s < 0 || row0 + 2 * s >= K.h || col0 - s < 0 || col0 + 2 * s >= K.w) ? 1u : 0u;
                 auto I = [&](int dr, int dc) -> float {
                     int r = row0 + dr, c = col0 + dc;
-                    r = r < 0 ? 0 : (r >= P.h ? P.h - 1 : r);
-                    c = c < 0 ? 0 : (c >= P.w ? P.w - 1 : c);
+                    r = r < 0 ? 0 : (r >= K.h ? K.h - 1 : r);
+                    c = c < 0 ? 0 : (c >= K.w ? K.w - 1 : c);
                     return (float)P.img[(size_t)r * width + c];
                 };
                 const float du = 0.5f * ((w_tl * I(0, s) + w_tr * I(0, 2 * s) + w_bl * I(s, s) + w_br * I(s, 2 * s)) -

@@ -3,8 +3,9 @@
 // (:117-138) and AddPoint's voxel key (:195-208).
 //
 //   k_vis_score  one cloud point per thread, in the cloud's order: the world
-//                point exactly as k_to_world stores it (world_point), then
-//                vis_project and vis_score (cam_model.h): w2c, the frame test,
+//                point exactly as k_to_world stores it (cloud_world_point,
+//                device_common.h), then vis_project and vis_score
+//                (cam_model.h): w2c, the frame test,
 //                the grid index, shiTomasiScore over the 10 x 10 byte window
 //                (aligned 4-byte loads, a row at a time).  A point of positive
 //                score bids for its cell with one 64-bit atomicMax of
@@ -13,7 +14,7 @@
 //                among equal scores, so the table is what the reference's
 //                sequential `cur_value > map_value[index]` leaves, whatever
 //                the order of execution.  The call's counters take one integer
-//                add per block and counter (wave ballots first).
+//                add per block and counter (block_tally).
 //   k_vis_flags  one cell per thread: 1 where the cell has a winner, and their
 //                count.
 //   k_vis_emit   behind an exclusive scan of the flags: one wave per occupied
@@ -34,20 +35,13 @@ static_assert(sizeof(livo_vis_point) == 64, "one 64-B record");
 static_assert(kVisBlock % 64 == 0 && kVisBlock <= 1024, "whole waves");
 constexpr int kVisWaves = kVisBlock / 64;
 
-__device__ __forceinline__ void vis_world(const VisParams& P, int i, float& wx, float& wy, float& wz) {
-    const int64_t k = P.iperm ? (int64_t)P.iperm[i] : (int64_t)i;
-    const float* p = P.src + P.stride * k;
-    world_point(P.W.rot, P.W.pos, P.W.R_LI, P.W.t_LI, p[0], p[1], p[2], wx, wy, wz);
-}
-
 __global__ __launch_bounds__(kVisBlock) void k_vis_score(VisParams P) {
     const int i = blockIdx.x * kVisBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int fate = kVisOutOfFrame;
     bool behind = false;
-    if (i < P.n) {
+    if (i < (int)P.cloud.n) {
         float wx, wy, wz;
-        vis_world(P, i, wx, wy, wz);
+        cloud_world_point(P.cloud, P.W, i, wx, wy, wz);
         double pc[2];
         int index;
         fate = vis_project(P.cam, P.grid, wx, wy, wz, pc, behind, index);
@@ -61,36 +55,19 @@ __global__ __launch_bounds__(kVisBlock) void k_vis_score(VisParams P) {
             }
         }
     }
-    __shared__ uint32_t cnt[kVisWaves][kVisCtrOut];
-    const unsigned long long mi = __ballot(fate != kVisOutOfFrame), mb = __ballot(behind),
-                             mo = __ballot(fate == kVisOverflow);
-    if (lane == 0) {
-        cnt[w][kVisCtrInFrame] = (uint32_t)__popcll(mi);
-        cnt[w][kVisCtrBehind] = (uint32_t)__popcll(mb);
-        cnt[w][kVisCtrOverflow] = (uint32_t)__popcll(mo);
-    }
-    __syncthreads();
-    if (threadIdx.x < kVisCtrOut) {
-        uint32_t v = 0;
-        for (int ww = 0; ww < kVisWaves; ww++) v += cnt[ww][threadIdx.x];
-        if (v) atomicAdd(P.ctr + threadIdx.x, (unsigned long long)v);
-    }
+    static_assert(kVisCtrInFrame == 0 && kVisCtrBehind == 1 && kVisCtrOverflow == 2 && kVisCtrOut == 3, "the order");
+    const bool pred[kVisCtrOut] = {fate != kVisOutOfFrame, behind, fate == kVisOverflow};
+    const uint32_t v = block_tally<kVisWaves>(pred);
+    if (threadIdx.x < kVisCtrOut && v) atomicAdd(P.ctr + threadIdx.x, (unsigned long long)v);
 }
 
 __global__ __launch_bounds__(kVisBlock) void k_vis_flags(VisParams P) {
     const int c = blockIdx.x * kVisBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const bool occ = c < P.grid.length && P.table[c] != 0ull;
     if (c < P.grid.length) P.flag[c] = occ ? 1u : 0u;
-    __shared__ uint32_t cnt[kVisWaves];
-    const unsigned long long m = __ballot(occ);
-    if (lane == 0) cnt[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t v = 0;
-        for (int ww = 0; ww < kVisWaves; ww++) v += cnt[ww];
-        if (v) atomicAdd(P.ctr + kVisCtrOut, (unsigned long long)v);
-    }
+    const bool pred[1] = {occ};
+    const uint32_t v = block_tally<kVisWaves>(pred);
+    if (threadIdx.x == 0 && v) atomicAdd(P.ctr + kVisCtrOut, (unsigned long long)v);
 }
 
 __global__ __launch_bounds__(kVisBlock) void k_vis_emit(VisParams P) {
@@ -102,7 +79,7 @@ __global__ __launch_bounds__(kVisBlock) void k_vis_emit(VisParams P) {
     const int i = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
     const uint32_t pos = P.slot[c];
     float wx, wy, wz;
-    vis_world(P, i, wx, wy, wz);
+    cloud_world_point(P.cloud, P.W, i, wx, wy, wz);
     double pc[2];
     bool behind;
     int index;
@@ -133,8 +110,8 @@ __global__ __launch_bounds__(kVisBlock) void k_vis_emit(VisParams P) {
 static inline unsigned vis_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 int launch_vis_score(const VisParams& p, void* stream) {
-    if (p.n <= 0) return LIVO_OK;
-    hipLaunchKernelGGL(k_vis_score, dim3(vis_blocks(p.n, kVisBlock)), dim3(kVisBlock), 0, (hipStream_t)stream, p);
+    if (p.cloud.n <= 0) return LIVO_OK;
+    hipLaunchKernelGGL(k_vis_score, dim3(vis_blocks(p.cloud.n, kVisBlock)), dim3(kVisBlock), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 int launch_vis_flags(const VisParams& p, void* stream) {

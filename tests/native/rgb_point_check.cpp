@@ -8,7 +8,6 @@
 // float xyz[3 * n] (world points).
 // Output: "pose" and the 12 doubles of Rcw, Pcw as hex floats; then per point
 // "fate r g b a edge".
-#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -32,13 +31,16 @@ int main(int argc, char** argv) {
     ok = std::fread(img.data(), 1, img.size(), f) == img.size() && std::fread(xyz.data(), 4, xyz.size(), f) == xyz.size();
     std::fclose(f);
     if (!ok) return 2;
-    RgbCam C;
-    cam_pose(Rci, Pci, rot, pos, C.Rcw, C.Pcw);
-    C.fx = cam[0]; C.fy = cam[1]; C.cx = cam[2]; C.cy = cam[3];
-    for (int k = 0; k < 5; k++) C.d[k] = cam[4 + k];
-    C.distortion = std::fabs(C.d[0]) > 0.0000001 ? 1 : 0;  // as livo_cloud_colorize sets it
-    C.w = w;
-    C.h = h;
+    // the camera as livo_cloud_colorize fills it
+    livo_vio_params vp{};
+    livo_state st{};
+    vp.cam.fx = cam[0]; vp.cam.fy = cam[1]; vp.cam.cx = cam[2]; vp.cam.cy = cam[3];
+    for (int k = 0; k < 5; k++) vp.cam.d[k] = cam[4 + k];
+    vp.cam.width = w;
+    vp.cam.height = h;
+    for (int k = 0; k < 9; k++) vp.R_ci[k] = Rci[k], st.rot[k] = rot[k];
+    for (int k = 0; k < 3; k++) vp.P_ci[k] = Pci[k], st.pos[k] = pos[k];
+    const FrameCam C = frame_cam(vp, st);
     std::printf("pose");
     for (int k = 0; k < 9; k++) std::printf(" %a", C.Rcw[k]);
     for (int k = 0; k < 3; k++) std::printf(" %a", C.Pcw[k]);

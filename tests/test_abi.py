@@ -37,6 +37,20 @@ def test_library_exports_every_declared_symbol(built):
     assert exported == set(_declared())
 
 
+def test_carve_cursor_totals_and_alignment(tmp_path):
+    """csrc/carve.h, the cursor the frame stages lay their device buffers out with (a layout run over a
+    null base for the byte total, then over the buffer for the pointers): tests/native/carve_check.cpp on
+    the CPU under the address and undefined-behaviour sanitizers.  The two passes end at the same offset,
+    every array is 256-byte aligned and inside the total, consecutive arrays do not overlap."""
+    exe = tmp_path / "carve_check"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "fast-livo-noted_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "native", "carve_check.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout == "ok\n"
+
+
 def test_hip_code_object_is_gfx950(built):
     import livo_amd
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-S", livo_amd.LIB_PATH], capture_output=True,
