@@ -33,6 +33,7 @@ SOURCES = [
     ("vio_kernels.hip", True),
     ("rgb_kernels.hip", True),
     ("vis_kernels.hip", True),
+    ("vmap_kernels.hip", True),
     ("ikd_incr_kernels.hip", True),
     ("prims.hip", True),
     ("livo_capi.cpp", False),

@@ -104,6 +104,23 @@ static void free_scan_buf(ScanBuf& s) {
 
 }  // namespace
 
+// The resident visual map (livo_vmap_*): the points, their observations and
+// patches and the frame table in one buffer, the frames' images in another
+// (sized by the first frame), and the host's copy of what validation needs.
+struct VmapDev {
+    bool ready = false;
+    int64_t max_points = 0, max_frames = 0, n_obs = 0;
+    int32_t ps = 0, w = 0, h = 0;
+    void* buf = nullptr;
+    size_t bytes = 0;
+    void* img = nullptr;
+    size_t img_bytes = 0;
+    VmStore dev{};                 // the arrays in buf / img, n_points and n_frames
+    CamIntrinsics K{};             // of the frames (the first one's)
+    std::vector<int32_t> count;    // observations per point
+    std::vector<VmFrame> frames;   // by slot
+};
+
 // The device iVox map and its AddPoints / overflow-pass scratch.
 struct IvoxDev {
     bool ready = false;
@@ -338,6 +355,10 @@ struct livo_ctx {
     DevImage gray_img;                 // livo_vio_select: the last uploaded gray image (reused by gray == NULL)
     void* vis_buf = nullptr;           // ... and its cell table, flags, slots, counters, records and patches
     size_t vis_bytes = 0;
+    VmapDev vmap;                      // the resident visual map (livo_vmap_*)
+    DevImage match_img;                // livo_vio_match: the last uploaded gray image (reused by gray == NULL)
+    void* vm_buf = nullptr;            // ... and its voxel set, depth image, bids, records and patches
+    size_t vm_bytes = 0;
     void* prim_tmp = nullptr;          // rocPRIM scratch (sorts, scans)
     size_t prim_bytes = 0;
     // scans
@@ -1937,6 +1958,10 @@ int livo_ctx_destroy(livo_ctx* c) {
     dev_free(c->bgr_img.p);
     dev_free(c->gray_img.p);
     if (c->vis_buf) (void)hipFree(c->vis_buf);
+    dev_free(c->match_img.p);
+    if (c->vm_buf) (void)hipFree(c->vm_buf);
+    if (c->vmap.buf) (void)hipFree(c->vmap.buf);
+    if (c->vmap.img) (void)hipFree(c->vmap.img);
     dev_free(c->nodes);
     dev_free(c->lnodes);
     dev_free(c->lpts);
@@ -4588,6 +4613,356 @@ int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const
     if (out && cap < sel) return LIVO_E_CAPACITY;
     if (out && sel > 0) {
         HIP_TRY(hipMemcpyAsync(out, V.out, (size_t)sel * sizeof(livo_vis_point), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(patches, V.patches, (size_t)sel * pst3 * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return LIVO_OK;
+}
+
+int livo_vmap_reset(livo_ctx* c, int64_t max_points, int64_t max_frames, int32_t patch_size) {
+    if (!c || max_points < 1 || max_frames < 1 || patch_size < 1 || patch_size > 8) return LIVO_E_INVALID;
+    if (max_points > (int64_t)0x7FFFFFFF / kVmMaxObs || max_frames > (int64_t)0x7FFFFFFF - kVmBlock)
+        return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    VmapDev& m = c->vmap;
+    m.ready = false;
+    const size_t pst3 = (size_t)3 * patch_size * patch_size;
+    VmStore D{};
+    VmFrame* frame;
+    auto layout = [&](Carve k) {
+        D.pt = k.take<VmPoint>((size_t)max_points);
+        D.obs = k.take<VmObs>((size_t)max_points * kVmMaxObs);
+        D.patch = k.take<float>((size_t)max_points * kVmMaxObs * pst3);
+        D.frame = frame = k.take<VmFrame>((size_t)max_frames);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&m.buf, &m.bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)m.buf});
+    (void)frame;
+    D.img = (const uint8_t*)m.img;
+    m.dev = D;
+    m.max_points = max_points;
+    m.max_frames = max_frames;
+    m.ps = patch_size;
+    m.w = m.h = 0;
+    m.n_obs = 0;
+    m.count.clear();
+    m.frames.clear();
+    m.ready = true;
+    return LIVO_OK;
+}
+
+static int vmap_frame_slot(const VmapDev& m, int32_t frame_id) {
+    for (size_t k = 0; k < m.frames.size(); k++)
+        if (m.frames[k].id == frame_id) return (int)k;
+    return -1;
+}
+
+int livo_vmap_add_frame(livo_ctx* c, int32_t frame_id, const livo_state* state, const livo_vio_params* p,
+                        const uint8_t* gray, int32_t width, int32_t height) {
+    if (!c || !state || !p || frame_id < 0 || width <= 0 || height <= 0) return LIVO_E_INVALID;
+    VmapDev& m = c->vmap;
+    if (!m.ready || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
+    const FrameCam cam = frame_cam(*p, *state);
+    if (cam.distortion) return LIVO_E_INVALID;
+    if (!m.frames.empty() && (width != m.w || height != m.h || cam.fx != m.K.fx || cam.fy != m.K.fy ||
+                              cam.cx != m.K.cx || cam.cy != m.K.cy))
+        return LIVO_E_INVALID;
+    if (!gray && !image_reusable(c->gray_img, width, height)) return LIVO_E_INVALID;
+    if (vmap_frame_slot(m, frame_id) >= 0) return LIVO_E_INVALID;
+    if ((int64_t)m.frames.size() >= m.max_frames) return LIVO_E_CAPACITY;
+    if (set_device(c)) return LIVO_E_HIP;
+    const size_t bytes = (size_t)width * (size_t)height;
+    if (m.frames.empty()) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        RC_TRY(ensure_dev_bytes(&m.img, &m.img_bytes, bytes * (size_t)m.max_frames));
+        m.dev.img = (const uint8_t*)m.img;
+        m.w = width;
+        m.h = height;
+        m.K = cam;
+    }
+    VmFrame f{};
+    f.id = frame_id;
+    std::memcpy(f.Rcw, cam.Rcw, sizeof(f.Rcw));
+    std::memcpy(f.Pcw, cam.Pcw, sizeof(f.Pcw));
+    vm_frame_pos(f.Rcw, f.Pcw, f.pos);
+    const size_t slot = m.frames.size();
+    uint8_t* dst = (uint8_t*)m.img + slot * bytes;
+    HIP_TRY(hipMemcpyAsync(dst, gray ? gray : c->gray_img.p, bytes, gray ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync((VmFrame*)m.dev.frame + slot, &f, sizeof(f), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.frames.push_back(f);
+    m.dev.n_frames = (int32_t)m.frames.size();
+    return LIVO_OK;
+}
+
+int livo_vmap_add(livo_ctx* c, int32_t frame_id, int64_t n, const int32_t* point_ids, const livo_vis_point* pts,
+                  const int32_t* levels, const float* patches, int32_t* ids_out) {
+    if (!c || n < 0 || (n > 0 && (!pts || !patches))) return LIVO_E_INVALID;
+    VmapDev& m = c->vmap;
+    if (!m.ready) return LIVO_E_INVALID;
+    const int slot = vmap_frame_slot(m, frame_id);
+    if (slot < 0) return LIVO_E_INVALID;
+    if (n == 0) return LIVO_OK;
+    const int64_t np0 = (int64_t)m.count.size();
+    if (levels)
+        for (int64_t i = 0; i < n; i++)
+            if (levels[i] < 0 || levels[i] > 8) return LIVO_E_INVALID;
+    // the place of every observation, on a copy of the counts: nothing is written on an error
+    std::vector<int32_t> count = m.count, point((size_t)n), index((size_t)n), after((size_t)n);
+    if (!point_ids) {
+        if (np0 + n > m.max_points) return LIVO_E_CAPACITY;
+        count.resize((size_t)(np0 + n), 0);
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t id = point_ids ? (int64_t)point_ids[i] : np0 + i;
+        if (id < 0 || id >= (int64_t)count.size()) return LIVO_E_INVALID;
+        if (count[(size_t)id] >= kVmMaxObs) return LIVO_E_CAPACITY;
+        point[(size_t)i] = (int32_t)id;
+        index[(size_t)i] = count[(size_t)id]++;
+    }
+    for (int64_t i = 0; i < n; i++) after[(size_t)i] = count[(size_t)point[(size_t)i]];
+    std::vector<VmObs> obs((size_t)n);
+    std::vector<VmPoint> fresh(point_ids ? 0 : (size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        VmObs& o = obs[(size_t)i];
+        o = VmObs{};
+        o.frame_id = frame_id;
+        o.level = point_ids && levels ? levels[i] : 0;
+        o.slot = slot;
+        o.px[0] = pts[i].u;
+        o.px[1] = pts[i].v;
+        vm_cam2world(m.K, o.px[0], o.px[1], o.f);
+        if (!point_ids) {
+            VmPoint& q = fresh[(size_t)i];
+            q = VmPoint{};
+            q.pos[0] = (double)pts[i].x;
+            q.pos[1] = (double)pts[i].y;
+            q.pos[2] = (double)pts[i].z;
+            q.value = pts[i].score;
+            q.n_obs = 1;
+            for (int k = 0; k < 3; k++) q.voxel[k] = pts[i].voxel[k];
+        }
+    }
+    if (set_device(c)) return LIVO_E_HIP;
+    const int pst3 = 3 * m.ps * m.ps;
+    VmPutParams P{};
+    VmObs* d_obs;
+    float* d_pat;
+    int32_t *d_point, *d_index, *d_count;
+    auto layout = [&](Carve k) {
+        d_obs = k.take<VmObs>((size_t)n);
+        d_pat = k.take<float>((size_t)n * pst3);
+        d_point = k.take<int32_t>((size_t)n);
+        d_index = k.take<int32_t>((size_t)n);
+        d_count = k.take<int32_t>((size_t)n);
+        return k.total();
+    };
+    RC_TRY(ensure_scratch(c, layout(Carve{nullptr})));
+    layout(Carve{(char*)c->scratch});
+    HIP_TRY(hipMemcpyAsync(d_obs, obs.data(), (size_t)n * sizeof(VmObs), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_pat, patches, (size_t)n * pst3 * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_point, point.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_index, index.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_count, after.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (!point_ids)
+        HIP_TRY(hipMemcpyAsync(m.dev.pt + np0, fresh.data(), (size_t)n * sizeof(VmPoint), hipMemcpyHostToDevice,
+                               c->stream));
+    P.map = m.dev;
+    P.n = (int32_t)n;
+    P.pst3 = pst3;
+    P.obs = d_obs;
+    P.patches = d_pat;
+    P.point = d_point;
+    P.index = d_index;
+    P.count = d_count;
+    RC_TRY(launch_vm_put(P, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    m.count.swap(count);
+    m.n_obs += n;
+    m.dev.n_points = (int32_t)m.count.size();
+    if (ids_out && !point_ids)
+        for (int64_t i = 0; i < n; i++) ids_out[i] = (int32_t)(np0 + i);
+    return LIVO_OK;
+}
+
+int livo_vmap_info(livo_ctx* c, livo_vmap_counts* info) {
+    if (!c || !info) return LIVO_E_INVALID;
+    const VmapDev& m = c->vmap;
+    if (!m.ready) return LIVO_E_INVALID;
+    std::memset(info, 0, sizeof(*info));
+    info->n_points = (int64_t)m.count.size();
+    info->n_obs = m.n_obs;
+    info->n_frames = (int64_t)m.frames.size();
+    info->max_points = m.max_points;
+    info->max_frames = m.max_frames;
+    info->patch_size = m.ps;
+    info->width = m.w;
+    info->height = m.h;
+    return LIVO_OK;
+}
+
+int livo_vmap_dump(livo_ctx* c, livo_vmap_point* points, int64_t cap_points, livo_vmap_obs* obs, float* patches,
+                   int64_t cap_obs, int64_t* n_points, int64_t* n_obs) {
+    if (!c || !n_points || !n_obs || cap_points < 0 || cap_obs < 0) return LIVO_E_INVALID;
+    const VmapDev& m = c->vmap;
+    if (!m.ready) return LIVO_E_INVALID;
+    const int64_t np = (int64_t)m.count.size();
+    *n_points = np;
+    *n_obs = m.n_obs;
+    if (!points && !obs && !patches) return LIVO_OK;
+    if ((points && cap_points < np) || ((obs || patches) && cap_obs < m.n_obs)) return LIVO_E_RANGE;
+    if (np == 0) return LIVO_OK;
+    if (set_device(c)) return LIVO_E_HIP;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t pst3 = (size_t)3 * m.ps * m.ps;
+    std::vector<VmPoint> pt((size_t)np);
+    std::vector<VmObs> ob((size_t)np * kVmMaxObs);
+    HIP_TRY(hipMemcpy(pt.data(), m.dev.pt, pt.size() * sizeof(VmPoint), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ob.data(), m.dev.obs, ob.size() * sizeof(VmObs), hipMemcpyDeviceToHost));
+    int64_t at = 0;
+    for (int64_t i = 0; i < np; i++) {
+        const int cnt = m.count[(size_t)i];
+        if (pt[(size_t)i].n_obs != cnt) return LIVO_E_HIP;
+        if (points) {
+            livo_vmap_point& q = points[i];
+            std::memset(&q, 0, sizeof(q));
+            std::memcpy(q.pos, pt[(size_t)i].pos, sizeof(q.pos));
+            q.value = pt[(size_t)i].value;
+            q.n_obs = cnt;
+            std::memcpy(q.voxel, pt[(size_t)i].voxel, sizeof(q.voxel));
+            q.first_obs = at;
+        }
+        for (int k = 0; k < cnt; k++) {
+            if (obs) {
+                const VmObs& o = ob[(size_t)i * kVmMaxObs + k];
+                livo_vmap_obs& r = obs[at + k];
+                std::memset(&r, 0, sizeof(r));
+                r.frame_id = o.frame_id;
+                r.level = o.level;
+                std::memcpy(r.px, o.px, sizeof(r.px));
+                std::memcpy(r.f, o.f, sizeof(r.f));
+            }
+        }
+        if (patches && cnt > 0)  // a point's observations lie together
+            HIP_TRY(hipMemcpy(patches + (size_t)at * pst3, m.dev.patch + (size_t)i * kVmMaxObs * pst3,
+                              (size_t)cnt * pst3 * 4, hipMemcpyDeviceToHost));
+        at += cnt;
+    }
+    return LIVO_OK;
+}
+
+int livo_vio_match(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                   int32_t grid_size, int32_t ncc_en, double ncc_thre, double outlier_threshold,
+                   const uint8_t* gray, int32_t width, int32_t height, livo_vmatch_point* out, double* pos,
+                   int32_t* search_levels, float* patches, int64_t cap, int64_t* n_out, livo_vmatch_stats* stats) {
+    if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
+    if (grid_size < 1 || p->patch_size < 2 || p->patch_size > 8 || p->patch_size % 2 || cap < 0) return LIVO_E_INVALID;
+    if (width <= 0 || height <= 0 || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
+    if (out ? !(pos && search_levels && patches) : cap != 0) return LIVO_E_INVALID;
+    VmapDev& m = c->vmap;
+    if (!m.ready || p->patch_size != m.ps) return LIVO_E_INVALID;
+    VmatchParams V{};
+    V.cam = frame_cam(*p, *state);  // once per call
+    if (V.cam.distortion) return LIVO_E_INVALID;
+    if (!m.frames.empty() && (width != m.w || height != m.h)) return LIVO_E_INVALID;
+    V.grid.ps = p->patch_size;
+    V.grid.border = (p->patch_size / 2 + 1) * 8;
+    V.grid.grid_size = grid_size;
+    if ((int64_t)width - 2 * V.grid.border < grid_size || (int64_t)height - 2 * V.grid.border < grid_size)
+        return LIVO_E_INVALID;
+    V.grid.grid_n_height = height / grid_size;
+    const int64_t length = (int64_t)(width / grid_size) * V.grid.grid_n_height;
+    if (length > (int64_t)0x7FFFFFFF - kVmBlock) return LIVO_E_RANGE;
+    V.grid.length = (int32_t)length;
+    if (!gray && !image_reusable(c->match_img, width, height)) return LIVO_E_INVALID;
+    RC_TRY(frame_cloud(c, scan_id, &V.cloud));  // in the caller's point order (iperm)
+    const int64_t n = V.cloud.n;
+    if (n > ((int64_t)1 << 30)) return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    if (gray) RC_TRY(image_stage(c->match_img, gray, (size_t)width * (size_t)height, c->stream));
+    const int pst3 = 3 * p->patch_size * p->patch_size;
+    const int64_t np = (int64_t)m.count.size();
+    int log2 = 6;  // two slots per cloud point at least: a probe always ends
+    while (((int64_t)1 << log2) < 2 * n) log2++;
+    V.vset_log2 = log2;
+    const size_t npix = (size_t)width * (size_t)height;
+    uint32_t* d_slot;
+    char* clear_end;
+    auto layout = [&](Carve k) {
+        // cleared to 0xFF: the set, the bids, the warp owners
+        V.vset = k.take<unsigned long long>((size_t)1 << log2);
+        V.bid = k.take<unsigned long long>((size_t)length);
+        V.owner = k.take<uint32_t>((size_t)m.max_frames);
+        clear_end = (char*)k.take<char>(0);
+        // cleared to 0: the depth image, the counters
+        V.depth = k.take<uint32_t>(npix);
+        V.ctr = k.take<unsigned long long>(kVmCtrN);
+        V.cand = k.take<int32_t>((size_t)length);
+        V.keep = k.take<uint32_t>((size_t)length);
+        V.slot = d_slot = k.take<uint32_t>((size_t)length);
+        V.rec = k.take<livo_vmatch_point>((size_t)length);
+        V.cpatch = k.take<float>((size_t)length * pst3);
+        V.out = k.take<livo_vmatch_point>((size_t)length);
+        V.pos = k.take<double>((size_t)length * 3);
+        V.levels = k.take<int32_t>((size_t)length);
+        V.patches = k.take<float>((size_t)length * pst3);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&c->vm_buf, &c->vm_bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)c->vm_buf});
+    V.W = world_params(c, *state);
+    vm_frame_pos(V.cam.Rcw, V.cam.Pcw, V.fpos);
+    V.map = m.dev;
+    V.img = c->match_img.p;
+    V.ncc_en = ncc_en ? 1 : 0;
+    V.store = out ? 1 : 0;
+    V.ncc_thre = ncc_thre;
+    V.err_thre = outlier_threshold * (double)(p->patch_size * p->patch_size);
+    unsigned long long ctr[kVmCtrN] = {};
+    if (np > 0) {  // (:334: an empty map returns at once)
+        HIP_TRY(hipMemsetAsync(V.vset, 0xFF, (size_t)(clear_end - (char*)V.vset), c->stream));
+        HIP_TRY(hipMemsetAsync(V.depth, 0, (size_t)((char*)(V.ctr + kVmCtrN) - (char*)V.depth), c->stream));
+        RC_TRY(launch_vm_cloud(V, c->stream));
+        RC_TRY(launch_vm_map(V, c->stream));
+        RC_TRY(launch_vm_cell(V, c->stream));
+        RC_TRY(launch_vm_warp(V, c->stream));
+        if (out) {  // (the cells bound the result: the survivors are written before their count is known)
+            RC_TRY(ivox_scan(c, V.keep, d_slot, length));
+            RC_TRY(launch_vm_scatter(V, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(ctr, V.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (gray) {  // the upload is done: later calls may reuse it
+        c->match_img.w = width;
+        c->match_img.h = height;
+    }
+    const int64_t sel = (int64_t)ctr[kVmCtrOut];
+    *n_out = sel;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->n_in = n;
+        stats->n_voxels = (int64_t)ctr[kVmCtrVoxels];
+        stats->map_tested = (int64_t)ctr[kVmCtrTested];
+        stats->in_frame = (int64_t)ctr[kVmCtrInFrame];
+        stats->cell_overflow = (int64_t)ctr[kVmCtrOverflow];
+        stats->cells_marked = (int64_t)ctr[kVmCtrMarked];
+        stats->depth_rejected = (int64_t)ctr[kVmCtrDepth];
+        stats->view_rejected = (int64_t)ctr[kVmCtrView];
+        stats->ncc_rejected = (int64_t)ctr[kVmCtrNcc];
+        stats->error_rejected = (int64_t)ctr[kVmCtrError];
+        stats->warp_shared = (int64_t)ctr[kVmCtrShared];
+        stats->warp_nan = (int64_t)ctr[kVmCtrNan];
+        stats->n_out = sel;
+    }
+    if (out && cap < sel) return LIVO_E_CAPACITY;
+    if (out && sel > 0) {
+        HIP_TRY(hipMemcpyAsync(out, V.out, (size_t)sel * sizeof(livo_vmatch_point), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(pos, V.pos, (size_t)sel * 24, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(search_levels, V.levels, (size_t)sel * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(patches, V.patches, (size_t)sel * pst3 * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }

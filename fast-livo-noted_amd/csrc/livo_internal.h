@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "cam_model.h"
+#include "vmap_model.h"
 #include "livo.h"
 #include "stl_select.h"
 
@@ -635,6 +636,64 @@ struct VisParams {
 int launch_vis_score(const VisParams& p, void* stream);
 int launch_vis_flags(const VisParams& p, void* stream);
 int launch_vis_emit(const VisParams& p, void* stream);
+// LidarSelector::addFromSparseMap (vmap_kernels.hip) on the resident visual map:
+// the cloud of launch_to_world gives the frame's voxel set and depth image, the
+// map points bid for their grid cells, each cell's point is tested, its
+// observation's patch warped and compared, the survivors written in ascending
+// cell order.
+constexpr int kVmBlock = 256;
+enum { kVmCtrVoxels = 0, kVmCtrTested, kVmCtrInFrame, kVmCtrOverflow, kVmCtrMarked, kVmCtrDepth, kVmCtrView,
+       kVmCtrNcc, kVmCtrError, kVmCtrShared, kVmCtrNan, kVmCtrOut, kVmCtrN };
+struct VmStore {
+    VmPoint* pt;              // max_points
+    VmObs* obs;               // max_points x kVmMaxObs
+    float* patch;             // max_points x kVmMaxObs x 3 ps^2
+    const VmFrame* frame;     // max_frames
+    const uint8_t* img;       // max_frames images of cam.w x cam.h
+    int32_t n_points, n_frames;
+};
+struct VmatchParams {
+    CloudSrc cloud;           // n < 2^31 - kVmBlock
+    WorldParams W;
+    FrameCam cam;
+    VisGrid grid;             // ps even
+    VmStore map;
+    double fpos[3];           // new_frame_->pos()
+    const uint8_t* img;       // the current gray image
+    int32_t ncc_en, store;    // store: write the warped patch into the map
+    double ncc_thre, err_thre;  // err_thre = outlier_threshold * ps^2
+    unsigned long long* vset; // 2^vset_log2 packed voxel keys; ~0: empty
+    int32_t vset_log2, pad_;
+    uint32_t* depth;          // cam.w x cam.h: 1 + the last cloud index on the pixel; 0: none
+    unsigned long long* bid;  // grid.length cell bids (vm_bid); ~0: unmarked
+    uint32_t* owner;          // per frame slot: the lowest cell that reached the warp with it; ~0: none
+    int32_t* cand;            // grid.length: the chosen observation of the cell's point, -1: none / rejected
+    uint32_t* keep;           // grid.length: 1 survivor
+    const uint32_t* slot;     // their exclusive scan (the scatter)
+    livo_vmatch_point* rec;   // grid.length records, by cell
+    float* cpatch;            // grid.length x 3 ps^2, by cell
+    unsigned long long* ctr;  // kVmCtrN counters, zeroed by the caller
+    livo_vmatch_point* out;   // survivors, ascending cell index
+    double* pos;              // 3 each
+    int32_t* levels;
+    float* patches;           // 3 ps^2 each
+};
+int launch_vm_cloud(const VmatchParams& p, void* stream);
+int launch_vm_map(const VmatchParams& p, void* stream);
+int launch_vm_cell(const VmatchParams& p, void* stream);
+int launch_vm_warp(const VmatchParams& p, void* stream);
+int launch_vm_scatter(const VmatchParams& p, void* stream);
+// livo_vmap_add: n staged observations (and their patches) into their slots, and the points' counts.
+struct VmPutParams {
+    VmStore map;
+    int32_t n, pst3;
+    const VmObs* obs;         // n staged
+    const float* patches;     // n x pst3
+    const int32_t* point;     // n: the point of each
+    const int32_t* index;     // n: its place in the point's list
+    const int32_t* count;     // n: the point's count after the call
+};
+int launch_vm_put(const VmPutParams& p, void* stream);
 // laserCloudOri / corr_normvect compaction in the caller's order (stored-order sel / normvec / points).
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream);
 int launch_ori_scatter(const float* pts4, const float* normvec, const uint8_t* sel, const int32_t* perm,

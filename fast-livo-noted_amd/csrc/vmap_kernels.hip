@@ -1,0 +1,288 @@
+// vmap_kernels.hip — CDNA4 (gfx950) kernels of the resident visual map and of
+// LidarSelector::addFromSparseMap, src/lidar_selection.cpp:332-593.  The
+// arithmetic of one item is vmap_model.h's (shared with the host check).
+//
+//   k_vm_cloud    one cloud point per thread: the world point exactly as
+//                 k_to_world stores it, its floor voxel key inserted into the
+//                 frame's hash set (one 64-bit CAS per probe; the set has at
+//                 least two slots per cloud point, so a probe always ends),
+//                 and 1 + its cloud index bid for its depth pixel with a
+//                 32-bit atomicMax: the last index wins, as the reference's
+//                 sequential loop leaves it.  The depth itself is recomputed
+//                 from that index where it is read (the same functions, so
+//                 the same bits): the image to clear is 4 bytes a pixel.
+//   k_vm_map      one map point per thread: its stored key looked up, the
+//                 projection, and one 64-bit atomicMin of distance bits << 32
+//                 | ~id for its cell (vm_bid).
+//   k_vm_cell     one cell per thread: the cell's point through the depth
+//                 continuity test and the view choice; a cell that passes bids
+//                 its index for its reference frame's warp (atomicMin).
+//   k_vm_warp     one wave per cell that passed: the warp owner's matrix and
+//                 level recomputed by the shared function, one warped and one
+//                 current sample per lane, NCC and the error summed in index
+//                 order by lane 0 from LDS, the keep flag, the cell's record
+//                 and patch pyramid, and the warped patch into the map.
+//   k_vm_scatter  behind an exclusive scan of the keep flags: one wave per
+//                 survivor copies its record, position, level and patches.
+//   k_vm_put      livo_vmap_add: one wave per staged observation.
+// No position is decided by an atomic: two calls give the same bytes.
+// Numerics as livo_kernels.hip: -ffp-contract=off.
+#include <hip/hip_runtime.h>
+
+#include "device_common.h"
+#include "livo_internal.h"
+
+namespace livo {
+
+static_assert(sizeof(livo_vmatch_point) == 48, "one 48-B record");
+static_assert(kVmBlock % 64 == 0 && kVmBlock <= 1024, "whole waves");
+constexpr int kVmWaves = kVmBlock / 64;
+
+__device__ __forceinline__ uint32_t vm_bid_id(unsigned long long b) {
+    return 0xFFFFFFFFu - (uint32_t)(b & 0xFFFFFFFFull);
+}
+
+__global__ __launch_bounds__(kVmBlock) void k_vm_cloud(VmatchParams P) {
+    const int i = blockIdx.x * kVmBlock + threadIdx.x;
+    bool fresh = false;
+    if (i < (int)P.cloud.n) {
+        float wx, wy, wz, depth;
+        cloud_world_point(P.cloud, P.W, i, wx, wy, wz);
+        int64_t key[3], pix;
+        const bool hit = vm_cloud_point(P.cam, P.grid.border, wx, wy, wz, key, pix, depth);
+        unsigned long long k;
+        if (vm_pack_key(key, k)) {
+            const uint32_t mask = (1u << P.vset_log2) - 1u;
+            uint32_t s = vm_hash(k, P.vset_log2);
+            for (;;) {
+                unsigned long long cur = P.vset[s];
+                if (cur == kVmBidEmpty) cur = atomicCAS(P.vset + s, kVmBidEmpty, k);
+                if (cur == kVmBidEmpty) {
+                    fresh = true;
+                    break;
+                }
+                if (cur == k) break;
+                s = (s + 1u) & mask;
+            }
+        }
+        if (hit) atomicMax(P.depth + pix, (uint32_t)i + 1u);  // (0 <= pix < w * h: inside the border)
+    }
+    const bool pred[1] = {fresh};
+    const uint32_t v = block_tally<kVmWaves>(pred);
+    if (threadIdx.x == 0 && v) atomicAdd(P.ctr + kVmCtrVoxels, (unsigned long long)v);
+}
+
+__device__ __forceinline__ bool vm_set_has(const VmatchParams& P, unsigned long long k) {
+    const uint32_t mask = (1u << P.vset_log2) - 1u;
+    uint32_t s = vm_hash(k, P.vset_log2);
+    for (;;) {
+        const unsigned long long cur = P.vset[s];
+        if (cur == k) return true;
+        if (cur == kVmBidEmpty) return false;
+        s = (s + 1u) & mask;
+    }
+}
+
+__global__ __launch_bounds__(kVmBlock) void k_vm_map(VmatchParams P) {
+    const int i = blockIdx.x * kVmBlock + threadIdx.x;
+    bool tested = false;
+    int fate = kVmSkip;
+    if (i < P.map.n_points) {
+        const VmPoint pt = P.map.pt[i];
+        unsigned long long k;
+        tested = vm_pack_key(pt.voxel, k) && vm_set_has(P, k);
+        if (tested) {
+            double pf[3], pc[2];
+            int index;
+            float dist;
+            fate = vm_map_point(P.cam, P.grid, P.fpos, pt.pos, pf, pc, index, dist);
+            if (fate == kVmInFrame) atomicMin(P.bid + index, vm_bid(dist, (uint32_t)i));  // (0 <= index < length)
+        }
+    }
+    static_assert(kVmCtrTested + 1 == kVmCtrInFrame && kVmCtrInFrame + 1 == kVmCtrOverflow, "the order");
+    const bool pred[3] = {tested, fate != kVmSkip, fate == kVmOverflow};
+    const uint32_t v = block_tally<kVmWaves>(pred);
+    if (threadIdx.x < 3 && v) atomicAdd(P.ctr + kVmCtrTested + threadIdx.x, (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(kVmBlock) void k_vm_cell(VmatchParams P) {
+    const int c = blockIdx.x * kVmBlock + threadIdx.x;
+    bool marked = false, depth_rej = false, view_rej = false;
+    if (c < P.grid.length) {
+        const unsigned long long b = P.bid[c];
+        marked = b != kVmBidEmpty;
+        int chosen = -1;
+        if (marked && b != kVmBidNone) {
+            const uint32_t id = vm_bid_id(b);
+            const VmPoint pt = P.map.pt[id];
+            double pf[3], pc[2];
+            int index;
+            float dist;
+            (void)vm_map_point(P.cam, P.grid, P.fpos, pt.pos, pf, pc, index, dist);
+            const int half = P.grid.ps / 2, u0 = (int)pc[0], v0 = (int)pc[1];
+            for (int u = -half; u <= half && !depth_rej; u++)
+                for (int v = -half; v <= half; v++) {
+                    if (u == 0 && v == 0) continue;
+                    const uint32_t d = P.depth[(int64_t)(v + v0) * P.cam.w + (u + u0)];  // (half < border)
+                    if (d == 0u) continue;
+                    float wx, wy, wz, depth = 0.0f;
+                    cloud_world_point(P.cloud, P.W, (int)(d - 1u), wx, wy, wz);
+                    int64_t key[3], pix;
+                    (void)vm_cloud_point(P.cam, P.grid.border, wx, wy, wz, key, pix, depth);
+                    if (vm_depth_breaks(pf[2], depth)) {
+                        depth_rej = true;
+                        break;
+                    }
+                }
+            if (!depth_rej) {
+                double cosine = 0.0;
+                const VmObs* obs = P.map.obs + (size_t)id * kVmMaxObs;
+                const int best = vm_close_view(P.fpos, pt.pos, obs, pt.n_obs, P.map.frame, cosine);
+                view_rej = pt.n_obs <= 0 || cosine < 0.5;
+                if (!view_rej) {
+                    chosen = best;
+                    atomicMin(P.owner + obs[best].slot, (uint32_t)c);
+                }
+            }
+        }
+        P.cand[c] = chosen;
+    }
+    static_assert(kVmCtrMarked + 1 == kVmCtrDepth && kVmCtrDepth + 1 == kVmCtrView, "the order");
+    const bool pred[3] = {marked, depth_rej, view_rej};
+    const uint32_t v = block_tally<kVmWaves>(pred);
+    if (threadIdx.x < 3 && v) atomicAdd(P.ctr + kVmCtrMarked + threadIdx.x, (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(kVmBlock) void k_vm_warp(VmatchParams P) {
+    __shared__ float s_ref[kVmWaves][64], s_cur[kVmWaves][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x * kVmWaves + wave;  // one wave per cell
+    const int chosen = c < P.grid.length ? P.cand[c] : -1;
+    const int ps = P.grid.ps, pst = ps * ps;
+    bool shared = false, nan = false, ncc_rej = false, err_rej = false, kept = false;
+    uint32_t id = 0u;
+    double pc[2] = {0.0, 0.0};
+    int level = 0;
+    float* stored = nullptr;
+    if (chosen >= 0) {
+        id = vm_bid_id(P.bid[c]);
+        const VmPoint pt = P.map.pt[id];
+        const VmObs o = P.map.obs[(size_t)id * kVmMaxObs + chosen];
+        stored = P.map.patch + ((size_t)id * kVmMaxObs + chosen) * 3 * pst;
+        // Warp_map: the matrix and level of the first cell that met this reference frame
+        const int oc = (int)P.owner[o.slot];
+        shared = oc != c;
+        double A[4];
+        if (shared) {
+            const uint32_t id2 = vm_bid_id(P.bid[oc]);
+            const VmPoint pt2 = P.map.pt[id2];
+            const VmObs o2 = P.map.obs[(size_t)id2 * kVmMaxObs + P.cand[oc]];
+            vm_warp_matrix(P.cam, P.map.frame[o2.slot], o2, pt2.pos, ps / 2, A);
+        } else {
+            vm_warp_matrix(P.cam, P.map.frame[o.slot], o, pt.pos, ps / 2, A);
+        }
+        level = vm_search_level(A, 2);
+        float Ai[4];
+        vm_inverse2f(A, Ai);
+        nan = Ai[0] != Ai[0];
+        double pf[3];
+        int index;
+        float dist;
+        (void)vm_map_point(P.cam, P.grid, P.fpos, pt.pos, pf, pc, index, dist);
+        if (lane < pst) {
+            const uint8_t* ref_img = P.map.img + (size_t)o.slot * P.cam.w * P.cam.h;
+            s_ref[wave][lane] =
+                nan ? stored[lane] : vm_warp_sample(Ai, o.px, level, ps, lane, ref_img, P.cam.w, P.cam.h);
+            s_cur[wave][lane] = vis_getpatch(P.img, P.cam.w, pc, ps, 0, lane);
+        }
+    }
+    __syncthreads();
+    if (chosen >= 0) {
+        float* dst = P.cpatch + (size_t)c * 3 * pst;
+        for (int e = lane; e < 3 * pst; e += 64) dst[e] = e < pst ? s_ref[wave][e] : stored[e];
+        if (P.store && !nan && lane < pst) stored[lane] = s_ref[wave][lane];
+    }
+    if (lane == 0 && c < P.grid.length) {
+        if (chosen >= 0) {
+            double ncc = 0.0;
+            float err = 0.0f;
+            if (P.ncc_en) {
+                ncc = vm_ncc(s_ref[wave], s_cur[wave], pst);
+                ncc_rej = ncc < P.ncc_thre;
+            }
+            if (!ncc_rej) {
+                err = vm_error(s_ref[wave], s_cur[wave], pst);
+                err_rej = (double)err > P.err_thre;
+            }
+            kept = !ncc_rej && !err_rej;
+            livo_vmatch_point r;
+            r.point_id = (int32_t)id;
+            r.cell = c;
+            r.obs_index = chosen;
+            r.frame_id = P.map.obs[(size_t)id * kVmMaxObs + chosen].frame_id;
+            r.search_level = level;
+            r.error = err;
+            r.ncc = ncc;
+            r.u = pc[0];
+            r.v = pc[1];
+            P.rec[c] = r;
+        }
+        P.keep[c] = kept ? 1u : 0u;
+    }
+    static_assert(kVmCtrNcc + 1 == kVmCtrError && kVmCtrError + 1 == kVmCtrShared && kVmCtrShared + 1 == kVmCtrNan &&
+                      kVmCtrNan + 1 == kVmCtrOut, "the order");
+    const bool one = lane == 0;  // a wave's cell counts once
+    const bool pred[5] = {one && ncc_rej, one && err_rej, one && shared, one && nan, one && kept};
+    const uint32_t v = block_tally<kVmWaves>(pred);
+    if (threadIdx.x < 5 && v) atomicAdd(P.ctr + kVmCtrNcc + threadIdx.x, (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(kVmBlock) void k_vm_scatter(VmatchParams P) {
+    const int lane = threadIdx.x & 63;
+    const int c = blockIdx.x * kVmWaves + (threadIdx.x >> 6);
+    if (c >= P.grid.length || P.keep[c] == 0u) return;
+    const uint32_t pos = P.slot[c];
+    const livo_vmatch_point r = P.rec[c];
+    if (lane == 0) {
+        P.out[pos] = r;
+        P.levels[pos] = r.search_level;
+    }
+    if (lane < 3) P.pos[(size_t)pos * 3 + lane] = P.map.pt[r.point_id].pos[lane];
+    const int pst3 = 3 * P.grid.ps * P.grid.ps;
+    const float* src = P.cpatch + (size_t)c * pst3;
+    float* dst = P.patches + (size_t)pos * pst3;
+    for (int e = lane; e < pst3; e += 64) dst[e] = src[e];
+}
+
+__global__ __launch_bounds__(kVmBlock) void k_vm_put(VmPutParams P) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kVmWaves + (threadIdx.x >> 6);  // one wave per observation
+    if (i >= P.n) return;
+    const int point = P.point[i];
+    const size_t at = (size_t)point * kVmMaxObs + P.index[i];
+    if (lane == 0) {
+        P.map.obs[at] = P.obs[i];
+        P.map.pt[point].n_obs = P.count[i];
+    }
+    const float* src = P.patches + (size_t)i * P.pst3;
+    float* dst = P.map.patch + at * P.pst3;
+    for (int e = lane; e < P.pst3; e += 64) dst[e] = src[e];
+}
+
+static inline unsigned vm_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+#define VM_LAUNCH(kernel, count, per)                                                                        \
+    if ((count) <= 0) return LIVO_OK;                                                                        \
+    hipLaunchKernelGGL(kernel, dim3(vm_blocks((count), (per))), dim3(kVmBlock), 0, (hipStream_t)stream, p); \
+    return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP
+
+int launch_vm_cloud(const VmatchParams& p, void* stream) { VM_LAUNCH(k_vm_cloud, p.cloud.n, kVmBlock); }
+int launch_vm_map(const VmatchParams& p, void* stream) { VM_LAUNCH(k_vm_map, (int64_t)p.map.n_points, kVmBlock); }
+int launch_vm_cell(const VmatchParams& p, void* stream) { VM_LAUNCH(k_vm_cell, (int64_t)p.grid.length, kVmBlock); }
+int launch_vm_warp(const VmatchParams& p, void* stream) { VM_LAUNCH(k_vm_warp, (int64_t)p.grid.length, kVmWaves); }
+int launch_vm_scatter(const VmatchParams& p, void* stream) {
+    VM_LAUNCH(k_vm_scatter, (int64_t)p.grid.length, kVmWaves);
+}
+int launch_vm_put(const VmPutParams& p, void* stream) { VM_LAUNCH(k_vm_put, (int64_t)p.n, kVmWaves); }
+
+}  // namespace livo

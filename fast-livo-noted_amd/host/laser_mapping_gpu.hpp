@@ -241,6 +241,37 @@ public:
         return st;
     }
 
+    // lidar_selector->addFromSparseMap(img, pg) (lidar_selection.cpp:332-593) on the resident
+    // visual map (livo_vmap_reset / livo_vmap_add_frame / livo_vmap_add): pg and img as
+    // addSparseMap takes them (the image in a buffer of this stage's own; nullptr reuses the
+    // previous call's).  Fills sub_sparse_map's arrays as livo_vio_update reads them:
+    // `pos` (3 doubles a point), `search_levels`, `patches` (3 * patch_size^2 floats a point),
+    // and `points` (the records: map point, cell, observation, error), in ascending cell order.
+    livo_vmatch_stats addFromSparseMap(const livo_vio_params& vio, const uint8_t* img, int32_t width, int32_t height,
+                                       int32_t grid_size, bool ncc_en, double ncc_thre, double outlier_threshold,
+                                       std::vector<livo_vmatch_point>& points, std::vector<double>& pos,
+                                       std::vector<int32_t>& search_levels, std::vector<float>& patches,
+                                       bool dense_map_en = true) {
+        if (!dense_map_en && scan_id_ < 0) throw Error("addFromSparseMap", LIVO_E_NOSCAN);
+        const int32_t id = dense_map_en ? -1 : scan_id_;
+        int64_t n = 0;
+        livo_vmatch_stats st{};
+        check(livo_vio_match(ctx_, id, &state, &vio, grid_size, ncc_en ? 1 : 0, ncc_thre, outlier_threshold, img, width,
+                             height, nullptr, nullptr, nullptr, nullptr, 0, &n, &st),
+              "livo_vio_match");  // the sizing call (it uploads the image and leaves the map as it is)
+        const size_t per = (size_t)3 * (size_t)vio.patch_size * (size_t)vio.patch_size;
+        points.resize((size_t)n);
+        pos.resize((size_t)n * 3);
+        search_levels.resize((size_t)n);
+        patches.resize((size_t)n * per);
+        if (n > 0)
+            check(livo_vio_match(ctx_, id, &state, &vio, grid_size, ncc_en ? 1 : 0, ncc_thre, outlier_threshold, nullptr,
+                                 width, height, points.data(), pos.data(), search_levels.data(), patches.data(), n, &n,
+                                 &st),
+                  "livo_vio_match");
+        return st;
+    }
+
     livo_ctx* ctx() const { return ctx_; }
     const livo_params& params() const { return params_; }
 

@@ -11,6 +11,8 @@ path:
     IEKF loop of LaserMapping::Run       -> Context.iekf_update(_batch)
     LaserMapping::publish_frame_world_rgb -> Context.colorize
     LidarSelector::addSparseMap          -> Context.vio_select
+    feat_map / imgs_ (the visual map)    -> Context.vmap_reset / vmap_add_frame / vmap_add / vmap_dump
+    LidarSelector::addFromSparseMap      -> Context.vio_match
 
 There is no CPU fallback: loading fails loudly if the HIP library is missing,
 and every compute call raises LivoError when the GPU path fails.
@@ -183,6 +185,27 @@ class VisStats(C.Structure):
                 ("cell_overflow", C.c_int64), ("n_out", C.c_int64), ("n_cells", C.c_int64)]
 
 
+class VmapCounts(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_obs", C.c_int64), ("n_frames", C.c_int64), ("max_points", C.c_int64),
+                ("max_frames", C.c_int64), ("patch_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+VMAP_POINT_DTYPE = np.dtype([("pos", np.float64, (3,)), ("value", np.float32), ("n_obs", np.int32),
+                             ("voxel", np.int64, (3,)), ("first_obs", np.int64)])
+VMAP_OBS_DTYPE = np.dtype([("frame_id", np.int32), ("level", np.int32), ("px", np.float64, (2,)),
+                           ("f", np.float64, (3,))])
+VMATCH_POINT_DTYPE = np.dtype([("point_id", np.int32), ("cell", np.int32), ("obs_index", np.int32),
+                               ("frame_id", np.int32), ("search_level", np.int32), ("error", np.float32),
+                               ("ncc", np.float64), ("u", np.float64), ("v", np.float64)])
+
+
+class VmatchStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in (
+        "n_in", "n_voxels", "map_tested", "in_frame", "cell_overflow", "cells_marked", "depth_rejected",
+        "view_rejected", "ncc_rejected", "error_rejected", "warp_shared", "warp_nan", "n_out")]
+
+
 def vio_params(cam: dict, Rci, Pci) -> VioParams:
     """livo_vio_params from a camera dict (fx, fy, cx, cy, d, width, height) and the extrinsics."""
     p = VioParams()
@@ -253,6 +276,15 @@ SIGNATURES = {
                                       _P, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(RgbStats)]),
     "livo_vio_select": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.POINTER(VioParams), C.c_int32, _P, C.c_int32,
                                   C.c_int32, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(VisStats)]),
+    "livo_vmap_reset": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32]),
+    "livo_vmap_add_frame": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.POINTER(VioParams), _P, C.c_int32,
+                                      C.c_int32]),
+    "livo_vmap_add": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
+    "livo_vmap_info": (C.c_int, [_P, C.POINTER(VmapCounts)]),
+    "livo_vmap_dump": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "livo_vio_match": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.POINTER(VioParams), C.c_int32, C.c_int32,
+                                 C.c_double, C.c_double, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64,
+                                 C.POINTER(C.c_int64), C.POINTER(VmatchStats)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -818,6 +850,98 @@ class Context:
                 C.byref(n), C.byref(vs)))
         stats = {f: int(getattr(vs, f)) for f, _ in VisStats._fields_}
         return pts[:n.value], pat[:n.value], stats
+
+    # ------------------------------------------------- the visual map ----
+    def vmap_reset(self, max_points: int, max_frames: int, patch_size: int):
+        """An empty resident visual map of fixed capacities (livo_vmap_reset)."""
+        _check("livo_vmap_reset", self._L.livo_vmap_reset(self.h, max_points, max_frames, patch_size))
+
+    def vmap_add_frame(self, frame_id: int, state: dict, vio_params: VioParams, gray=None):
+        """Stores a past gray image (None: vio_select's retained one) and its pose under frame_id."""
+        st = state_to_c(state)
+        img = None if gray is None else np.ascontiguousarray(gray, np.uint8)
+        if img is not None and img.ndim != 2:
+            raise ValueError("gray must be (height, width)")
+        w, h = (vio_params.cam.width, vio_params.cam.height) if img is None else (img.shape[1], img.shape[0])
+        _check("livo_vmap_add_frame", self._L.livo_vmap_add_frame(
+            self.h, frame_id, C.byref(st), C.byref(vio_params), _ptr(img), w, h))
+
+    def vmap_add(self, frame_id: int, pts, patches, point_ids=None, levels=None):
+        """Observations from frame_id (livo_vmap_add): pts a VIS_POINT_DTYPE array, patches (n, 3 ps^2).
+        point_ids None creates the points and returns their ids; else one observation is appended to each."""
+        pts = np.ascontiguousarray(pts, VIS_POINT_DTYPE)
+        pat = np.ascontiguousarray(patches, np.float32)
+        n = len(pts)
+        ids = None if point_ids is None else np.ascontiguousarray(point_ids, np.int32)
+        lev = None if levels is None else np.ascontiguousarray(levels, np.int32)
+        if pat.size != n * 3 * self.vmap_info()["patch_size"] ** 2 or (ids is not None and len(ids) != n) or \
+                (lev is not None and len(lev) != n):
+            raise ValueError("pts, patches, point_ids and levels disagree in length")
+        out = np.zeros(n, np.int32)
+        _check("livo_vmap_add", self._L.livo_vmap_add(
+            self.h, frame_id, n, _ptr(ids), _ptr(pts), _ptr(lev), _ptr(pat), _ptr(out)))
+        return out if ids is None else ids
+
+    def vmap_info(self) -> dict:
+        v = VmapCounts()
+        _check("livo_vmap_info", self._L.livo_vmap_info(self.h, C.byref(v)))
+        return {f: int(getattr(v, f)) for f, _ in VmapCounts._fields_ if f != "pad_"}
+
+    def vmap_dump(self):
+        """(points: VMAP_POINT_DTYPE, obs: VMAP_OBS_DTYPE, patches (n_obs, 3 ps^2)) in id / list order."""
+        n_p, n_o = C.c_int64(), C.c_int64()
+        _check("livo_vmap_dump", self._L.livo_vmap_dump(self.h, None, 0, None, None, 0, C.byref(n_p), C.byref(n_o)))
+        ps = self.vmap_info()["patch_size"]
+        pts = np.zeros(n_p.value, VMAP_POINT_DTYPE)
+        obs = np.zeros(n_o.value, VMAP_OBS_DTYPE)
+        pat = np.zeros((n_o.value, 3 * ps * ps), np.float32)
+        if n_p.value > 0:
+            _check("livo_vmap_dump", self._L.livo_vmap_dump(
+                self.h, _ptr(pts), len(pts), _ptr(obs), _ptr(pat), len(obs), C.byref(n_p), C.byref(n_o)))
+        return pts, obs, pat
+
+    def vio_match(self, state: dict, gray, vio_params: VioParams, grid_size: int, ncc_en: bool = False,
+                  ncc_thre: float = 0.0, outlier_threshold: float = 100.0, scan_id: int = -1, frame: dict = None):
+        """LidarSelector::addFromSparseMap (livo_vio_match): the resident visual map matched into the gray
+        image (None: the image of the previous call) in the camera of vio_params at `state`, the cloud of
+        frame_to_world(state, scan_id) giving the voxel set and the depth image.  Returns a dict that
+        vio_update accepts (pos, levels, patches, patch_size, cam, Rci, Pci and, when gray is given, image)
+        with records (VMATCH_POINT_DTYPE, ascending cell) and stats; `frame` entries are copied in first."""
+        st = state_to_c(state)
+        img = None
+        if gray is not None:
+            img = np.ascontiguousarray(gray, np.uint8)
+            if img.ndim != 2:
+                raise ValueError("gray must be (height, width)")
+            w, h = img.shape[1], img.shape[0]
+        else:
+            w, h = vio_params.cam.width, vio_params.cam.height
+        n = C.c_int64()
+        vs = VmatchStats()
+        head = (self.h, scan_id, C.byref(st), C.byref(vio_params), grid_size, int(bool(ncc_en)), float(ncc_thre),
+                float(outlier_threshold))
+        # the sizing call uploads the image; the real one reuses it
+        _check("livo_vio_match", self._L.livo_vio_match(
+            *head, _ptr(img), w, h, None, None, None, None, 0, C.byref(n), C.byref(vs)))
+        cap = n.value
+        pst3 = 3 * vio_params.patch_size * vio_params.patch_size
+        rec = np.zeros(cap, VMATCH_POINT_DTYPE)
+        pos = np.zeros((cap, 3), np.float64)
+        lev = np.zeros(cap, np.int32)
+        pat = np.zeros((cap, pst3), np.float32)
+        if cap > 0:
+            _check("livo_vio_match", self._L.livo_vio_match(
+                *head, None, w, h, _ptr(rec), _ptr(pos), _ptr(lev), _ptr(pat), cap, C.byref(n), C.byref(vs)))
+        cam = vio_params.cam
+        out = dict(frame or {})
+        out.update({"pos": pos, "levels": lev, "patches": pat, "patch_size": int(vio_params.patch_size),
+                    "cam": {"fx": cam.fx, "fy": cam.fy, "cx": cam.cx, "cy": cam.cy, "d": list(cam.d),
+                            "width": cam.width, "height": cam.height},
+                    "Rci": np.array(vio_params.R_ci[:]).reshape(3, 3), "Pci": np.array(vio_params.P_ci[:]),
+                    "records": rec, "stats": {f: int(getattr(vs, f)) for f, _ in VmatchStats._fields_}})
+        if img is not None:
+            out["image"] = img
+        return out
 
     def scan_inherit_neighbors(self, dst: int, src: int):
         _check("livo_scan_inherit_neighbors", self._L.livo_scan_inherit_neighbors(self.h, dst, src))

@@ -31,6 +31,8 @@
  *   livo_cloud_colorize ← LaserMapping::publish_frame_world_rgb (the coloured cloud)
  *                                                   src/laser_mapping.cpp:1351-1381
  *   livo_vio_select     ← LidarSelector::addSparseMap (a frame's new visual map points)
+ *   livo_vmap_*         ← feat_map, imgs_ and the features' T_f_w_ (the resident visual map)
+ *   livo_vio_match      ← LidarSelector::addFromSparseMap (the visual map matched into a frame)
  *                                                   src/lidar_selection.cpp:117-221
  *
  * Conventions
@@ -56,13 +58,14 @@
 extern "C" {
 #endif
 
-/* 8: livo_vio_select added (nothing else changed).
+/* 9: the resident visual map (livo_vmap_*) and livo_vio_match added (nothing else changed).
+ * 8: livo_vio_select added (nothing else changed).
  * 7: livo_cloud_colorize added (nothing else changed).
  * 5: livo_ivox_info grew add_passes (round 4).
  * 4: livo_timings grew the per-evaluation fields (eval_ms ... gap_ms), LIVO_E_BUSY
  *    and the submit / wait pair were added (round 3); a binary built against 3
  *    passes a smaller livo_timings. */
-#define LIVO_ABI_VERSION 8
+#define LIVO_ABI_VERSION 9
 #define LIVO_DIM_STATE 18        /* DIM_STATE, include/common_lib.h:32 */
 #define LIVO_NUM_MATCH_POINTS 5  /* NUM_MATCH_POINTS, include/common_lib.h:37 */
 #define LIVO_MAX_EVALS 16        /* max h_share/solve evaluations per scan update */
@@ -590,6 +593,125 @@ typedef struct livo_vis_stats {
 int livo_vio_select(livo_ctx* ctx, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
                     int32_t grid_size, const uint8_t* gray, int32_t width, int32_t height,
                     livo_vis_point* out, float* patches, int64_t cap, int64_t* n, livo_vis_stats* stats);
+/* ------------------------------------------------------------------------
+ * The resident visual map (LidarSelector::feat_map, imgs_ and the features'
+ * T_f_w_): plain storage with no policy.  Points hold a position, a score, a
+ * voxel key and up to 20 observations (addObservation's cap, :945); an
+ * observation holds its frame id, px, f = cam2world(px), level and its patch
+ * pyramid (3 x patch_size^2 floats, Feature::patch layout); a frame holds its
+ * gray image and pose.  addObservation's decision logic (add_flag,
+ * getFurthestViewObs / deleteFeatureRef) and releasing frames are not here.
+ * ------------------------------------------------------------------------ */
+typedef struct livo_vmap_counts {
+    int64_t n_points, n_obs, n_frames;
+    int64_t max_points, max_frames;
+    int32_t patch_size;
+    int32_t width, height;           /* of the stored images (0 before the first frame)              */
+    int32_t pad_;
+} livo_vmap_counts;
+typedef struct livo_vmap_point {     /* 64 bytes */
+    double  pos[3];                  /* Point::pos_                                                   */
+    float   value;                   /* Point::value (the shiTomasi score)                            */
+    int32_t n_obs;                   /* observations, in list order from first_obs                    */
+    int64_t voxel[3];                /* AddPoint's VOXEL_KEY                                          */
+    int64_t first_obs;               /* index of its first observation in the dump                    */
+} livo_vmap_point;
+typedef struct livo_vmap_obs {       /* 48 bytes */
+    int32_t frame_id, level;         /* Feature::id_, Feature::level                                  */
+    double  px[2];                   /* Feature::px                                                   */
+    double  f[3];                    /* Feature::f = cam2world(px)                                    */
+} livo_vmap_obs;
+/* (Re)creates an empty map of fixed capacities: max_points points of at most
+ * 20 observations, max_frames frames, patches of patch_size (1..8) squared.
+ * LIVO_E_INVALID for a capacity < 1. */
+int livo_vmap_reset(livo_ctx* ctx, int64_t max_points, int64_t max_frames, int32_t patch_size);
+/* Stores a past image and its pose (frame_cam of p at state: Rcw, Pcw; the
+ * frame position -Rcw^T Pcw, in double) under frame_id (>= 0).  gray: 8-bit,
+ * width x height = p->cam.width x height, row stride width, copied into a
+ * buffer of the map's own; gray == NULL copies livo_vio_select's retained
+ * image device to device.  Every frame of a map has the first one's size and
+ * intrinsics source p->cam (undistorted: |d0| <= 1e-7).  LIVO_E_INVALID: no map,
+ * a distorted camera, a size mismatch, no retained image, a duplicate id;
+ * LIVO_E_CAPACITY: the store is full. */
+int livo_vmap_add_frame(livo_ctx* ctx, int32_t frame_id, const livo_state* state, const livo_vio_params* p,
+                        const uint8_t* gray, int32_t width, int32_t height);
+/* Adds n observations seen from stored frame frame_id.  point_ids == NULL
+ * creates n points from livo_vis_point records (addSparseMap's tail): pos_ =
+ * the record's float x, y, z widened, value = score, the voxel key = voxel,
+ * one observation with px = (u, v) at level 0; their ids, consecutive from the
+ * map's count, go to ids_out (n, may be NULL).  With point_ids, one
+ * observation is appended to each listed point in order (addFrameRef): px from
+ * the record's u, v, the level from levels (NULL: 0), the other fields
+ * ignored.  patches: n x 3 x patch_size^2 floats as livo_vio_select writes
+ * them.  f = ((u - cx) / fx, (v - cy) / fy, 1) normalised, in double, with the
+ * frame's intrinsics.  LIVO_E_INVALID: an unknown frame or id, a level outside
+ * 0..8; LIVO_E_CAPACITY: beyond max_points or 20 observations.  Nothing is
+ * written on an error. */
+int livo_vmap_add(livo_ctx* ctx, int32_t frame_id, int64_t n, const int32_t* point_ids, const livo_vis_point* pts,
+                  const int32_t* levels, const float* patches, int32_t* ids_out);
+int livo_vmap_info(livo_ctx* ctx, livo_vmap_counts* info);
+/* The map in id / list order: points (cap_points), obs (cap_obs) and patches
+ * (cap_obs x 3 x patch_size^2) may all be NULL to query *n_points and *n_obs,
+ * else the capacities must suffice (LIVO_E_RANGE otherwise, the counts set). */
+int livo_vmap_dump(livo_ctx* ctx, livo_vmap_point* points, int64_t cap_points, livo_vmap_obs* obs, float* patches,
+                   int64_t cap_obs, int64_t* n_points, int64_t* n_obs);
+
+/* LidarSelector::addFromSparseMap (src/lidar_selection.cpp:332-593, with
+ * getWarpMatrixAffine / getBestSearchLevel / warpAffine / NCC :224-318 and
+ * Point::getCloseViewObs, src/point.cpp:142-170): the resident visual map
+ * matched into the frame at `state`.  The cloud of livo_frame_to_world (same
+ * scan_id, x, y, z bit for bit; it stands for pg_down: the 0.2 m VoxelGrid in
+ * front is not run) gives the frame's 0.5 m voxel set and a depth image (on a
+ * shared pixel the last cloud index wins, as the reference's sequential loop);
+ * every map point whose stored key is in the set is projected, the nearest
+ * point of each grid cell (cur_dist <= 10000; the greatest id among equals) is
+ * tested for depth continuity, its observation of the closest view is chosen
+ * (cosine >= 0.5), that observation's patch is warped from its own stored
+ * image into the observation's stored level-0 patch (the reference aliases
+ * patch_wrap = ref_ftr->patch: livo_vmap_dump shows it) with the affine
+ * matrix and search level of the lowest cell that reached this step with the
+ * same reference frame (Warp_map's key is the frame id), and compared with
+ * the frame's level-0 patch: NCC (if ncc_en, rejected below ncc_thre) and the
+ * squared error (rejected above outlier_threshold * patch_size^2).  The
+ * survivors come in ascending cell index: out (records), pos (n x 3),
+ * search_levels (n) and patches (n x 3 x patch_size^2) exactly as
+ * livo_vio_update reads them.  DESIGN.md §8.9 has the arithmetic.
+ * gray and its reuse as livo_vio_select, in a buffer of this entry point's
+ * own.  LIVO_E_INVALID: no map (livo_vmap_reset), a distorted camera, a size
+ * or patch size that differs from the map's, an odd patch_size, grid_size < 1
+ * or a frame narrower than one cell inside the border.  An empty map gives
+ * *n = 0.  *n = survivors (set on LIVO_OK and LIVO_E_CAPACITY).  out == NULL
+ * with cap == 0 returns *n and the stats and leaves the map unchanged;
+ * otherwise out, pos, search_levels and patches are all needed, and cap < *n
+ * returns LIVO_E_CAPACITY with none of them written (the map's level-0
+ * patches are rewarped as by a successful call).  stats may be NULL.  Two
+ * calls on the same input give the same bytes. */
+typedef struct livo_vmatch_point {   /* 48 bytes */
+    int32_t point_id;                /* the map point                                                 */
+    int32_t cell;                    /* grid index i (sub_sparse_map->index)                          */
+    int32_t obs_index;               /* its chosen observation, in list order                         */
+    int32_t frame_id;                /* ... and that observation's frame                              */
+    int32_t search_level;
+    float   error;                   /* sub_sparse_map->errors                                        */
+    double  ncc;                     /* 0 when ncc_en is 0                                            */
+    double  u, v;                    /* pc = new_frame_->w2c(pt->pos_)                                */
+} livo_vmatch_point;
+typedef struct livo_vmatch_stats {
+    int64_t n_in;                    /* points of the source cloud                                    */
+    int64_t n_voxels;                /* distinct 0.5 m voxels of the cloud (sub_feat_map.size())      */
+    int64_t map_tested;              /* map points whose stored key is in the set                     */
+    int64_t in_frame;                /* of those: in front of the camera and inside the border        */
+    int64_t cell_overflow;           /* of those: index >= length (dropped)                           */
+    int64_t cells_marked;            /* cells of TYPE_MAP                                             */
+    int64_t depth_rejected, view_rejected, ncc_rejected, error_rejected;
+    int64_t warp_shared;             /* cells that took another cell's warp (same reference frame)    */
+    int64_t warp_nan;                /* cells whose inverse was NaN: the stored patch left as it was   */
+    int64_t n_out;                   /* survivors = *n                                                */
+} livo_vmatch_stats;
+int livo_vio_match(livo_ctx* ctx, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                   int32_t grid_size, int32_t ncc_en, double ncc_thre, double outlier_threshold,
+                   const uint8_t* gray, int32_t width, int32_t height, livo_vmatch_point* out, double* pos,
+                   int32_t* search_levels, float* patches, int64_t cap, int64_t* n, livo_vmatch_stats* stats);
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
