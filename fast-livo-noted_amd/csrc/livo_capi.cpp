@@ -43,6 +43,8 @@ struct ScanBuf {
     uint32_t* ikcnt = nullptr;  // per block
     bool searched = false;      // a search has filled the neighbour cache
     bool nn_compact = false;    // a fused batch may have stored hot-only records (kRecNoXyz): ensure_nn_coords
+    bool nn_lazy = false;       // the last fused search skipped records: ensure_nn_records rebuilds them ...
+    double nn_pose[12] = {};    // ... by the same search at its pose (rot, pos; IekfSlot::nn_pose)
     int64_t cap = 0;            // points the buffers were sized for (>= n; reused after a release)
     hipEvent_t ready = nullptr; // livo_scan_upload_async: recorded on the upload stream when the scan is built
     bool pending = false;       // an asynchronous upload may still be building it (get_scan waits)
@@ -257,7 +259,8 @@ struct BatchPlan {
     bool kcopy = false;  // staging copies by kernel over host-mapped memory (else DMA)
     bool wb = false;     // the stopping solve writes its slot into the host staging copy itself
     bool iv = false;     // iVox search (its own overflow replay lists)
-    int prof = 0;        // profiling level of this batch (0: no event is recorded)
+    bool lazy = false;   // fused: searches after the first skip unread records (KnnParams::rec_lazy)
+    int prof = 0;       // profiling level of this batch (0: no event is recorded)
     Staging* stage = nullptr;
     size_t stride = 0;   // bytes from one slot to the next
     int ngroups = 0;
@@ -409,6 +412,9 @@ struct livo_ctx {
     // the fused run searches on a static map store hot-only neighbour records, the
     // coordinates filled on demand (LIVO_REC_COMPACT=0: full records)
     bool rec_compact = true;
+    // ... and their later searches skip the records nothing in the loop reads; a scan's
+    // records are rebuilt on demand (ensure_nn_records; LIVO_REC_LAZY=0: stored)
+    bool rec_lazy = true;
     // LIVO_EVAL_GEN=1: every fused evaluation takes the generic kernel (the A/B and test reference
     // of the static-map specialisation)
     bool eval_gen = false;
@@ -429,6 +435,9 @@ struct livo_ctx {
     // scratch for livo_knn / debug outputs
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
+    // ensure_nn_records: the plane cache and plane states its launch writes (the scan's own stay)
+    void* rec_tmp = nullptr;
+    size_t rec_tmp_bytes = 0;
     // profiling
     int profiling = 0;
     hipEvent_t ev[kMaxGroups][3 * LIVO_MAX_EVALS + 2] = {};
@@ -530,7 +539,9 @@ static bool any_inflight(const livo_ctx* c) {
 // neighbour records gets their cold halves on `st`, ahead of a consumer on that
 // stream that reads coordinates from the records.  (The keys index the cell
 // grid as it is now: fill_all_nn_coords runs before anything replaces it.)
+static int ensure_nn_records(livo_ctx* c, ScanBuf* s, hipStream_t st);
 static int ensure_nn_coords(livo_ctx* c, ScanBuf* s, hipStream_t st) {
+    RC_TRY(ensure_nn_records(c, s, st));  // (skipped records first: they come back whole)
     if (!s->nn_compact) return LIVO_OK;
     s->nn_compact = false;
     if (s->n == 0 || !c->gpts) return LIVO_OK;
@@ -633,6 +644,7 @@ static KnnParams make_knn_params(livo_ctx* c) {
     kp.iv = ivox_params(c);
     kp.canon = c->dyn.active ? 1 : 0;
     kp.rec_compact = (c->rec_compact && vr && !c->dyn.active) ? 1 : 0;
+    kp.rec_lazy = (kp.rec_compact && c->rec_lazy && !c->eval_gen) ? 1 : 0;
     kp.eval_gen = c->eval_gen ? 1 : 0;
     return kp;
 }
@@ -765,6 +777,45 @@ static void init_slot(IekfSlot& s, const livo_state& st, const livo_state& prior
     s.ctrl.rematch_num = 0;
     s.ctrl.max_iter = max_iter;
     cov_factor(s);
+}
+
+// Records on demand: a scan whose last fused search left out the records nothing in the
+// loop read (nn_lazy) gets all of them back -- the same search again, at the pose that
+// search ran at (nn_pose), against the map as it still is (every caller that changes the
+// map comes here first, fill_all_nn_coords).  One k_iekf_eval<false> launch that searches,
+// stores full records (rec_compact off: both halves, as LIVO_REC_COMPACT=0 stores them),
+// replays its flagged queries and stops at the sums (no solve): deterministic, so the
+// bytes are those the loop's search would have stored.  The launch's plane cache and plane
+// states go to a buffer of the context's: the scan's own stay as the loop left them (an
+// evaluation after the last search may have fitted planes the search left at state 0).
+// Finished on `st` before it returns: the staging slot and that buffer are the context's.
+static int ensure_nn_records(livo_ctx* c, ScanBuf* s, hipStream_t st) {
+    if (!s->nn_lazy) return LIVO_OK;
+    s->nn_lazy = false;
+    if (!s->searched || s->n == 0) return LIVO_OK;  // (invalidated records: searched again before any read)
+    RC_TRY(ensure_slot(c));
+    RC_TRY(ensure_replay(c, s->n));
+    livo_state pose{};
+    std::memcpy(pose.rot, s->nn_pose, 9 * sizeof(double));
+    std::memcpy(pose.pos, s->nn_pose + 9, 3 * sizeof(double));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (an earlier user of the staging slot)
+    const size_t plane_b = ((size_t)s->n * 16 + 255) & ~(size_t)255;
+    RC_TRY(ensure_dev_bytes(&c->rec_tmp, &c->rec_tmp_bytes, plane_b + (size_t)s->n));
+    init_slot(c->h_slots[0], pose, pose, c->params.max_iterations);
+    fill_job(c->h_jobs[0], *s, c->d_slots);
+    c->h_jobs[0].plane = (float*)c->rec_tmp;
+    c->h_jobs[0].pstate = (uint8_t*)c->rec_tmp + plane_b;
+    HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_jobs, c->h_jobs, sizeof(HsJob), hipMemcpyHostToDevice, st));
+    KnnParams kp = make_knn_params(c);
+    kp.rec_compact = 0;
+    kp.rec_lazy = 0;
+    HsParams hp = make_hs_params(c);
+    hp.solve = 0;
+    RC_TRY(launch_iekf_eval(kp, hp, 1, s->n, false, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s->nn_compact = false;  // (full records)
+    return LIVO_OK;
 }
 
 static int create_group_streams(livo_ctx* c) {
@@ -1907,6 +1958,7 @@ int livo_ctx_create(int device, const livo_params* p, livo_ctx** out) {
     if (const char* env = std::getenv("LIVO_LANE_SERIAL")) c->lane_serial = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_SLOT_WB")) c->slot_wb = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_REC_COMPACT")) c->rec_compact = std::atoi(env) != 0;
+    if (const char* env = std::getenv("LIVO_REC_LAZY")) c->rec_lazy = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_EVAL_GEN")) c->eval_gen = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_XCD_CHUNK")) c->xcd_chunk = std::max(0, std::atoi(env));  // tuning knob
     if (const char* env = std::getenv("LIVO_GRID_PPC")) {  // tuning knob
@@ -1986,6 +2038,7 @@ int livo_ctx_destroy(livo_ctx* c) {
             if (e) (void)hipEventDestroy(e);
     }
     if (c->scratch) (void)hipFree(c->scratch);
+    if (c->rec_tmp) (void)hipFree(c->rec_tmp);
     if (c->events_ready) {
         for (auto& g : c->ev)
             for (auto& e : g) (void)hipEventDestroy(e);
@@ -2590,7 +2643,7 @@ static int alloc_scan_buf(livo_ctx* c, ScanBuf& s, int64_t N) {
     }
     s.used = true;
     s.searched = false;
-    s.nn_compact = false;
+    s.nn_compact = s.nn_lazy = false;
     s.n = N;
     s.nblk = (int32_t)std::max<int64_t>(1, (N + kBlock * kPtsPerThread - 1) / (kBlock * kPtsPerThread));
     s.pending = false;
@@ -3138,6 +3191,7 @@ int livo_scan_neighbors(livo_ctx* c, int32_t id, int32_t* idx, float* sqdist) {
     for (const BatchLane& B : c->lane)
         if (B.busy && std::find(B.ids.begin(), B.ids.end(), id) != B.ids.end()) return LIVO_E_BUSY;
     if (set_device(c)) return LIVO_E_HIP;
+    RC_TRY(ensure_nn_records(c, s, c->stream));  // (the records the last fused search left out)
     std::vector<NNRec> rec((size_t)s->n);
     if (s->n > 0) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3463,8 +3517,12 @@ static void group_params(livo_ctx* c, int L, const BatchPlan& P, int gi, KnnPara
 // The fused loop: one launch per evaluation and group (a launch whose scans all stopped exits at once).
 static int queue_fused(livo_ctx* c, const BatchPlan& P, const int32_t* ids, const KnnParams* kp, const HsParams* hp) {
     // (rec_compact: the ikd-Tree backend's run searches on a static map, the only writer of hot-only records)
-    if (kp[0].rec_compact)
-        for (int32_t b = 0; b < P.n; b++) get_scan_q(c, ids[b])->nn_compact = true;
+    // (a new update replaces what an earlier one left to rebuild: batch_collect flags its own)
+    for (int32_t b = 0; b < P.n; b++) {
+        ScanBuf* s = get_scan_q(c, ids[b]);
+        s->nn_lazy = false;
+        if (kp[0].rec_compact) s->nn_compact = true;
+    }
     const int evals = c->params.max_iterations + 1;
     for (int e = 0; e < evals; e++)
         for (int gi = 0; gi < P.ngroups; gi++) {
@@ -3544,7 +3602,7 @@ static int prof_batch_end(livo_ctx* c, const BatchPlan& P) {
 // searched again before anything reads them (livo_scan_neighbors: LIVO_E_NOSCAN).
 static void batch_records_invalid(livo_ctx* c, int32_t n, const int32_t* ids) {
     for (int32_t b = 0; b < n; b++)
-        if (ScanBuf* s = get_scan_q(c, ids[b])) s->searched = false;
+        if (ScanBuf* s = get_scan_q(c, ids[b])) s->searched = s->nn_lazy = false;
 }
 
 static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int model, const livo_state* states,
@@ -3573,6 +3631,7 @@ static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int 
         KnnParams kp[kMaxGroups];
         HsParams hp[kMaxGroups];
         for (int gi = 0; gi < P.ngroups; gi++) group_params(c, L, P, gi, kp[gi], hp[gi]);
+        B.plan.lazy = P.fused && kp[0].rec_lazy != 0;
         RC_TRY(P.fused ? queue_fused(c, P, ids, kp, hp) : queue_unfused(c, P, kp, hp));
         for (int gi = 0; gi < P.ngroups; gi++) RC_TRY(finish_group(c, B, P, gi));
         return prof_batch_end(c, P);
@@ -3689,7 +3748,15 @@ static int batch_collect(livo_ctx* c, int L, livo_state* states, livo_iter_stats
             states[b] = s.state;
             if (stats) stats[b] = s.stats;
         }
-        c->scans[ids[b]].searched = true;
+        ScanBuf& sc = c->scans[ids[b]];
+        sc.searched = true;
+        // a scan whose last search was not the loop's first left out the records no lane
+        // read (k_iekf_eval<false>, rec_lazy): its pose stays with the scan, for ensure_nn_records
+        int last = 0;
+        for (int e = 0; e < std::min<int>(s.ctrl.n_evals, LIVO_MAX_EVALS); e++)
+            if (s.eval_search[e]) last = e;
+        sc.nn_lazy = P.lazy && last > 0;
+        if (sc.nn_lazy) std::memcpy(sc.nn_pose, s.nn_pose, sizeof(sc.nn_pose));
     }
     if (P.prof) batch_timings(c, P, ids.data(), c->last_replays);
     return LIVO_OK;
@@ -3989,11 +4056,11 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
     uint32_t* flags = (uint32_t*)(base + ob);
     uint32_t* pos = (uint32_t*)(base + ob + fb);
     uint8_t* dcat = (uint8_t*)(base + ob + 2 * fb);
+    rc = ensure_nn_coords(c, s, c->stream);  // (first: rebuilding skipped records takes the staging slot)
+    if (rc) return rc;
     init_slot(c->h_slots[0], *state, *state, c->params.max_iterations);
     HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(flags, 0, fb, c->stream));
-    rc = ensure_nn_coords(c, s, c->stream);
-    if (rc) return rc;
     MapIncrParams mp{};
     mp.pts = s->pts;
     mp.nn = s->nn;
@@ -4047,7 +4114,7 @@ int livo_scan_inherit_neighbors(livo_ctx* c, int32_t dst, int32_t src) {
     if (d->n == 0) return LIVO_OK;
     int rc = s->searched ? ensure_nn_coords(c, s, c->stream) : LIVO_OK;  // (whole records are copied)
     if (rc) return rc;
-    d->nn_compact = false;
+    d->nn_compact = d->nn_lazy = false;
     rc = launch_inherit_nn(d->nn, d->d_perm, d->n, s->nn, s->d_iperm, s->searched ? s->n : 0, c->stream);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(d->pstate, 0, (size_t)d->n, c->stream));  // new neighbours: planes to refit

@@ -271,6 +271,10 @@ struct alignas(128) IekfSlot {
     unsigned hs_ticket;         // reduction shards done in the current pass (the last one solves; IKFoM: blocks)
     int32_t model;              // SlotModel
     unsigned pad_[2];
+    // The pose the scan's last search ran at (rot, pos: the doubles its queries were
+    // transformed with), kept by solve_scan before its boxplus: the host rebuilds the
+    // records that search skipped from it (ensure_nn_records)
+    double nn_pose[12];
     // Factors of the state covariance, made by the host when it stages the slot
     // (init_slot; the covariance changes only when the scan's loop stops):
     // S = P(0:6, 0:6) = L L^T (Cholesky, row-major 6x6, zero above the diagonal)
@@ -415,6 +419,9 @@ struct KnnParams {
     // k_iekf_eval's run searches on a static map store the records' hot halves only
     // (kRecNoXyz; LIVO_REC_COMPACT=0: full records)
     int32_t rec_compact;
+    // ... and its later searches leave out the records that nothing in the loop reads; the
+    // host rebuilds a scan's records on demand (ensure_nn_records; LIVO_REC_LAZY=0: stored)
+    int32_t rec_lazy;
     int32_t eval_gen;       // 1: launch_iekf_eval takes the generic kernel whatever the map (LIVO_EVAL_GEN=1)
 };
 

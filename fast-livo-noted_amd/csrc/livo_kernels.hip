@@ -866,7 +866,8 @@ __device__ unsigned long long g_amb_reason[8];
 // lane l's half at l * 4 + ((k + (l >> 2)) & 3), so that 16 consecutive lanes'
 // 16-B writes of one part cover all 64 banks.
 __device__ __forceinline__ int rec_stage_slot(int l, int k) { return l * 4 + ((k + (l >> 2)) & 3); }
-// Whether a lane's record of a search is read before the scan's next search rewrites it:
+// Whether a lane's record of a search is read inside the loop (before the scan's next
+// search, or its end: the host rebuilds what a caller asks for afterwards):
 // a flagged query's replay reads its record back, and a full list beyond the sqdist gate
 // leaves plane state 0 (fit_plane), which the next evaluation fits from the record.
 // (A short list, d5 = +inf, counts too: that costs a store, never a missing record.)
@@ -2426,6 +2427,8 @@ __device__ __forceinline__ int solve_scan(IekfSlot* slot, SolveLds& L, const int
         // the loop condition iterCount < NUM_MAX_ITERATIONS (:178) also ends it
         ctrl.stop = (stop || ctrl.iter_count >= ctrl.max_iter || ctrl.n_evals >= LIVO_MAX_EVALS) ? 1 : 0;
         stop_now = stop ? 1 : 0;
+        // an evaluation that searched: its pose (rot, pos) stays with the slot (nn_pose)
+        if (searched && lane < 12) st_sc1(slot->nn_pose + lane, L.st.rot[lane]);
         if (lane < 9) {  // mat3_mul(rot, E) entry (r, c), sums in index order
             const int r = lane / 3, c = lane % 3;
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
@@ -3198,13 +3201,19 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
     // NUM_MAX_ITERATIONS >= 2 and room for all its evaluations -- solve_scan then stops
     // no scan before its second search -- and no debug output.  Block-uniform, from
     // kernel parameters and the control block read above.
+    // A later search's records are dead whenever the host rebuilds records on demand
+    // (rec_lazy, ensure_nn_records: the same search again at the pose solve_scan keeps
+    // in nn_pose): the loop itself reads only what rec_needed keeps.
     bool dead = false;
 #ifndef LIVO_EVAL_PROF
-    if constexpr (FIRST && kStatic) {
+    if constexpr (kStatic) {
         const IekfCtrl& c = slot->ctrl;
-        dead = P.rec_compact && E.h.solve && !E.h.dbg.normvec && !E.h.dbg.world && !E.h.dbg.sel &&
-               c.max_iter >= 2 && c.max_iter + 1 <= LIVO_MAX_EVALS && c.iter_count == -1 && c.rematch_num == 0 &&
-               c.n_evals == 0;
+        dead = P.rec_compact && E.h.solve && !E.h.dbg.normvec && !E.h.dbg.world && !E.h.dbg.sel;
+        if constexpr (FIRST)
+            dead = dead && c.max_iter >= 2 && c.max_iter + 1 <= LIVO_MAX_EVALS && c.iter_count == -1 &&
+                   c.rematch_num == 0 && c.n_evals == 0;
+        else
+            dead = dead && P.rec_lazy;
     }
 #endif
     const PoseRef pose{slot->state.rot, slot->state.pos};

@@ -225,7 +225,16 @@ int livo_scan_release(livo_ctx* ctx, int32_t scan_id);
  * idx: N x 5 map indices (-1 pad); sqdist: N x 5 (+inf pad); either may be NULL.
  * LIVO_E_NOSCAN if the scan was never searched, or if the last batched update
  * on it failed with LIVO_E_HIP after some of its launches were queued (its
- * records are then no single search's answer, see livo_iekf_update_batch). */
+ * records are then no single search's answer, see livo_iekf_update_batch).
+ * Cost: after a batched update on a static map (livo_map_build, no point added or
+ * deleted since) the loop's last search has stored only the records the loop itself
+ * read.  The first call that reads a scan's records afterwards -- this one,
+ * livo_h_share, livo_scan_inherit_neighbors, livo_map_incremental, an unfused,
+ * iVox or IKFoM update of the scan, or a change of the map or backend, which
+ * does it for every such scan -- runs that scan's search once more, at the pose
+ * of its last search, and leaves the same records a stored search would have;
+ * later calls cost nothing.  LIVO_REC_LAZY=0 (read when the context is created)
+ * stores them in the loop instead. */
 int livo_scan_neighbors(livo_ctx* ctx, int32_t scan_id, int32_t* idx, float* sqdist);
 
 /* One h_share_model evaluation on a resident scan at the given state.
