@@ -2,50 +2,25 @@
 front-end section).
 
 Parity status: "parity unpinned" against the reference itself (ROS/PCL/Eigen
-absent; the reference ships no fixtures).  Pinned against independent numpy
-restatements of the documented behaviour:
+absent; the reference ships no fixtures).  Pinned against the independent numpy
+restatements of the documented behaviour in oracle/frontend_ref.py (on the edge
+inputs, with derived bars: tests/test_frontend_reference.py):
   * UndistortPcl's backward walk (IMU_Processing.cpp:340-378), including the
     first point being re-compensated by every remaining IMU segment (the inner
     loop breaks at begin() without stepping) and points at or before the first
     pose untouched;
   * PCL VoxelGrid::applyFilter: leaf indices, voxel order (ascending index),
     point counts exact; centroids to float rounding (the reference sums a
-    voxel in std::sort's unstable order; numpy here sums in input order).
+    voxel in std::sort's unstable order; the restatement's centroid is the
+    float64 mean).
 """
 import numpy as np
 
-
-def _exp(g, dt):
-    n = np.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
-    if n <= 1e-7:
-        return np.eye(3)
-    r = g / n
-    K = np.array([[0, -r[2], r[1]], [r[2], 0, -r[0]], [-r[1], r[0], 0]])
-    a = n * dt
-    return np.eye(3) + np.sin(a) * K + ((1 - np.cos(a)) * K) @ K
+import frontend_ref as fr
 
 
 def _undistort_np(raw, poses, Re, pe, RLI, tLI):
-    p = raw.astype(np.float32).copy()
-    extR = RLI.T @ Re.T
-    ext_t = RLI.T @ tLI
-    it = len(p) - 1
-
-    def comp(i, h):
-        dt = float(p[i, 4]) / 1000.0 - h[0]
-        Ri = h[13:22].reshape(3, 3) @ _exp(h[4:7], dt)
-        T = h[10:13] + h[7:10] * dt + 0.5 * h[1:4] * dt * dt - pe
-        c = extR @ (Ri @ (RLI @ p[i, :3].astype(np.float64) + tLI) + T) - ext_t
-        p[i, :3] = c.astype(np.float32)
-
-    for kp in range(len(poses) - 1, 0, -1):
-        h = poses[kp - 1]
-        while float(p[it, 4]) / 1000.0 > h[0]:
-            comp(it, h)
-            if it == 0:
-                break
-            it -= 1
-    return p
+    return fr.undistort(raw, poses, Re, pe, RLI, tLI)[0]
 
 
 def test_undistort_matches_numpy(built):
@@ -72,41 +47,18 @@ def test_undistort_first_point_recompensated(built):
     assert np.allclose(got, exp, rtol=0, atol=2e-6)
     # point 1 moved once, with the last pose before its time
     h = poses[int(np.searchsorted(poses[:, 0], raw[1, 4] / 1000.0)) - 1]
-    dt = float(raw[1, 4]) / 1000.0 - h[0]
-    Ri = h[13:22].reshape(3, 3) @ _exp(h[4:7], dt)
-    T = h[10:13] + h[7:10] * dt + 0.5 * h[1:4] * dt * dt - pe
-    once = Re.T @ (Ri @ (raw[1, :3].astype(np.float64) + synth.T_LI) + T) - synth.T_LI
+    once = fr.compensate(raw[1:2, :3], raw[1:2, 4], h, Re, pe, np.eye(3), synth.T_LI)[0][0]
     assert np.allclose(got[1, :3], once, atol=2e-6)
     # point 0 moved by its segment and every earlier one: not the single move
     h0 = poses[int(np.searchsorted(poses[:, 0], raw[0, 4] / 1000.0)) - 1]
-    dt0 = float(raw[0, 4]) / 1000.0 - h0[0]
-    R0 = h0[13:22].reshape(3, 3) @ _exp(h0[4:7], dt0)
-    T0 = h0[10:13] + h0[7:10] * dt0 + 0.5 * h0[1:4] * dt0 * dt0 - pe
-    once0 = Re.T @ (R0 @ (raw[0, :3].astype(np.float64) + synth.T_LI) + T0) - synth.T_LI
+    once0 = fr.compensate(raw[0:1, :3], raw[0:1, 4], h0, Re, pe, np.eye(3), synth.T_LI)[0][0]
     assert np.abs(got[0, :3] - once0).max() > 1e-3
 
 
 def _voxel_np(raw, leaf):
-    leaf = np.float32(leaf)
-    inv = np.float32(1.0) / leaf
-    mn = raw[:, :3].min(0)
-    mx = raw[:, :3].max(0)
-    d = ((mx - mn) * inv).astype(np.int64) + 1
-    assert np.prod(d) <= 2 ** 31 - 1
-    mnb = np.floor(mn * inv).astype(np.int64)
-    mxb = np.floor(mx * inv).astype(np.int64)
-    div = mxb - mnb + 1
-    ijk = (np.floor(raw[:, :3] * inv) - mnb.astype(np.float32)).astype(np.int64)
-    idx = (ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]).astype(np.uint32)
-    o = np.argsort(idx, kind="stable")
-    keys, start, cnt = np.unique(idx[o], return_index=True, return_counts=True)
-    out = np.zeros((len(keys), 5), np.float32)
-    for k, (s, c) in enumerate(zip(start, cnt)):
-        acc = np.zeros(5, np.float32)
-        for j in o[s:s + c]:
-            acc += raw[j]
-        out[k] = acc / np.float32(c)
-    return out, cnt
+    v = fr.voxel_grid(raw, leaf)
+    assert v.filtered
+    return v.centroid.astype(np.float32), v.count
 
 
 def test_voxel_grid_matches_numpy(built):

@@ -7,6 +7,11 @@ rounding); VoxelGrid voxel set, order and counts exact, centroids to float
 rounding (the reference sums a voxel in std::sort's unstable order); the
 resident scan it creates is the scan livo_scan_upload makes of the same
 points (same device Morton order: IEKF results bit-identical).
+
+These cases run synth.make_raw_scan alone: sorted times, no point on a segment
+boundary, identity R_LI.  tests/test_gpu_frontend_edges.py holds the same entry
+points to the plain reference oracle/frontend_ref.py on unsorted times, exact
+boundaries, tilted extrinsics and VoxelGrid's edges, with derived bars.
 """
 import numpy as np
 import pytest
