@@ -231,7 +231,14 @@ struct Staging {
     int ensure(size_t bytes) {
         if (bytes <= cap) return LIVO_OK;
         free();
-        if (hipMalloc((void**)&d, bytes) != hipSuccess) {
+        // zeroed: a group staged inline (BatchPlan::Group::inl) never copies the slots' ticket
+        // lines in; they start at 0 here and every pass's completers leave them at 0
+        // (the fill runs on the null stream, which the lanes' non-blocking streams do not wait
+        // for: it is finished here, before the batch that asked for the area queues its copies)
+        if (hipMalloc((void**)&d, bytes) != hipSuccess || hipMemset(d, 0, bytes) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess) {
+            (void)hipGetLastError();
+            if (d) (void)hipFree(d);
             d = nullptr;
             return LIVO_E_OOM;
         }
@@ -269,6 +276,7 @@ struct BatchPlan {
         int max_nblk;
         int64_t max_n, off;  // off: the group's start in the lane's replay list
         hipStream_t st;
+        bool inl;            // staged in its launches' arguments (EvalInline): no staging copy on its stream
     } g[kMaxGroups];
 };
 
@@ -409,6 +417,7 @@ struct livo_ctx {
     // the other groups' tails (20.5k vs 19.1k updates/s, profiles/r03_ab_lanes.txt)
     bool lane_serial = false;
     bool slot_wb = true;            // fused batches: the stopping solve writes the slot back (LIVO_SLOT_WB)
+    bool stage_copy = false;        // submitted fused batches stage by copy kernel as before (LIVO_STAGE_COPY=1)
     // the fused run searches on a static map store hot-only neighbour records, the
     // coordinates filled on demand (LIVO_REC_COMPACT=0: full records)
     bool rec_compact = true;
@@ -1957,6 +1966,7 @@ int livo_ctx_create(int device, const livo_params* p, livo_ctx** out) {
     }
     if (const char* env = std::getenv("LIVO_LANE_SERIAL")) c->lane_serial = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_SLOT_WB")) c->slot_wb = std::atoi(env) != 0;
+    if (const char* env = std::getenv("LIVO_STAGE_COPY")) c->stage_copy = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_REC_COMPACT")) c->rec_compact = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_REC_LAZY")) c->rec_lazy = std::atoi(env) != 0;
     if (const char* env = std::getenv("LIVO_EVAL_GEN")) c->eval_gen = std::atoi(env) != 0;
@@ -3429,6 +3439,10 @@ static int64_t batch_plan(livo_ctx* c, int L, int32_t n, const int32_t* ids, int
         G.max_n = 1;
         G.off = off;
         G.st = B.st[gi];
+        // a submitted fused batch's group of at most kInlineJobs scans: jobs, pose and control in
+        // the launches' arguments, the slot through the first solve (a larger group: the copy kernel)
+        // (P.wb: the jobs carry their slots' host-mapped addresses, HsJob::host_slot)
+        G.inl = P.fused && P.kcopy && P.wb && !c->stage_copy && G.count <= kInlineJobs;
         for (int32_t b = G.first; b < G.first + G.count; b++) {
             const ScanBuf* s = get_scan_q(c, ids[b]);
             G.max_nblk = std::max(G.max_nblk, (int)s->nblk);
@@ -3481,7 +3495,9 @@ static int stage_group(livo_ctx* c, int L, const BatchPlan& P, int gi, const int
         for (int q = 0; q < prev->plan.ngroups; q++) HIP_TRY(hipStreamWaitEvent(st, prev->done[q], 0));
     const size_t s0 = (size_t)G.first * P.stride, sb = (size_t)G.count * P.stride;
     const size_t j0 = (size_t)P.n * P.stride + (size_t)G.first * sizeof(HsJob), jb = (size_t)G.count * sizeof(HsJob);
-    if (P.kcopy) {
+    if (G.inl) {
+        // (nothing to copy: queue_fused puts the group's jobs and slot heads into its launches)
+    } else if (P.kcopy) {
         RC_TRY(launch_copy_ranges(P.stage->h_dev, P.stage->d, s0, sb, j0, jb, st));
     } else {
         HIP_TRY(hipMemcpyAsync(P.stage->d + s0, P.stage->h + s0, sb, hipMemcpyHostToDevice, st));
@@ -3524,12 +3540,31 @@ static int queue_fused(livo_ctx* c, const BatchPlan& P, const int32_t* ids, cons
         if (kp[0].rec_compact) s->nn_compact = true;
     }
     const int evals = c->params.max_iterations + 1;
+    // the groups staged inline: the host copies of their jobs, and for the first launch the
+    // pose and control block of each slot and where its first solve finds the rest
+    EvalInline inl[kMaxGroups];
+    const HsJob* const hjobs = reinterpret_cast<const HsJob*>(P.stage->h + (size_t)P.n * P.stride);
+    for (int gi = 0; gi < P.ngroups; gi++) {
+        const BatchPlan::Group& G = P.g[gi];
+        if (!G.inl) continue;
+        EvalInline& I = inl[gi];
+        std::memset(&I, 0, sizeof(I));
+        I.n = G.count;
+        for (int32_t k = 0; k < G.count; k++) {
+            const IekfSlot& s = hslot(P, G.first + k);
+            I.jobs[k] = hjobs[G.first + k];
+            std::memcpy(I.head[k].rot, s.state.rot, sizeof(I.head[k].rot));
+            std::memcpy(I.head[k].pos, s.state.pos, sizeof(I.head[k].pos));
+            I.head[k].ctrl = s.ctrl;
+        }
+    }
     for (int e = 0; e < evals; e++)
         for (int gi = 0; gi < P.ngroups; gi++) {
             const BatchPlan::Group& G = P.g[gi];
             // level 2: ev[gi][e] before evaluation e, ev[gi][evals] after the last (finish_group)
             if (e > 0) HIP_TRY(prof_record(P, kProfL2, c->ev[gi][e], G.st));
-            RC_TRY(launch_iekf_eval(kp[gi], hp[gi], G.count, G.max_n, e == 0, G.st));
+            if (G.inl) inl[gi].first_in = e == 0;
+            RC_TRY(launch_iekf_eval(kp[gi], hp[gi], G.count, G.max_n, e == 0, G.st, G.inl ? &inl[gi] : nullptr));
             if (e == 0) HIP_TRY(prof_record(P, kProfL1, c->ev[gi][1], G.st));
         }
     return LIVO_OK;

@@ -466,7 +466,34 @@ enum EvalKind : int { kEvalRunsStatic = 0, kEvalGeneric = 1 };
 #ifndef LIVO_EVAL_WAVES
 #define LIVO_EVAL_WAVES 5  // waves per SIMD the static kernel's VGPR budget must allow (<= 96 VGPRs)
 #endif
-int launch_iekf_eval(const KnnParams& kp, const HsParams& hp, int n_jobs, int64_t max_n, bool first, void* stream);
+// A stream group staged in the launches themselves (inline staging): its
+// jobs ride in every launch's arguments, and the FIRST launch also carries what its
+// blocks read of each slot before the tail -- the pose and the control block -- so no
+// copy precedes the group's chain.  The device slot is filled by the first solve, from
+// the slot's host-mapped staging copy (HsJob::host_slot, which such a group's jobs all set).
+constexpr int kInlineJobs = 4;  // scans of a group staged this way (more: the copy kernel, P.jobs)
+struct alignas(16) EvalHead {
+    double rot[9], pos[3];  // state.rot, state.pos
+    IekfCtrl ctrl;          // the loop's start state (init_slot)
+};
+static_assert(sizeof(EvalHead) == 128, "128 B a scan");
+struct EvalInline {
+    int32_t n;              // > 0: jobs[0, n) are the launch's jobs (KnnParams / HsParams::jobs unused)
+    int32_t first_in;       // the FIRST launch: head[] set; each scan's first solve reads its job's host_slot (the
+                            // staging copy the host wrote before the launch) and fills the device slot
+    int32_t pad_[2];
+    HsJob jobs[kInlineJobs];
+    EvalHead head[kInlineJobs];
+};
+struct EvalParams {
+    KnnParams k;
+    HsParams h;
+    EvalInline in;
+};
+static_assert(sizeof(EvalParams) <= 4096, "kernel arguments: one 4-KB segment");
+// inl: null, or a group of inl->n == n_jobs <= kInlineJobs scans staged inline
+int launch_iekf_eval(const KnnParams& kp, const HsParams& hp, int n_jobs, int64_t max_n, bool first, void* stream,
+                     const EvalInline* inl = nullptr);
 int launch_solve_ik(const HsParams& p, int n_jobs, void* stream);
 int launch_copy_words(const void* src, void* dst, size_t bytes, void* stream);  // 16-B aligned, bytes % 16 == 0
 // bytes [o0, o0 + n0) and [o1, o1 + n1) of src to the same offsets of dst, one launch (16-B aligned)

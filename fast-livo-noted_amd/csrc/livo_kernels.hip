@@ -2796,6 +2796,43 @@ __device__ __forceinline__ void hs_host_slot(const HsJob& job, const IekfSlot* s
     }
 }
 
+// An inline-staged scan's slot, from its host-mapped staging copy (src, written by the
+// host before the launch) to the device slot, by threads t of nt of the block that
+// solves the scan first: every byte below the shard tickets -- the inputs later solves
+// read (prior, covariance, its factors), the zeroed statistics and counters, the words
+// this solve stores again afterwards -- all loads in flight before the first store.
+//  - Ticket lines: the shard tickets lie outside the range, and the scan's ticket
+//    (hs_ticket) is written with the host's 0 when every arrival of this pass has been
+//    counted (the caller is the block that took the last one); both are reset by their
+//    completers as in every pass, and start at 0 in a zeroed staging area.
+//  - Hand-off invariant: sc1 stores; the caller drains them (s_waitcnt
+//    vmcnt(0)) ahead of a block barrier, so this block's later stores to the same words
+//    land after them and a stopping scan's read-back (hs_host_slot: sc1 loads after that
+//    barrier) sees them.  No other workgroup of the launch reads the slot.
+//  - Slot aliasing: src is also hs_host_slot's target when the scan stops at this
+//    solve.  Every load of src (here and in solve_stage) has returned before that same
+//    barrier, which every thread passes before hs_host_slot's first store.
+constexpr int kSlotThroughWords = (int)(offsetof(IekfSlot, sh_ticket) / 8);
+static_assert(offsetof(IekfSlot, sh_ticket) % 8 == 0 && offsetof(IekfSlot, sh_ticket) + sizeof(IekfSlot::sh_ticket) == kSlotLmBytes,
+              "the shard tickets end the LaserMapping slot");
+template <int NT>
+__device__ __forceinline__ void slot_through_t(const IekfSlot* src, IekfSlot* slot, int t) {
+    constexpr int kPer = (kSlotThroughWords + NT - 1) / NT;
+    const unsigned long long* s = reinterpret_cast<const unsigned long long*>(src);
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(slot);
+    unsigned long long v[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const int w = t + k * NT;
+        v[k] = w < kSlotThroughWords ? ld_sc1(s + w) : 0ull;
+    }
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const int w = t + k * NT;
+        if (w < kSlotThroughWords) st_sc1(d + w, v[k]);
+    }
+}
+
 // The block partial of one 256-point chunk (blk): the row butterflies into R.red,
 // then wave 0's fixed pairwise tree over the rows, stored write-through (sc1).
 // Ends with wave 0's stores issued; a caller that reuses R.red must barrier first.
@@ -2828,7 +2865,7 @@ __device__ __forceinline__ void hs_scan_tail(const HsParams& P, const HsJob& job
 #ifdef LIVO_TAIL_PROF
                                              , unsigned long long tp
 #endif
-);
+                                             , bool first_in = false);
 
 // Block partials of a scan's h_share sums -> a two-level fixed-order reduction
 // -> (P.solve) the scan's solve.  nblk = partials (256-point chunks) of the scan
@@ -2912,7 +2949,8 @@ __device__ __forceinline__ bool hs_shard_level(const HsJob& job, IekfSlot* slot,
 
 template <int NT, int NU = kRedUsed>
 __device__ __forceinline__ void hs_ticket_tail(const HsParams& P, const HsJob& job, IekfSlot* slot, int nblk,
-                                               unsigned blk, HsReduceLds& R, SolveLds& L, int pk = -1) {
+                                               unsigned blk, HsReduceLds& R, SolveLds& L, int pk = -1,
+                                               bool first_in = false) {
     const int tid = threadIdx.x;
 #ifdef LIVO_TAIL_PROF
     unsigned long long tp = __builtin_amdgcn_s_memtime();
@@ -2930,9 +2968,9 @@ __device__ __forceinline__ void hs_ticket_tail(const HsParams& P, const HsJob& j
     __syncthreads();
     if (!R.last2) return;
 #ifdef LIVO_TAIL_PROF
-    hs_scan_tail<NT, NU>(P, job, slot, K, R, L, pk, tp);
+    hs_scan_tail<NT, NU>(P, job, slot, K, R, L, pk, tp, first_in);
 #else
-    hs_scan_tail<NT, NU>(P, job, slot, K, R, L, pk);
+    hs_scan_tail<NT, NU>(P, job, slot, K, R, L, pk, first_in);
 #endif
 }
 
@@ -2944,7 +2982,7 @@ __device__ __forceinline__ void hs_scan_tail(const HsParams& P, const HsJob& job
 #ifdef LIVO_TAIL_PROF
                                              , unsigned long long tp
 #endif
-) {
+                                             , bool first_in) {
     const int tid = threadIdx.x;
     // the scan's serial tail (reduction, solve) ahead of the other waves on its SIMDs
     __builtin_amdgcn_s_setprio(3);
@@ -2953,7 +2991,12 @@ __device__ __forceinline__ void hs_scan_tail(const HsParams& P, const HsJob& job
 #endif
     const bool solve = P.solve != 0;  // (kernel parameter: uniform)
     // the solve's inputs go out first, in the same round trip as the partials
-    if (solve) solve_stage(slot, L, tid, NT);
+    // first_in (uniform): an inline-staged scan's first solve takes its inputs from the slot's
+    // host-mapped staging copy, which the host wrote before the launch
+    const IekfSlot* const stage_in = first_in ? reinterpret_cast<const IekfSlot*>(job.host_slot) : nullptr;
+    if (solve) solve_stage(stage_in ? stage_in : slot, L, tid, NT);
+    // an inline-staged scan's first solve: the slot goes through to the device beside the partials' loads
+    if (stage_in) slot_through_t<NT>(stage_in, slot, tid);
     {
         // thread (g, c) sums blocks g, g+G, ... of column c in that order, kRedInFlight
         // loads in flight (G = NT / 32 groups)
@@ -2975,6 +3018,8 @@ __device__ __forceinline__ void hs_scan_tail(const HsParams& P, const HsJob& job
         }
         R.fin[g * kRedCols + c] = acc;
     }
+    // (slot_through's stores drained: the slot words this tail stores below land after them)
+    if (stage_in) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // the block partials' sums and the staged inputs
     const bool wb = solve && job.host_slot != nullptr;  // (uniform) the stopping solve writes the host's slot
     if (tid >= 64) {
@@ -3037,9 +3082,9 @@ __device__ __forceinline__ void hs_scan_tail(const HsParams& P, const HsJob& job
 template <int NT, int NU = kRedUsed, class Col>
 __device__ __forceinline__ void hshare_reduce_solve(const HsParams& P, const HsJob& job, IekfSlot* slot,
                                                     const Col& col, int nblk, unsigned blk, HsReduceLds& R,
-                                                    SolveLds& L, int pk = -1) {
+                                                    SolveLds& L, int pk = -1, bool first_in = false) {
     hs_block_partial<NT, NU>(job, col, blk, R);
-    hs_ticket_tail<NT, NU>(P, job, slot, nblk, blk, R, L, pk);
+    hs_ticket_tail<NT, NU>(P, job, slot, nblk, blk, R, L, pk, first_in);
 }
 
 template <bool FIRST>
@@ -3125,11 +3170,6 @@ __device__ __forceinline__ void replay_wave(const KnnParams& P, const HsJob& job
     }
 }
 
-struct EvalParams {
-    KnnParams k;
-    HsParams h;
-};
-
 #ifdef LIVO_EVAL_PROF  // per-phase block time of k_iekf_eval (tools/eval_prof.py; compiled out of the product)
 // [search][phase]: cycles summed over blocks (thread 0's s_memtime deltas) and block counts
 __device__ unsigned long long g_eval_prof[3][8];  // [no search / rematch / first search][phase]
@@ -3184,8 +3224,36 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
     unsigned bjob, bx;
     // the same block order in every evaluation: the plane caches stay in the L2 that wrote them
     xcd_chunk_block(P.nb, P.xcd_chunk, bjob, bx);
-    const HsJob job = P.jobs[bjob];
+    // The group's jobs ride in the arguments (E.in.n > 0; kernel parameter: uniform) or lie in
+    // the staged table.  bjob is block-uniform, and neither is written while the launch runs:
+    // one uniform-indexed read through the constant address space either way.
+    using CWord = const __attribute__((address_space(4))) unsigned long long;
+    HsJob job;
+    {
+        constexpr int kW = (int)(sizeof(HsJob) / 8);
+        static_assert(sizeof(HsJob) % 8 == 0, "HsJob in 8-B words");
+        CWord* const src = E.in.n > 0 ? (CWord*)&E.in.jobs[bjob] : (CWord*)&P.jobs[bjob];
+        unsigned long long w[kW];
+#pragma unroll
+        for (int k = 0; k < kW; k++) w[k] = src[k];
+        __builtin_memcpy(&job, w, sizeof(HsJob));
+    }
     IekfSlot* slot = job.slot;
+    // The FIRST launch of an inline-staged group: nothing has filled the device slot yet.  Its
+    // blocks take the pose and the control block from the arguments and touch the slot at its
+    // ticket lines only (in their start state: hs_shard_level / hs_scan_tail reset them, the
+    // staging area is allocated zeroed); the scan's first solve reads the slot's host-mapped
+    // staging copy (job.host_slot) and fills the device slot (hs_scan_tail, slot_through_t).
+    const bool first_in = FIRST && E.in.first_in != 0;
+    // The scan's head is addressed in the kernel-argument segment itself (E is the kernels' one
+    // argument, at offset 0): a pointer into the by-value parameter that meets the slot's in a
+    // select would make the compiler keep a private copy of all of E (1.7 KB of scratch).
+    const EvalHead& head = *reinterpret_cast<const EvalHead*>(
+        (const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(EvalParams, in.head) +
+        (first_in ? bjob : 0u) * sizeof(EvalHead));
+    IekfCtrl ctrl_in;
+    if (first_in) ctrl_in = head.ctrl;
+    else ctrl_in = slot->ctrl;
     if (bx > 0 && (int)bx * kEvalBlock >= job.n) return;  // (an empty scan keeps one block: it solves)
     const int i = (int)bx * kEvalBlock + threadIdx.x;
     const bool valid = i < job.n;
@@ -3193,7 +3261,7 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
     // with the slot's control reads: an evaluation without a search runs on them
     HsPointIn pin = !FIRST && valid ? hshare_load(job, i, true) : HsPointIn{};
     bool prefit = false;  // the plane of this evaluation fitted in the search branch
-    if (slot->ctrl.stop) return;  // block-uniform
+    if (ctrl_in.stop) return;  // block-uniform
     const int search = FIRST ? 1 : slot->ctrl.search_en;
     // The first search's records are dead when the scan is sure to search again before
     // anything but this launch reads them: the loop's solve follows
@@ -3207,7 +3275,7 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
     bool dead = false;
 #ifndef LIVO_EVAL_PROF
     if constexpr (kStatic) {
-        const IekfCtrl& c = slot->ctrl;
+        const IekfCtrl& c = ctrl_in;
         dead = P.rec_compact && E.h.solve && !E.h.dbg.normvec && !E.h.dbg.world && !E.h.dbg.sel;
         if constexpr (FIRST)
             dead = dead && c.max_iter >= 2 && c.max_iter + 1 <= LIVO_MAX_EVALS && c.iter_count == -1 &&
@@ -3216,9 +3284,13 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
             dead = dead && P.rec_lazy;
     }
 #endif
-    const PoseRef pose{slot->state.rot, slot->state.pos};
+    // (rot, then pos, in the slot's state and in the head alike: one base pointer)
+    static_assert(offsetof(livo_state, pos) == 9 * sizeof(double) && offsetof(EvalHead, pos) == 9 * sizeof(double) &&
+                      offsetof(IekfSlot, state) == 0 && offsetof(livo_state, rot) == 0, "pose: rot[9], pos[3]");
+    const double* const pose_b = first_in ? head.rot : slot->state.rot;
+    const PoseRef pose{pose_b, pose_b + 9};
 #ifdef LIVO_EVAL_PROF
-    const int tl_e = min(slot->ctrl.n_evals, LIVO_MAX_EVALS - 1);
+    const int tl_e = min(ctrl_in.n_evals, LIVO_MAX_EVALS - 1);
 #endif
     EVAL_MARK(0);
     unsigned n_slots = 0u, n_pts = 0u;  // hash slots and map points this thread's search read
@@ -3422,7 +3494,8 @@ __device__ __forceinline__ void iekf_eval_body(const EvalParams& E, EvalLds<KIND
 #else
     const int pk = -1;
 #endif
-    hshare_reduce_solve<kEvalBlock, kRedUsed + 2>(E.h, job, slot, col, nblk, bx, U.rs.R, U.rs.solve, pk);
+    hshare_reduce_solve<kEvalBlock, kRedUsed + 2>(E.h, job, slot, col, nblk, bx, U.rs.R, U.rs.solve, pk,
+                                                  FIRST && E.in.first_in != 0);
     EVAL_MARK(4);
 #ifdef LIVO_EVAL_PROF
     if (threadIdx.x == 0 && blockIdx.x < (unsigned)kTlBlocks) {
@@ -4212,11 +4285,16 @@ int launch_copy_ranges(const void* src, void* dst, size_t o0, size_t n0, size_t 
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 
-int launch_iekf_eval(const KnnParams& kp, const HsParams& hp, int n_jobs, int64_t max_n, bool first, void* stream) {
+int launch_iekf_eval(const KnnParams& kp, const HsParams& hp, int n_jobs, int64_t max_n, bool first, void* stream,
+                     const EvalInline* inl) {
     if (n_jobs <= 0 || max_n <= 0) return LIVO_OK;
+    if (inl && (inl->n != n_jobs || n_jobs > kInlineJobs || (inl->first_in && !first))) return LIVO_E_INVALID;
+    for (int k = 0; inl && k < n_jobs; k++)
+        if (!inl->jobs[k].host_slot) return LIVO_E_INVALID;
     EvalParams E;
     E.k = kp;
     E.h = hp;
+    E.in = inl ? *inl : EvalInline{};
     E.k.nb = (int32_t)((max_n + kEvalBlock - 1) / kEvalBlock);
     if ((int64_t)E.k.nb * n_jobs >= (1ll << 31)) return LIVO_E_RANGE;
     const dim3 grid((unsigned)(E.k.nb * n_jobs)), block(kEvalBlock);
