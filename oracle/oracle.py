@@ -90,6 +90,7 @@ def lib():
         L.orc_knn.argtypes = [P, P, C.c_int64, C.c_int, P, P, P, C.c_int]
         L.orc_knn_brute.argtypes = [P, C.c_int64, P, C.c_int64, C.c_int, P, P, C.c_int]
         L.orc_esti_plane.argtypes = [P, C.c_float, P]
+        L.orc_esti_plane_trace.argtypes = [P, C.c_float, P, P]
         L.orc_to_world.argtypes = [P, C.c_int64, C.c_int, P, P, P, P, P]
         L.orc_h_share.argtypes = [P, P, C.c_int64, P, P, P, P, C.c_int, C.c_double, P, P, P, P, P, P, P, P,
                                   P, P, C.c_int]
@@ -272,6 +273,30 @@ def esti_plane(pts5x3, threshold=0.1):
     out = np.zeros(4, np.float32)
     ok = lib().orc_esti_plane(_p(p), C.c_float(threshold), _p(out))
     return bool(ok), out
+
+
+PLANE_TRACE_DTYPE = np.dtype([("transp", np.int32, 3), ("nonzero", np.int32), ("tau_zero", np.int32, 3),
+                              ("recomputed", np.int32, (2, 2)), ("back_skipped", np.int32, 3), ("tie", np.int32, 2),
+                              ("big_sq", np.float32, 3), ("rank_thr", np.float32, 3)])
+
+
+def esti_plane_trace(pts5x3, threshold=0.1):
+    """esti_plane and the branches it took: (ok, pabcd, trace).  trace: transp (the column swapped into
+    place k at step k), perm (the column of A in place i), nonzero, tau_zero[k], recomputed[k][j - 1] (the
+    column in place j recomputed its norm at step k; k = 0, 1), back_skipped[i], tie[k] (another column's
+    norm equalled the pivot's at step k), and big_sq[k] /
+    rank_thr[k], the two sides of the rank test at step k."""
+    p = np.ascontiguousarray(pts5x3, np.float32).reshape(15)
+    out = np.zeros(4, np.float32)
+    tr = np.zeros(1, PLANE_TRACE_DTYPE)
+    ok = lib().orc_esti_plane_trace(_p(p), C.c_float(threshold), _p(out), _p(tr))
+    t = {k: tr[k][0].copy() if tr[k][0].ndim else int(tr[k][0]) for k in PLANE_TRACE_DTYPE.names}
+    perm = [0, 1, 2]
+    for k in range(3):
+        j = int(t["transp"][k])
+        perm[k], perm[j] = perm[j], perm[k]
+    t["perm"] = tuple(perm)
+    return bool(ok), out, t
 
 
 def new_cache(n: int) -> dict:

@@ -7,6 +7,9 @@ the restatement is pinned against independent implementations instead:
   * LAPACK xGELSY (column-pivoting QR least squares) for esti_plane;
   * numpy float64 for the Jacobian / normal equations and the IEKF algebra;
 and against its own committed golden fixtures (tests/golden/) for regressions.
+The plane fit off its well-conditioned path (rank loss, pivot ties, tau = 0, fits
+far from and through the origin) and the gates at their thresholds are held to a
+60-digit reference in tests/test_plane_reference.py.
 """
 import math
 import os
