@@ -323,7 +323,9 @@ constexpr int rec_flag(uint32_t cf) { return (int)(cf & kRecFlagMask); }
 // neighbour k (the hot half alone), the pads where k >= count.
 // (count -1: a record of a 0xFF-filled buffer that no search wrote, livo_ivox_knn)
 inline int rec_host_cnt(const NNRec& r) { return r.cf == 0xFFFFFFFFu ? -1 : rec_cnt(r.cf); }
-inline int32_t rec_host_idx(const NNRec& r, int k) { return r.idx[k]; }
+// (a record no search has written yet is all zeros, count 0: an empty Nearest_Points entry, which
+// an iVox search with no candidate leaves as it is; its indices read as the -1 pad, not as map point 0)
+inline int32_t rec_host_idx(const NNRec& r, int k) { return rec_cnt(r.cf) == 0 ? -1 : r.idx[k]; }
 inline float rec_host_sqdist(const NNRec& r, int k) { return r.sqdist[k]; }
 
 // One scan of a batched launch.

@@ -141,14 +141,20 @@ def test_h_share_parity(ctx100k, tree100k):
         ctx100k.scan_release(sid)
 
 
-def _iekf_compare(gpu_ctx, tree, body, st0, max_iter, t_LI):
+def _iekf_compare(gpu_ctx, tree, body, st0, max_iter, t_LI, R_LI=None):
     gpu_ctx.set_params(max_iterations=max_iter)
     sid = gpu_ctx.scan_upload(body)
     try:
         sg, stg = gpu_ctx.iekf_update(sid, st0)
     finally:
         gpu_ctx.scan_release(sid)
-    sr, str_ = tree.iekf_update(body, st0, R_LI=np.eye(3), t_LI=t_LI, max_iter=max_iter)
+    sr, str_ = tree.iekf_update(body, st0, R_LI=np.eye(3) if R_LI is None else R_LI, t_LI=t_LI, max_iter=max_iter)
+    _iekf_bars(sg, stg, sr, str_, st0)
+    return stg
+
+
+def _iekf_bars(sg, stg, sr, str_, st0):
+    """One update (state, stats) of the device against the oracle's."""
     assert stg["iterations"] == str_["iterations"]
     assert stg["knn_passes"] == str_["knn_passes"]
     assert stg["converged"] == str_["converged"]

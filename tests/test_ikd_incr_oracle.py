@@ -184,3 +184,27 @@ def test_map_incremental_is_world_transform_then_add(built):
     for x, y in zip(a.dump(), b.dump()):
         assert np.array_equal(x, y)
     del rng
+
+
+@pytest.mark.parametrize("ext", ["tilt", "flip"])
+def test_map_incremental_under_extrinsic_is_to_world_then_add(built, ext):
+    """The same under a tilted and an upside-down LiDAR-IMU extrinsic (tests/extrinsic_cases.py): the
+    points map_incremental adds are oracle.to_world's (held to the 60-digit front-end reference under
+    tilt), so its counts and map equal Add_Points of them on a twin map."""
+    import extrinsic_cases as xc
+    import oracle
+    from livo_amd import synth
+    R_LI, t_LI = xc.ext(ext)
+    m = synth.make_map(20_000)
+    body, st = xc.scan(3_000, 1, ext)
+    a, b = oracle.DynMap(m), oracle.DynMap(m)
+    sa = a.map_incremental(body, st, R_LI=R_LI, t_LI=t_LI, filter_size_map=0.3)
+    W = oracle.to_world(body, st, R_LI, t_LI)[:, :3]
+    assert np.abs(W - xc.world_of(body, st, R_LI, t_LI)).max() < 4e-6  # (metres in float32: the same points)
+    sb = b.add_points(W, 0.3)
+    assert sa == sb and sa["events"] > 0 and sa["added"] > 0
+    for x, y in zip(a.dump(), b.dump()):
+        assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
+    # the scan lands on the room: without R_LI it would not, and the add would differ
+    c = oracle.DynMap(m)
+    assert c.map_incremental(body, st, R_LI=np.eye(3), t_LI=t_LI, filter_size_map=0.3) != sa

@@ -128,22 +128,34 @@ def test_ivox_lru_and_eviction_match_ordereddict(built):
         assert iv.info()["num_grids"] == len(od)
 
 
-def test_map_incremental_matches_numpy(built):
+@pytest.mark.parametrize("ext", ["ident", "tilt", "flip"])
+def test_map_incremental_matches_numpy(built, ext):
+    """ext: the LiDAR-IMU extrinsic (tests/extrinsic_cases.py).  Under tilt and flip the world points are
+    oracle.to_world's (held to the 60-digit front-end reference under tilt), so every point the map
+    takes is bitwise one of them."""
+    import extrinsic_cases as xc
     import oracle
     from livo_amd import synth
+    R_LI, t_LI = xc.ext(ext)
     m = synth.make_map(100_000)
     iv = oracle.Ivox()
     iv.add_points(m)
-    body, _, _ = synth.make_scan(4_000, 1)
-    st = synth.make_state(1)
+    body, st = xc.scan(4_000, 1, ext)
     cache = oracle.new_cache(body.shape[0])
-    st1, _ = iv.iekf_update(body, st, cache, t_LI=synth.T_LI)
+    st1, stats = iv.iekf_update(body, st, cache, R_LI=R_LI, t_LI=t_LI)
+    assert stats["effct_feat_num"][0] >= 0.5 * len(body) and stats["iterations"] >= 2
     n0 = iv.info()["num_points"]
     fs = 0.5
-    cat, counts = iv.map_incremental(body, st1, cache, t_LI=synth.T_LI, filter_size_map=fs)
+    cat, counts = iv.map_incremental(body, st1, cache, R_LI=R_LI, t_LI=t_LI, filter_size_map=fs)
     # numpy restatement of laser_mapping.cpp:343-380
-    pI = body.astype(np.float64) + synth.T_LI
-    pw = ((st1["rot"] @ pI.T).T + st1["pos"]).astype(np.float32)
+    pw = oracle.to_world(body, st1, R_LI, t_LI)[:, :3]
+    if ext == "ident":
+        pI = body.astype(np.float64) + synth.T_LI
+        assert np.array_equal(pw, ((st1["rot"] @ pI.T).T + st1["pos"]).astype(np.float32))
+    else:
+        assert np.abs(pw - xc.world_of(body, st1, R_LI, t_LI)).max() < 4e-6  # (float32 of metres: the same points)
+        if ext == "tilt":  # (not symmetric: the transposed matrix puts them metres away)
+            assert np.abs(pw - xc.world_of(body, st1, R_LI.T, t_LI)).max() > 0.5
     f = np.float32(fs)
     c = (np.floor(pw / f) + np.float32(0.5)) * f
     near = cache["xyz"].reshape(-1, 5, 3)
@@ -166,7 +178,39 @@ def test_map_incremental_matches_numpy(built):
     new = ids >= n0
     order = np.argsort(ids[new])
     exp_pts = np.concatenate([pw[exp == 1], pw[exp == 2]])
-    assert np.array_equal(xyz[new][order], exp_pts)
+    assert np.array_equal(xyz[new][order].view(np.uint32), exp_pts.view(np.uint32))
+    assert counts["added"] > 0 and counts["no_downsample"] + int(np.sum(exp == 0)) > 0
+
+
+def test_map_incremental_flip_equals_pretransformed_identity(built):
+    """The upside-down mounting against a second Ivox driven with R_LI = I on the cloud R_LI p_b:
+    diag(1, -1, -1) p_b is exact in float32 and R_LI p_b + t_LI takes the same double operations
+    either way (the products by 0 add +-0), so the update, the categories, the counts and the whole map
+    are equal bit for bit over two scans.  A dropped or half-applied R_LI in the oracle's iVox loop or
+    in its map_incremental breaks it."""
+    import extrinsic_cases as xc
+    import oracle
+    from livo_amd import synth
+    R_LI, t_LI = xc.EXT["flip"]
+    m = synth.make_map(100_000)
+    a, b = oracle.Ivox(), oracle.Ivox()
+    a.add_points(m)
+    b.add_points(m)
+    for sid in (1, 2):
+        body, st = xc.scan(4_000, sid, "flip")
+        pre = np.ascontiguousarray(body * np.array([1.0, -1.0, -1.0], np.float32))
+        assert np.array_equal(pre.astype(np.float64), body.astype(np.float64) @ R_LI.T)
+        ca, cb = oracle.new_cache(len(body)), oracle.new_cache(len(body))
+        sa, ta = a.iekf_update(body, st, ca, R_LI=R_LI, t_LI=t_LI)
+        sb, tb = b.iekf_update(pre, st, cb, R_LI=np.eye(3), t_LI=t_LI)
+        assert ta["effct_feat_num"] == tb["effct_feat_num"] and ta["effct_feat_num"][0] >= 0.5 * len(body)
+        assert np.array_equal(ta["solution"], tb["solution"]) and np.array_equal(sa["cov"], sb["cov"])
+        assert all(np.array_equal(ca[k], cb[k]) for k in ca)
+        cat_a, cnt_a = a.map_incremental(body, sa, ca, R_LI=R_LI, t_LI=t_LI, filter_size_map=0.5)
+        cat_b, cnt_b = b.map_incremental(pre, sb, cb, R_LI=np.eye(3), t_LI=t_LI, filter_size_map=0.5)
+        assert np.array_equal(cat_a, cat_b) and cnt_a == cnt_b and cnt_a["added"] > 0
+        for x, y in zip(a.dump(), b.dump()):
+            assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
 
 
 def test_ivox_iekf_converges(built):

@@ -117,12 +117,14 @@ def test_esti_plane_degenerate(built):
     assert abs(pabcd[2] + 1.0) < 1e-6 and abs(pabcd[3] - 2.0) < 1e-5  # x = (0, 0, -0.5)
 
 
-def _numpy_hshare(body, rot, pos, t_LI, nv, sel, lpc=0.001):
+def _numpy_hshare(body, rot, pos, R_LI, t_LI, nv, sel, lpc=0.001, drop_R_LI=False):
+    """H^T H and H^T L of laser_mapping.cpp:565-590 in numpy float64: p_I = R_LI p_b + t_LI,
+    A = [p_I]x (R^T n).  drop_R_LI: the wrong Jacobian that leaves R_LI out of p_I."""
     keep = sel.astype(bool)
     pb = body[keep].astype(np.float64)
     n = nv[keep, :3].astype(np.float64)
     pd2 = nv[keep, 3].astype(np.float64)
-    pI = pb + t_LI
+    pI = (pb if drop_R_LI else pb @ np.asarray(R_LI, np.float64).T) + t_LI
     A = np.cross(pI, n @ rot)  # [p_I]x (R^T n)
     H = np.c_[A, n]
     HTH = H.T @ H / lpc
@@ -130,12 +132,19 @@ def _numpy_hshare(body, rot, pos, t_LI, nv, sel, lpc=0.001):
     return HTH, HTL
 
 
-def test_h_share_normal_equations_vs_numpy(tree100k):
+EXT_NAMES = ["ident", "tilt", "flip"]
+
+
+@pytest.mark.parametrize("ext", EXT_NAMES)
+def test_h_share_normal_equations_vs_numpy(tree100k, ext):
+    import extrinsic_cases as xc
     synth = _synth()
-    body, _, _ = synth.make_scan(8_000, 4)
-    st = synth.make_state(4)
-    r = tree100k.h_share(body, st["rot"], st["pos"], np.eye(3), synth.T_LI, True)
-    HTH, HTL = _numpy_hshare(body, st["rot"], st["pos"], synth.T_LI, r["normvec"], r["sel"])
+    R_LI, t_LI = xc.ext(ext)
+    body, st = xc.scan(8_000, 4, ext)
+    if ext == "ident":
+        assert np.array_equal(body, synth.make_scan(8_000, 4)[0])  # (the scan of the test before the extrinsics)
+    r = tree100k.h_share(body, st["rot"], st["pos"], R_LI, t_LI, True)
+    HTH, HTL = _numpy_hshare(body, st["rot"], st["pos"], R_LI, t_LI, r["normvec"], r["sel"])
     assert r["effct"] == int(r["sel"].sum()) > 7_000
     assert np.allclose(r["HTH"][:6, :6], HTH, rtol=1e-10, atol=1e-6)
     assert np.allclose(r["HTL"][:6], HTL, rtol=1e-10, atol=1e-8)
@@ -145,6 +154,33 @@ def test_h_share_normal_equations_vs_numpy(tree100k):
     assert np.all(np.abs(pd2) <= 2.0)
     # neighbours of accepted points pass the sqdis[4] <= 5 gate
     assert np.all(r["cache"]["d"][r["sel"].astype(bool), 4] <= 5.0)
+    if ext != "ident":
+        # the input tells a Jacobian without R_LI apart: far outside any bar
+        bad, _ = _numpy_hshare(body, st["rot"], st["pos"], R_LI, t_LI, r["normvec"], r["sel"], drop_R_LI=True)
+        rel = np.linalg.norm(bad - r["HTH"][:6, :6]) / np.linalg.norm(r["HTH"][:6, :6])
+        good = np.linalg.norm(HTH - r["HTH"][:6, :6]) / np.linalg.norm(r["HTH"][:6, :6])
+        print(f"HTH vs numpy {ext}: {good:.2e}; with R_LI dropped from p_I: {rel:.3f}")
+        assert rel > 0.1, rel
+
+
+@pytest.mark.parametrize("ext", ["tilt", "flip"])
+def test_h_share_cache_is_knn_of_to_world(tree100k, ext):
+    """The neighbours h_share caches are those of the world points of oracle.to_world (held to the
+    60-digit front-end restatement under tilt in tests/test_frontend_reference.py), bit for bit:
+    the k-NN query reads the same R_LI as the front-end."""
+    import extrinsic_cases as xc
+    import oracle
+    R_LI, t_LI = xc.ext(ext)
+    body, st = xc.scan(3_000, 2, ext)
+    r = tree100k.h_share(body, st["rot"], st["pos"], R_LI, t_LI, True)
+    idx, d, _ = tree100k.knn(oracle.to_world(body, st, R_LI, t_LI)[:, :3])
+    assert np.array_equal(r["cache"]["idx"], idx)
+    assert np.array_equal(r["cache"]["d"].view(np.uint32), d.view(np.uint32))
+    assert r["effct"] >= 0.9 * len(body)
+    # and the transposed matrix gives other queries (tilt is not symmetric; flip is, and is its own transpose)
+    if ext == "tilt":
+        idx_t, _, _ = tree100k.knn(oracle.to_world(body, st, R_LI.T, t_LI)[:, :3])
+        assert (idx_t[:, 0] != idx[:, 0]).mean() > 0.5
 
 
 def _boxplus(st, d):
@@ -155,19 +191,50 @@ def _boxplus(st, d):
     return out
 
 
-def test_iekf_first_step_vs_numpy(tree100k):
+@pytest.mark.parametrize("ext", EXT_NAMES)
+def test_iekf_first_step_vs_numpy(tree100k, ext):
     """One IEKF evaluation (laser_mapping.cpp:187-193) against numpy float64."""
-    synth = _synth()
-    body, _, _ = synth.make_scan(6_000, 5)
-    st = synth.make_state(5)
-    r = tree100k.h_share(body, st["rot"], st["pos"], np.eye(3), synth.T_LI, True)
+    import extrinsic_cases as xc
+    R_LI, t_LI = xc.ext(ext)
+    body, st = xc.scan(6_000, 5, ext)
+    r = tree100k.h_share(body, st["rot"], st["pos"], R_LI, t_LI, True)
+    HTH, HTL = _numpy_hshare(body, st["rot"], st["pos"], R_LI, t_LI, r["normvec"], r["sel"])
     H18 = np.zeros((18, 18))
+    H18[:6, :6] = HTH
+    K1 = np.linalg.inv(H18 + np.linalg.inv(st["cov"]))
+    sol = K1[:, :6] @ HTL  # vec = prior - state = 0 on the first evaluation
+    _, stats = tree100k.iekf_update(body, st, R_LI=R_LI, t_LI=t_LI, max_iter=0)
+    assert stats["iterations"] == 1
+    assert stats["effct_feat_num"][0] == r["effct"] >= 0.9 * len(body)
+    assert np.allclose(stats["solution"][0], sol, rtol=1e-9, atol=1e-14)
+    # and from the oracle's own sums, as before the extrinsics
     H18[:9, :9] = r["HTH"]
     K1 = np.linalg.inv(H18 + np.linalg.inv(st["cov"]))
-    sol = K1[:, :9] @ r["HTL"]  # vec = prior - state = 0 on the first evaluation
-    _, stats = tree100k.iekf_update(body, st, R_LI=np.eye(3), t_LI=synth.T_LI, max_iter=0)
-    assert stats["iterations"] == 1
-    assert np.allclose(stats["solution"][0], sol, rtol=1e-9, atol=1e-14)
+    assert np.allclose(stats["solution"][0], K1[:, :9] @ r["HTL"], rtol=1e-9, atol=1e-14)
+
+
+@pytest.mark.parametrize("n,sid", [(10_000, 0), (1_000, 3)])
+def test_iekf_tilt_lands_where_identity_does(tree100k, n, sid):
+    """The scans of tests/test_gpu_extrinsic.py: under the tilt extrinsic the oracle finds nearly every
+    point a plane, runs evaluations with and without a search, and ends where the identity-extrinsic
+    update of the same scan ends.  The two scans are the same double points rounded to float32 in two
+    frames: each coordinate (below 32 m) moves by at most half an ulp, 2^-20 m, a point by sqrt(3) 2^-20
+    on either side, and a pose fitted to points displaced by at most d moves by about d at the
+    most (d / sqrt(n) when the roundings are independent): the bar is 2 sqrt(3) 2^-20 = 3.3e-6 m, against
+    the 0.1 m of the initial error.  Measured: 7.4e-8 m (10,000 points, 9,967 effective) and 1.0e-7 m (1,000 points, 994 effective), five
+    evaluations each."""
+    import extrinsic_cases as xc
+    out = {}
+    for ext in ("ident", "tilt"):
+        R_LI, t_LI = xc.ext(ext)
+        body, st = xc.scan(n, sid, ext)
+        out[ext] = tree100k.iekf_update(body, st, R_LI=R_LI, t_LI=t_LI, max_iter=4)
+        xc.oracle_floors(out[ext][1], n)
+    print(f"n={n}: effct {out['tilt'][1]['effct_feat_num']} evaluations {out['tilt'][1]['iterations']}")
+    assert out["tilt"][1]["iterations"] == out["ident"][1]["iterations"]
+    moved = np.linalg.norm(out["tilt"][0]["pos"] - out["ident"][0]["pos"])
+    print(f"n={n}: final position {moved:.2e} m from the identity run's")
+    assert moved < 2 * np.sqrt(3.0) * 2.0 ** -20
 
 
 def test_iekf_control_flow(tree100k):

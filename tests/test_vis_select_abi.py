@@ -243,10 +243,11 @@ def frame_image(name):
     return img, cam, synth.R_CI, synth.P_CI
 
 
-def frame_case(name, n):
+def frame_case(name, n, R_LI=None, t_LI=None):
     """(state, body points (n, 3) float32) of the frame: ceil(n / 2) unique points, the rest copies of them at
     other cloud indices; the unique points are back-projected from pixels spread over the frame and a margin
-    around it, a sixth of them mirrored through the camera centre (behind it, on the same ray)."""
+    around it, a sixth of them mirrored through the camera centre (behind it, on the same ray).  R_LI, t_LI:
+    the LiDAR-IMU extrinsic the body points are expressed under (default: synth's, R_LI = I)."""
     from livo_amd import synth
     img, cam, Rci, Pci = frame_image(name)
     seed = CASE_SEED[name]
@@ -260,7 +261,9 @@ def frame_case(name, n):
     pf = np.stack([(u - cam["cx"]) / cam["fx"] * z, (v - cam["cy"]) / cam["fy"] * z, z], axis=1)
     Rcw, Pcw = restate_pose(Rci, Pci, st["rot"], st["pos"])
     world = (pf - Pcw) @ Rcw                                  # p_w = Rcw^T (pf - Pcw)
-    body = (world - st["pos"]) @ st["rot"] - synth.T_LI       # R_LI = I
+    body = (world - st["pos"]) @ st["rot"] - (synth.T_LI if t_LI is None else np.asarray(t_LI, F64))
+    if R_LI is not None:
+        body = body @ np.asarray(R_LI, F64)                   # p_b = R_LI^T (p_I - t_LI)
     src = np.concatenate([np.arange(m), rng.permutation(m)[:n - m]])
     return st, np.ascontiguousarray(body[src][rng.permutation(n)], F32)
 

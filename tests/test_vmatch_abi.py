@@ -386,16 +386,21 @@ class Scene:
             out = np.where(which == (k if len(self.planes) == 2 else 1 - k), val, out)
         return np.clip(np.rint(out), 0, 255).astype(np.uint8).reshape(h, w)
 
-    def cloud(self, state, n, seed, margin=0.1):
+    def cloud(self, state, n, seed, margin=0.1, R_LI=None, t_LI=None):
         """n body-frame points (float32) of `state` on the surfaces seen through random pixels of its image."""
         rng = np.random.default_rng(seed)
         w, h = self.cam["width"], self.cam["height"]
         hit, _ = self._pixels(state, rng.uniform(-margin * w, (1 + margin) * w, n),
                               rng.uniform(-margin * h, (1 + margin) * h, n))
-        return self.body(state, hit)
+        return self.body(state, hit, R_LI, t_LI)
 
-    def body(self, state, world):
-        return np.ascontiguousarray((np.asarray(world) - state["pos"]) @ state["rot"] - self.synth.T_LI, F32)
+    def body(self, state, world, R_LI=None, t_LI=None):
+        """World points in the LiDAR frame of `state`: R_LI^T (R^T (p_w - p) - t_LI); by default synth's
+        extrinsic (R_LI = I, t_LI = synth.T_LI)."""
+        imu = (np.asarray(world) - state["pos"]) @ state["rot"] - (self.synth.T_LI if t_LI is None else np.asarray(t_LI))
+        if R_LI is not None:
+            imu = imu @ np.asarray(R_LI, F64)
+        return np.ascontiguousarray(imu, F32)
 
 
 def moved(state, dpos, drot_deg=(0.0, 0.0, 0.0)):
