@@ -1,7 +1,13 @@
 // GPU unit check (tests/test_gpu_ivox.py): wave_nth (fast-livo-noted_amd/csrc/
 // wave_select.h), the wave-parallel std::nth_element of the iVox search,
 // against libstdc++'s std::nth_element on the host, element for element.
-// One wave per case; cases of 1..kWRaw elements with many ties.
+// One wave per case; cases of 1..kWRaw elements with many ties, and McIlroy
+// adversaries (nth_adversary.h) that run each kernel into introselect's depth
+// limit.  wave_nth / wave_nth_big return false there (their callers hand the
+// query on): the returned status of every case must equal the host predicate
+// that replays introselect's rounds, and only a case the predicate says reaches
+// the limit is left unchecked element for element.  team_nth heap-selects on
+// its lane 0: every case is compared element for element.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +15,7 @@
 #include <random>
 #include <vector>
 
+#include "nth_adversary.h"
 #include "wave_select.h"
 
 using namespace livo;
@@ -82,12 +89,68 @@ struct DP {
     bool operator<(const DP& o) const { return d < o.d; }
 };
 
+// Adversarial cases appended to a set: ranges of `len` elements after `first` others, the 5 smallest
+// (nth = first + 4, the selection the iVox search runs: pivot driven to the top) and nth = n - 5
+// (pivot driven to the bottom); keys are the adversary's ranks.
+static void add_adversaries(std::vector<Case>& cases, std::vector<float>& in, int cap, std::initializer_list<int> lens) {
+    for (int len : lens)
+        for (int first : {0, 5})
+            for (int form = 0; form < 2; form++) {
+                const int n = first + len;
+                if (n > cap) continue;
+                const int nth = form == 0 ? first + 4 : n - 5;
+                const std::vector<int> v = nth_adversary::sequence(n, first, nth, form == 0);
+                const size_t c = cases.size();
+                cases.push_back(Case{n, first, nth});
+                in.resize((c + 1) * (size_t)cap, 0.f);
+                for (int p = 0; p < n; p++) in[c * (size_t)cap + p] = (float)v[(size_t)p];
+            }
+}
+
+// One set's results against libstdc++: ids element for element, and (status != nullptr) the returned
+// status against the host predicate.  Returns the mismatches; `limit` counts the cases the predicate
+// says reach the depth limit.
+static long compare(const char* name, const std::vector<Case>& cases, const std::vector<float>& in,
+                    const std::vector<uint32_t>& ids, const int* status, int cap, long& limit) {
+    long bad = 0;
+    limit = 0;
+    for (size_t c = 0; c < cases.size(); c++) {
+        const Case k = cases[c];
+        std::vector<DP> ref(k.n);
+        std::vector<SelElem> keys(k.n);
+        for (int p = 0; p < k.n; p++) {
+            ref[p] = DP{in[c * (size_t)cap + p], (uint32_t)p};
+            keys[p] = SelElem{ref[p].d, (uint32_t)p};
+        }
+        const bool lim = nth_adversary::depth_limit_reached(keys, k.first, k.nth, k.n);
+        limit += lim;
+        if (status) {
+            if ((status[c] != 0) == lim) {  // true where the limit ran out, or false where it did not
+                if (bad < 3) std::printf("%s case %zu n %d first %d nth %d: status %d, depth limit %s\n", name, c, k.n,
+                                         k.first, k.nth, status[c], lim ? "reached" : "not reached");
+                bad++;
+                continue;
+            }
+            if (lim) continue;  // the caller's fallback finishes it: nothing to compare here
+        }
+        std::nth_element(ref.begin() + k.first, ref.begin() + k.nth, ref.begin() + k.n);
+        for (int p = 0; p < k.n; p++)
+            if (ids[c * (size_t)cap + p] != ref[p].id) {
+                if (bad < 3) std::printf("%s case %zu n %d first %d nth %d: pos %d got %u want %u\n", name, c, k.n,
+                                         k.first, k.nth, p, ids[c * (size_t)cap + p], ref[p].id);
+                bad++;
+                break;
+            }
+    }
+    return bad;
+}
+
 int main(int argc, char** argv) {
-    const int ncase = argc > 1 ? std::atoi(argv[1]) : 20000;
+    const int nrand = argc > 1 ? std::atoi(argv[1]) : 20000;
     std::mt19937 rng(99);
-    std::vector<Case> cases(ncase);
-    std::vector<float> din((size_t)ncase * kWRaw, 0.f);
-    for (int c = 0; c < ncase; c++) {
+    std::vector<Case> cases(nrand);
+    std::vector<float> din((size_t)nrand * kWRaw, 0.f);
+    for (int c = 0; c < nrand; c++) {
         const int n = 1 + (int)(rng() % (c % 5 == 0 ? (unsigned)kWRaw : 140u));
         const int levels = 1 + (int)(rng() % 30u);
         for (int p = 0; p < n; p++)
@@ -97,6 +160,8 @@ int main(int argc, char** argv) {
         const int nth = first + (int)(rng() % (unsigned)(n - first));
         cases[c] = Case{n, first, nth};
     }
+    add_adversaries(cases, din, kWRaw, {24, 38, 64, 100, 128, 129, 200, 300, 400, 500, 507, 512});
+    const int ncase = (int)cases.size();
     Case* dc;
     float *di, *dd;
     uint32_t* dids;
@@ -113,35 +178,19 @@ int main(int argc, char** argv) {
         std::printf("kernel failed\n");
         return 2;
     }
-    std::vector<float> dout(din.size());
     std::vector<uint32_t> idout(din.size());
     std::vector<int> st(ncase);
-    hipMemcpy(dout.data(), dd, din.size() * 4, hipMemcpyDeviceToHost);
     hipMemcpy(idout.data(), dids, din.size() * 4, hipMemcpyDeviceToHost);
     hipMemcpy(st.data(), dst, 4 * ncase, hipMemcpyDeviceToHost);
-    long bad = 0, fallback = 0;
-    for (int c = 0; c < ncase; c++) {
-        const Case k = cases[c];
-        std::vector<DP> ref(k.n);
-        for (int p = 0; p < k.n; p++) ref[p] = DP{din[(size_t)c * kWRaw + p], (uint32_t)p};
-        std::nth_element(ref.begin() + k.first, ref.begin() + k.nth, ref.begin() + k.n);
-        if (!st[c]) {
-            fallback++;
-            continue;
-        }
-        for (int p = 0; p < k.n; p++)
-            if (idout[(size_t)c * kWRaw + p] != ref[p].id) {
-                if (bad < 3) std::printf("case %d n %d first %d nth %d: pos %d got %u want %u\n", c, k.n, k.first,
-                                         k.nth, p, idout[(size_t)c * kWRaw + p], ref[p].id);
-                bad++;
-                break;
-            }
-    }
+    long wlimit = 0;
+    const long bad = compare("wave", cases, din, idout, st.data(), kWRaw, wlimit);
+    std::printf("wave_nth: %d cases of up to %d, %ld mismatched, %ld reached the depth limit\n", ncase, kWRaw, bad,
+                wlimit);
     // wave_nth_big: cases of 1..kBigCap elements (ties, narrow and wide value ranges)
-    const int nbig = std::max(200, ncase / 10);
-    std::vector<Case> bcases(nbig);
-    std::vector<float> bin((size_t)nbig * kBigCap, 0.f);
-    for (int c = 0; c < nbig; c++) {
+    const int nbrand = std::max(200, nrand / 10);
+    std::vector<Case> bcases(nbrand);
+    std::vector<float> bin((size_t)nbrand * kBigCap, 0.f);
+    for (int c = 0; c < nbrand; c++) {
         const int n = 1 + (int)(rng() % (c % 3 == 0 ? (unsigned)kBigCap : 2000u));
         const int levels = 1 + (int)(rng() % 200u);
         for (int p = 0; p < n; p++)
@@ -151,6 +200,8 @@ int main(int argc, char** argv) {
         const int nth = first + (int)(rng() % (unsigned)(n - first));
         bcases[c] = Case{n, first, nth};
     }
+    add_adversaries(bcases, bin, kBigCap, {24, 128, 513, 600, 1000, 2048, 3000, 4091, 4096});
+    const int nbig = (int)bcases.size();
     Case* bc;
     float *bi, *bd;
     uint32_t* bids;
@@ -171,32 +222,17 @@ int main(int argc, char** argv) {
     std::vector<int> bs(nbig);
     hipMemcpy(bout.data(), bids, bin.size() * 4, hipMemcpyDeviceToHost);
     hipMemcpy(bs.data(), bst, 4 * nbig, hipMemcpyDeviceToHost);
-    long bbad = 0, bfall = 0;
-    for (int c = 0; c < nbig; c++) {
-        const Case k = bcases[c];
-        std::vector<DP> ref(k.n);
-        for (int p = 0; p < k.n; p++) ref[p] = DP{bin[(size_t)c * kBigCap + p], (uint32_t)p};
-        std::nth_element(ref.begin() + k.first, ref.begin() + k.nth, ref.begin() + k.n);
-        if (!bs[c]) {
-            bfall++;
-            continue;
-        }
-        for (int p = 0; p < k.n; p++)
-            if (bout[(size_t)c * kBigCap + p] != ref[p].id) {
-                if (bbad < 3) std::printf("big case %d n %d first %d nth %d: pos %d got %u want %u\n", c, k.n,
-                                          k.first, k.nth, p, bout[(size_t)c * kBigCap + p], ref[p].id);
-                bbad++;
-                break;
-            }
-    }
-    std::printf("wave_nth_big: %d cases of up to %d, %ld mismatched, %ld depth-limit fallbacks\n", nbig, kBigCap,
-                bbad, bfall);
+    long blimit = 0;
+    const long bbad = compare("big", bcases, bin, bout, bs.data(), kBigCap, blimit);
+    std::printf("wave_nth_big: %d cases of up to %d, %ld mismatched, %ld reached the depth limit\n", nbig, kBigCap,
+                bbad, blimit);
     // team_nth: 1..128 elements, mostly the 6..40 of an iVox grid's segment; ties
-    // (few levels, incl. all equal: the heap-select path) and wide ranges
-    const int nteam = std::max(4000, ncase);
-    std::vector<Case> tcases(nteam);
-    std::vector<float> tin((size_t)nteam * kTeamCap, 0.f);
-    for (int c = 0; c < nteam; c++) {
+    // (few levels, incl. all equal) and wide ranges; the adversaries reach the
+    // heap select on lane 0, on the range as the rounds before it narrowed it
+    const int ntrand = std::max(4000, nrand);
+    std::vector<Case> tcases(ntrand);
+    std::vector<float> tin((size_t)ntrand * kTeamCap, 0.f);
+    for (int c = 0; c < ntrand; c++) {
         const int n = 1 + (int)(rng() % (c % 3 == 0 ? (unsigned)kTeamCap : 40u));
         const int levels = 1 + (int)(rng() % (c % 7 == 0 ? 2u : 30u));
         for (int p = 0; p < n; p++)
@@ -207,6 +243,8 @@ int main(int argc, char** argv) {
                                      : first + (int)(rng() % (unsigned)(n - first));
         tcases[c] = Case{n, first, nth};
     }
+    add_adversaries(tcases, tin, kTeamCap, {24, 25, 31, 32, 33, 38, 48, 64, 90, 100, 119, 123, 127, 128});
+    const int nteam = (int)tcases.size();
     Case* tc;
     float* ti;
     uint32_t* tids;
@@ -222,23 +260,15 @@ int main(int argc, char** argv) {
     }
     std::vector<uint32_t> tout(tin.size());
     hipMemcpy(tout.data(), tids, tin.size() * 4, hipMemcpyDeviceToHost);
-    long tbad = 0;
-    for (int c = 0; c < nteam; c++) {
-        const Case k = tcases[c];
-        std::vector<DP> ref(k.n);
-        for (int p = 0; p < k.n; p++) ref[p] = DP{tin[(size_t)c * kTeamCap + p], (uint32_t)p};
-        std::nth_element(ref.begin() + k.first, ref.begin() + k.nth, ref.begin() + k.n);
-        for (int p = 0; p < k.n; p++)
-            if (tout[(size_t)c * kTeamCap + p] != ref[p].id) {
-                if (tbad < 3) std::printf("team case %d n %d first %d nth %d: pos %d got %u want %u\n", c, k.n,
-                                          k.first, k.nth, p, tout[(size_t)c * kTeamCap + p], ref[p].id);
-                tbad++;
-                break;
-            }
+    long tlimit = 0;
+    const long tbad = compare("team", tcases, tin, tout, nullptr, kTeamCap, tlimit);
+    std::printf("team_nth: %d cases of up to %d, %ld mismatched, %ld reached the depth limit\n", nteam, kTeamCap, tbad,
+                tlimit);
+    std::printf("%d cases, %ld mismatches\n", ncase + nbig + nteam, bad + bbad + tbad);
+    std::printf("depth limit reached: wave_nth %ld wave_nth_big %ld team_nth %ld\n", wlimit, blimit, tlimit);
+    if (wlimit == 0 || blimit == 0 || tlimit == 0) {
+        std::printf("a kernel never reached the depth limit\n");
+        return 1;
     }
-    std::printf("team_nth: %d cases of up to %d, %ld mismatched\n", nteam, kTeamCap, tbad);
-    bad += tbad;
-    std::printf("%d cases, %ld mismatches, %ld depth-limit fallbacks\n", ncase + nbig + nteam, bad + bbad,
-                fallback + bfall);
-    return (bad + bbad) == 0 ? 0 : 1;
+    return (bad + bbad + tbad) == 0 ? 0 : 1;
 }

@@ -392,14 +392,21 @@ def test_ivox_batch_overflow_groups(ivctx):
 def test_wave_nth_matches_libstdcxx(built):
     """The wave-parallel std::nth_element of the wave-cooperative iVox search
     (csrc/wave_select.h) against libstdc++ on the host, element for element:
-    20000 cases of 1..256 elements, many ties, nonzero first."""
+    20000 cases of 1..256 elements, many ties, nonzero first, and adversarial
+    sequences (tests/native/nth_adversary.h) that run wave_nth, wave_nth_big and
+    team_nth into introselect's depth limit: the returned status of every case
+    equals the host predicate, and team_nth's heap select is compared too."""
     import os
+    import re
     import subprocess
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fast-livo-noted_amd", "lib",
                        "wave_nth_check")
     r = subprocess.run([exe, "20000"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 mismatches" in r.stdout
+    m = re.search(r"depth limit reached: wave_nth (\d+) wave_nth_big (\d+) team_nth (\d+)", r.stdout)
+    assert m, r.stdout
+    assert all(int(g) > 0 for g in m.groups()), r.stdout
 
 
 @pytest.mark.parametrize("kind", ["wave", "thread", "team"])

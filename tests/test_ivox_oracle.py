@@ -228,3 +228,117 @@ def test_ivox_iekf_converges(built):
     # a second search from the updated state re-finds about the same matches
     h = iv.h_share(body, st1["rot"], st1["pos"], np.eye(3), synth.T_LI, True, cache)
     assert h["effct"] >= 0.9 * stats["effct_feat_num"][-1]
+
+
+# ---------------------------------------------------------------------------------------------
+# The search cascade's rare branches (tests/ivox_cascade_cases.py; GPU side: tests/test_gpu_ivox_cascade.py)
+@pytest.fixture(scope="module")
+def adv_cli(tmp_path_factory):
+    import ivox_cascade_cases as cc
+    return cc.build_cli(tmp_path_factory.mktemp("nth_adversary"))
+
+
+@pytest.mark.parametrize("first", [0, 5])
+@pytest.mark.parametrize("n", [24, 38, 64, 128, 129, 507, 600])
+def test_nth_adversary_reaches_depth_limit(adv_cli, n, first):
+    """tests/native/nth_adversary.h against libstdc++ itself, where the iVox search selects: a range of n
+    elements after `first` others, nth = first + 4.  The sequence is a permutation, the predicate (a
+    replay of introselect's rounds) says the depth limit is reached, and stl_select.h's sel_nth_element
+    equals std::nth_element element for element on it, which compares the __heap_select branch at the
+    nth that iVox uses."""
+    import ivox_cascade_cases as cc
+    seq, st = cc.adversary(adv_cli, first + n, first, first + 4)
+    assert sorted(seq.tolist()) == list(range(first + n))
+    assert st["depth_limit"]
+    assert st["sel_matches_std"]
+    # the predicate is no constant: a sorted range splits evenly, and 16 elements are too few to run out
+    assert not cc.check_keys(adv_cli, np.arange(first + n), first, first + 4)["depth_limit"]
+    assert not cc.adversary(adv_cli, first + 16, first, first + 4)[1]["depth_limit"]
+    # the unmirrored form (pivot to the bottom) gets there for nth near the end, not for nth = first + 4
+    assert cc.adversary(adv_cli, first + n, first, first + n - 5, mirrored=False)[1] == {
+        "depth_limit": True, "sel_matches_std": True}
+
+
+CASCADE_ROUTES = {  # scene -> (the kernel that answers under the default kind, raw points > kWRaw: streams)
+    "one-grid-128": ("team", False), "one-grid-129": ("wave-all", False),
+    "5+123": ("team", False), "5+124": ("wave-all", False),
+    "128-in-range-of-168": ("team", False), "129-in-range-of-169": ("wave-all", False),
+    "raw-512": ("wave-all", False), "raw-513-one-grid": ("big-wave", True), "raw-513-streams": ("wave-stream", True),
+    "stream-5+507": ("wave-stream", True), "stream-5+508": ("big-wave", True),
+    "stream-out-of-range": ("wave-stream", True),
+    "depth-0-24": ("team", False), "depth-0-64": ("team", False), "depth-0-128": ("team", False),
+    "depth-5-24": ("team", False), "depth-5-64": ("team", False), "depth-5-123": ("team", False),
+    "depth-0-300": ("big-wave-lane0", False), "depth-5-300": ("big-wave-lane0", False),
+    "depth-0-501": ("big-wave-lane0", True), "depth-5-500": ("big-wave-lane0", True),
+    "depth-0-600": ("big-wave-lane0", True), "depth-5-600": ("big-wave-lane0", True),
+}
+
+
+def test_cascade_scenes_are_what_they_claim(built, adv_cli):
+    """The scenes of tests/test_gpu_ivox_cascade.py, checked with the oracle and numpy alone so the GPU
+    comparison cannot pass vacuously: for every query the raw point total, the in-range count per grid
+    and the longest list (128 / 129, 512 / 513 raw, 5 + 507 / 5 + 508 staged) are the intended ones, the
+    branch they imply under the code's capacities is the intended one, every adversarial segment makes
+    the introselect predicate say "limit reached" as staged (distances as keys, at its first), and the
+    oracle finds what the counts say."""
+    import ivox_cascade_cases as cc
+    import oracle
+    scenes = cc.capacity_scenes() + [cc.depth_scene(adv_cli, f, n) for f, n in cc.DEPTH_CASES]
+    assert {s["name"] for s in scenes} == set(CASCADE_ROUTES)
+    for s in scenes:
+        ex = s["expect"]
+        pk = cc.keys_of(s["points"], s["res"])
+        max_grid = int(np.unique(pk, axis=0, return_counts=True)[1].max())
+        slice_entries = cc.NEARBY[s["nearby_type"]] * cc.KNN + max_grid + 8
+        iv = oracle.Ivox(resolution=s["res"], nearby_type=s["nearby_type"])
+        iv.add_points(s["points"])
+        _, rd, _, rc = iv.knn(s["queries"], s["max_num"], s["max_range"])
+        for qi, q in enumerate(s["queries"]):
+            tr = cc.trace(s, q)
+            assert (tr["raw"], tr["peak"]) == (ex["raw"], ex["peak"]), (s["name"], qi)
+            want, streams = CASCADE_ROUTES[s["name"]]
+            assert cc.route(tr, ex["limit"], slice_entries) == want, (s["name"], qi)
+            assert (tr["raw"] > cc.WRAW) == streams, (s["name"], qi)
+            assert rc[qi] == min(tr["final"], s["max_num"])
+            assert rd[qi, 0] == min(d.min() for _, d in tr["segs"] if len(d))
+            for t, first, length in s["adv"]:
+                assert tr["counts"][t] == length and tr["segs"][t][0] == first
+                # the adversarial grid's points are the nearest: its selection is what the query returns
+                assert np.array_equal(np.sort(rd[qi]), np.sort(tr["segs"][t][1])[:s["max_num"]])
+                if qi in (0, len(s["queries"]) - 1):
+                    keys = np.concatenate([np.zeros(first, np.float32), tr["segs"][t][1]])
+                    st = cc.check_keys(adv_cli, keys, first, first + 4)
+                    assert st["depth_limit"] and st["sel_matches_std"], (s["name"], qi)
+        if not s["adv"]:  # the shuffled grids split evenly: no depth limit on the way
+            tr = cc.trace(s, s["queries"][0])
+            for first, d in tr["segs"]:
+                if len(d) > s["max_num"]:
+                    keys = np.concatenate([np.zeros(first, np.float32), d])
+                    assert not cc.check_keys(adv_cli, keys, first, first + s["max_num"] - 1)["depth_limit"]
+    # the LDS edge: the largest slice that fits 64 KB, and one entry more
+    g = cc.lds_edge_grid()
+    for over in (False, True):
+        s = cc.lds_scene(over)
+        pk = cc.keys_of(s["points"], s["res"])
+        uk, cnt = np.unique(pk, axis=0, return_counts=True)
+        assert cnt.max() == s["expect"]["max_grid"] == g + over and tuple(uk[cnt.argmax()]) == (0, 0, 0)
+        sl = cc.NEARBY[s["nearby_type"]] * cc.KNN + int(cnt.max()) + 8
+        assert sl == s["expect"]["slice"]
+        assert (sl * cc.ENTRY_BYTES <= cc.LDS_BYTES) == (not over)
+        assert (sl + 1) * cc.ENTRY_BYTES > cc.LDS_BYTES >= (sl - 1) * cc.ENTRY_BYTES
+        qk = cc.keys_of(s["queries"], s["res"])
+        assert {tuple(k) for k in qk} == set(cc.NEAR26[:7])  # the grid's own cell and every neighbour
+        routes, ties = set(), 0
+        for q in s["queries"][::8]:
+            tr = cc.trace(s, q)
+            routes.add(cc.route(tr, False, sl))
+            d = np.concatenate([x for _, x in tr["segs"]])
+            ties += len(d) - len(np.unique(d))
+        assert routes == {"big-global" if over else "big-wave"}
+        assert ties > 1000  # exact duplicate distances: the order inside ties is nth_element's
+    # keys and range: some coordinates do make exact half products, at both resolutions and signs
+    for res in (0.5, 0.2):
+        pts, exact = cc.half_product_points(res)
+        inv = np.float32(1.0 / float(np.float32(res)))
+        prod = (pts[:len(exact), 0] * inv)[exact]
+        assert (prod > 0).sum() >= 3 and (prod < 0).sum() >= 3 and np.all(prod - np.floor(prod) == 0.5)
