@@ -174,10 +174,12 @@ SEL_HD void vis_row10(const uint8_t* img, int64_t o, int* B) {
 // the reference's `0.5 *` promotes it.  The discriminant cannot round below
 // zero here: s is exact (the sums stay below 2^24), s * s >= 4 dXX dYY, and
 // rounding is monotonic.
-SEL_HD float vis_score(const uint8_t* img, int w, int h, int u, int v) {
+// vis_score_at takes the image at byte offset `base` of a 4-byte aligned buffer
+// (a stored frame of the visual map, whose size need be no multiple of 4).
+SEL_HD float vis_score_at(const uint8_t* img, int64_t base, int w, int h, int u, int v) {
     if (u - 4 < 1 || u + 4 >= w - 1 || v - 4 < 1 || v + 4 >= h - 1) return 0.0f;
     int R0[10], R1[10], R2[10];  // rows y - 1, y, y + 1; columns u - 5 .. u + 4
-    const int64_t o = (int64_t)(v - 5) * w + (u - 5);
+    const int64_t o = base + (int64_t)(v - 5) * w + (u - 5);
     vis_row10(img, o, R0);
     vis_row10(img, o + w, R1);
     int sxx = 0, syy = 0, sxy = 0;
@@ -200,6 +202,7 @@ SEL_HD float vis_score(const uint8_t* img, int w, int h, int u, int v) {
     const float r = sqrtf(t);
     return (float)(0.5 * (double)(s - r));
 }
+SEL_HD float vis_score(const uint8_t* img, int w, int h, int u, int v) { return vis_score_at(img, 0, w, h, u, v); }
 
 // One value of LidarSelector::getpatch (lidar_selection.cpp:117-138): element k =
 // x * ps + y of the level's ps x ps patch around pixel pc, x the row.  The

@@ -5071,6 +5071,82 @@ int livo_vio_match(livo_ctx* c, int32_t scan_id, const livo_state* state, const 
     return LIVO_OK;
 }
 
+int livo_vio_observe(livo_ctx* c, int32_t frame_id, int64_t n, const int32_t* point_ids, const int32_t* search_levels,
+                     livo_vobs_point* out, livo_vobs_stats* stats) {
+    if (!c || n < 0 || (n > 0 && !point_ids)) return LIVO_E_INVALID;
+    VmapDev& m = c->vmap;
+    if (!m.ready) return LIVO_E_INVALID;
+    const int slot = vmap_frame_slot(m, frame_id);
+    if (slot < 0) return LIVO_E_INVALID;
+    const int64_t np = (int64_t)m.count.size();
+    if (n > np) return LIVO_E_INVALID;  // (an id twice, or one outside the map)
+    std::vector<int32_t> level((size_t)n, 0);
+    std::vector<uint8_t> listed((size_t)np, 0);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t id = point_ids[i];
+        if (id < 0 || id >= np || listed[(size_t)id]) return LIVO_E_INVALID;
+        listed[(size_t)id] = 1;
+        if (search_levels) {
+            if (search_levels[i] < 0 || search_levels[i] > 8) return LIVO_E_INVALID;
+            level[(size_t)i] = search_levels[i];
+        }
+    }
+    std::vector<livo_vobs_point> rec((size_t)n);
+    unsigned long long ctr[kVoCtrN] = {};
+    if (n > 0) {
+        if (set_device(c)) return LIVO_E_HIP;
+        VmObserveParams P{};
+        static_cast<CamIntrinsics&>(P.cam) = m.K;
+        const VmFrame& f = m.frames[(size_t)slot];
+        std::memcpy(P.cam.Rcw, f.Rcw, sizeof(f.Rcw));
+        std::memcpy(P.cam.Pcw, f.Pcw, sizeof(f.Pcw));
+        std::memcpy(P.cpos, f.pos, sizeof(f.pos));
+        P.map = m.dev;
+        P.n = (int32_t)n;
+        P.ps = m.ps;
+        P.border = (m.ps / 2 + 1) * 8;
+        P.slot = slot;
+        P.frame_id = frame_id;
+        int32_t *d_point, *d_level;
+        auto layout = [&](Carve k) {
+            P.ctr = k.take<unsigned long long>(kVoCtrN);
+            P.rec = k.take<livo_vobs_point>((size_t)n);
+            P.point = d_point = k.take<int32_t>((size_t)n);
+            P.level = d_level = k.take<int32_t>((size_t)n);
+            return k.total();
+        };
+        RC_TRY(ensure_scratch(c, layout(Carve{nullptr})));
+        layout(Carve{(char*)c->scratch});
+        HIP_TRY(hipMemsetAsync(P.ctr, 0, sizeof(ctr), c->stream));
+        HIP_TRY(hipMemcpyAsync(d_point, point_ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_level, level.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        RC_TRY(launch_vm_observe(P, c->stream));
+        HIP_TRY(hipMemcpyAsync(ctr, P.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(rec.data(), P.rec, (size_t)n * sizeof(livo_vobs_point), hipMemcpyDeviceToHost,
+                               c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (const livo_vobs_point& r : rec) {  // the device decided the counts: the host's copy follows
+            int32_t& cnt = m.count[(size_t)r.point_id];
+            m.n_obs += (int64_t)r.n_obs - cnt;
+            cnt = r.n_obs;
+        }
+        if (out) std::memcpy(out, rec.data(), (size_t)n * sizeof(livo_vobs_point));
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->n_in = n;
+        stats->behind = (int64_t)ctr[kVoCtrBehind];
+        stats->out_of_frame = (int64_t)ctr[kVoCtrOutOfFrame];
+        stats->pose_flagged = (int64_t)ctr[kVoCtrPose];
+        stats->pixel_flagged = (int64_t)ctr[kVoCtrPixel];
+        stats->added = (int64_t)ctr[kVoCtrAdded];
+        stats->deleted = (int64_t)ctr[kVoCtrDeleted];
+        stats->deleted_without_add = (int64_t)ctr[kVoCtrBare];
+        stats->n_obs_total = m.n_obs;
+    }
+    return LIVO_OK;
+}
+
 int livo_sync(livo_ctx* c) {
     if (!c) return LIVO_E_INVALID;
     if (set_device(c)) return LIVO_E_HIP;

@@ -730,6 +730,21 @@ struct VmPutParams {
     const int32_t* count;     // n: the point's count after the call
 };
 int launch_vm_put(const VmPutParams& p, void* stream);
+// livo_vio_observe (LidarSelector::addObservation): n distinct points of the map
+// against the stored frame `slot`; one wave owns one point.
+enum { kVoCtrBehind = 0, kVoCtrOutOfFrame, kVoCtrPose, kVoCtrPixel, kVoCtrAdded, kVoCtrDeleted, kVoCtrBare, kVoCtrN };
+struct VmObserveParams {
+    VmStore map;
+    FrameCam cam;             // the map's intrinsics at the frame's stored Rcw, Pcw
+    double cpos[3];           // the frame's stored position
+    int32_t n, ps, border;
+    int32_t slot, frame_id;   // the frame's slot in the store and its id
+    const int32_t* point;     // n point ids, no id twice
+    const int32_t* level;     // n search levels
+    livo_vobs_point* rec;     // n records, input order
+    unsigned long long* ctr;  // kVoCtrN counters, zeroed by the caller
+};
+int launch_vm_observe(const VmObserveParams& p, void* stream);
 // laserCloudOri / corr_normvect compaction in the caller's order (stored-order sel / normvec / points).
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream);
 int launch_ori_scatter(const float* pts4, const float* normvec, const uint8_t* sel, const int32_t* perm,

@@ -25,6 +25,9 @@
 //   k_vm_scatter  behind an exclusive scan of the keep flags: one wave per
 //                 survivor copies its record, position, level and patches.
 //   k_vm_put      livo_vmap_add: one wave per staged observation.
+//   k_vm_observe  livo_vio_observe (addObservation, :905-962): one wave per
+//                 matched point; the add decision, the eviction at 20
+//                 observations and the new observation, in the map.
 // No position is decided by an atomic: two calls give the same bytes.
 // Numerics as livo_kernels.hip: -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -269,6 +272,139 @@ __global__ __launch_bounds__(kVmBlock) void k_vm_put(VmPutParams P) {
     for (int e = lane; e < P.pst3; e += 64) dst[e] = src[e];
 }
 
+// p[e] = p[e + s] for e in [0, total), s > 0: words moved to lower addresses over
+// a range that overlaps itself, by one wave.  It goes upwards in chunks of
+// kVmShift * 64 words: all of a chunk's loads are in registers (vmcnt(0)) before
+// its first store is issued, so a store never reaches a word that the chunk has
+// yet to read, whatever s is (12 or 48 words of a small patch pyramid, 14 of an
+// observation: source and destination overlap inside one chunk); later chunks
+// read only above what earlier ones wrote.
+typedef uint32_t __attribute__((may_alias)) vm_word;
+constexpr int kVmShift = 4;
+__device__ __forceinline__ void vm_shift_down(vm_word* p, int total, int s, int lane) {
+    for (int base = 0; base < total; base += kVmShift * 64) {
+        vm_word v[kVmShift];
+#pragma unroll
+        for (int u = 0; u < kVmShift; u++) {
+            const int e = base + u * 64 + lane;
+            v[u] = e < total ? p[e + s] : 0u;
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+#pragma unroll
+        for (int u = 0; u < kVmShift; u++) {
+            const int e = base + u * 64 + lane;
+            if (e < total) p[e] = v[u];
+        }
+    }
+}
+
+// livo_vio_observe, LidarSelector::addObservation (:905-962): one wave per item,
+// and no point twice, so nothing one wave writes is read by another.  The
+// projection, delta_p, the pixel distance and the flags are computed alike on
+// every lane; the <= 20 frame distances one per lane into LDS, the choice
+// (vm_furthest_view) read from there; the 3 ps^2 samples of the new patch
+// pyramid spread over the lanes; the eviction's compaction by the whole wave.
+// Everything the item reads of its point is read before the first write.
+__global__ __launch_bounds__(kVmBlock) void k_vm_observe(VmObserveParams P) {
+    static_assert(sizeof(VmObs) % 4 == 0 && sizeof(livo_vobs_point) == 56, "whole words; a 56-B record");
+    constexpr int kObsWords = (int)(sizeof(VmObs) / 4);
+    __shared__ double s_dist[kVmWaves][kVmMaxObs];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * kVmWaves + wave;
+    const bool live = i < P.n;
+    const int pst = P.ps * P.ps, pst3 = 3 * pst;
+    int id = 0, n_obs = 0, fate = kVmObsBehind;
+    double pc[2] = {0.0, 0.0}, delta_p = 0.0, pixel_dist = 0.0;
+    VmObs* obs = nullptr;
+    if (live) {
+        id = P.point[i];
+        const VmPoint& pt = P.map.pt[id];
+        n_obs = pt.n_obs;  // (1 .. kVmMaxObs: the host keeps the counts)
+        obs = P.map.obs + (size_t)id * kVmMaxObs;
+        const double pos[3] = {pt.pos[0], pt.pos[1], pt.pos[2]};
+        fate = vm_observe_project(P.cam, P.border, pos, pc);
+        if (fate == kVmObsIn) {
+            delta_p = vm_observe_delta_p(P.map.frame[obs[0].slot], P.cpos);
+            pixel_dist = vm_pixel_dist(pc, obs[0].px);
+            if (n_obs >= kVmMaxObs && lane < kVmMaxObs)
+                s_dist[wave][lane] = vm_view_dist(P.map.frame[obs[lane].slot].pos, P.cpos);
+        } else {
+            pc[0] = pc[1] = 0.0;
+        }
+    }
+    __syncthreads();
+    bool pose = false, pixel = false, added = false, deleted = false;
+    int del = -1, del_frame = -1;
+    float score = 0.0f;
+    if (live && fate == kVmObsIn) {
+        pose = delta_p > 0.5;
+        pixel = pixel_dist > 40.0;
+        added = pose || pixel;
+        float fresh[3] = {0.0f, 0.0f, 0.0f};  // (3 ps^2 <= 192: at most 3 samples a lane)
+        if (added) {
+            const int64_t at = (int64_t)P.slot * P.cam.w * P.cam.h;
+            score = vis_score_at(P.map.img, at, P.cam.w, P.cam.h, (int)pc[0], (int)pc[1]);
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                const int e = q * 64 + lane, level = e / pst;
+                if (e < pst3) fresh[q] = vis_getpatch(P.map.img + at, P.cam.w, pc, P.ps, level, e - level * pst);
+            }
+        }
+        float* patch = P.map.patch + (size_t)id * kVmMaxObs * pst3;
+        if (n_obs >= kVmMaxObs) {  // getFurthestViewObs / deleteFeatureRef, add_flag or not
+            del = vm_furthest_view(s_dist[wave], kVmMaxObs);
+            del_frame = obs[del].frame_id;
+            const int rest = kVmMaxObs - 1 - del;
+            vm_shift_down((vm_word*)(obs + del), rest * kObsWords, kObsWords, lane);
+            vm_shift_down((vm_word*)(patch + (size_t)del * pst3), rest * pst3, pst3, lane);
+            n_obs = kVmMaxObs - 1;
+            deleted = true;
+        }
+        if (added) {  // addFrameRef
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                const int e = q * 64 + lane;
+                if (e < pst3) patch[(size_t)n_obs * pst3 + e] = fresh[q];
+            }
+            if (lane == 0) {
+                VmObs o{};
+                o.frame_id = P.frame_id;
+                o.level = P.level[i];
+                o.slot = P.slot;
+                o.px[0] = pc[0];
+                o.px[1] = pc[1];
+                vm_cam2world(P.cam, pc[0], pc[1], o.f);
+                obs[n_obs] = o;
+                P.map.pt[id].value = score;
+            }
+            n_obs += 1;
+        }
+        if (lane == 0 && (added || deleted)) P.map.pt[id].n_obs = n_obs;
+    }
+    if (live && lane == 0) {
+        livo_vobs_point r;
+        r.point_id = id;
+        r.flags = (fate == kVmObsBehind ? LIVO_VOBS_BEHIND : 0) | (fate == kVmObsOutOfFrame ? LIVO_VOBS_OUT_OF_FRAME : 0) |
+                  (pose ? LIVO_VOBS_POSE : 0) | (pixel ? LIVO_VOBS_PIXEL : 0) | (deleted ? LIVO_VOBS_DELETED : 0) |
+                  (added ? LIVO_VOBS_ADDED : 0);
+        r.n_obs = n_obs;
+        r.deleted_index = del;
+        r.deleted_frame_id = del_frame;
+        r.score = score;
+        r.u = pc[0];
+        r.v = pc[1];
+        r.delta_p = delta_p;
+        r.pixel_dist = pixel_dist;
+        P.rec[i] = r;
+    }
+    static_assert(kVoCtrBehind == 0 && kVoCtrBare == 6 && kVoCtrN == 7, "the order");
+    const bool one = live && lane == 0;  // a wave's item counts once
+    const bool pred[7] = {one && fate == kVmObsBehind, one && fate == kVmObsOutOfFrame, one && pose, one && pixel,
+                          one && added, one && deleted, one && deleted && !added};
+    const uint32_t v = block_tally<kVmWaves>(pred);
+    if (threadIdx.x < 7 && v) atomicAdd(P.ctr + threadIdx.x, (unsigned long long)v);
+}
+
 static inline unsigned vm_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 #define VM_LAUNCH(kernel, count, per)                                                                        \
@@ -284,5 +420,6 @@ int launch_vm_scatter(const VmatchParams& p, void* stream) {
     VM_LAUNCH(k_vm_scatter, (int64_t)p.grid.length, kVmWaves);
 }
 int launch_vm_put(const VmPutParams& p, void* stream) { VM_LAUNCH(k_vm_put, (int64_t)p.n, kVmWaves); }
+int launch_vm_observe(const VmObserveParams& p, void* stream) { VM_LAUNCH(k_vm_observe, (int64_t)p.n, kVmWaves); }
 
 }  // namespace livo

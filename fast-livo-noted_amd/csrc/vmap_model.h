@@ -7,6 +7,13 @@
 // for host and device (SEL_HD), as cam_model.h, so tests/native/vmatch_point_check.cpp
 // runs the kernels' code on the CPU.  Numerics: -ffp-contract=off, one IEEE operation
 // per step in the order DESIGN.md §8.9 states; 3-term sums left to right.
+//
+// At the end, the arithmetic of one item of LidarSelector::addObservation
+// (src/lidar_selection.cpp:905-962) with Point::getFurthestViewObs
+// (src/point.cpp:211-239): the projection and its two skips, delta_p, the pixel
+// distance and the observation to evict.  The reference's `delta_theta > 10`
+// compares an acos (at most pi; NaN compares false) with 10: it never holds and
+// is not computed.  tests/native/vobserve_point_check.cpp runs these on the CPU.
 #pragma once
 #include "cam_model.h"
 
@@ -246,6 +253,54 @@ SEL_HD float vm_error(const float* ref, const float* cur, int n) {
     float e = 0.0f;
     for (int i = 0; i < n; i++) e += (ref[i] - cur[i]) * (ref[i] - cur[i]);
     return e;
+}
+
+// ---- addObservation (:905-962) --------------------------------------------
+enum VmObsFate : int { kVmObsIn = 0, kVmObsBehind = 1, kVmObsOutOfFrame = 2 };
+
+// The item's pixel: skipped behind the camera (pt_cam.z <= 0: a NaN passes, and
+// then fails the frame test) or outside the border under which vis_getpatch's
+// taps are inside the image (the reference has no such test and reads outside).
+SEL_HD int vm_observe_project(const FrameCam& C, int border, const double* pos, double* pc) {
+    double pf[3];
+    cam_w2f(C.Rcw, C.Pcw, pos, pf);
+    if (pf[2] <= 0) return kVmObsBehind;
+    vio_world2cam(C, pf, pc);
+    return vm_in_frame(C, border, pc) ? kVmObsIn : kVmObsOutOfFrame;
+}
+
+// delta_p = |(pose_ref * pose_cur.inverse()).translation()| = |ref.Rcw cur.pos + ref.Pcw|.
+SEL_HD double vm_observe_delta_p(const VmFrame& ref, const double* cur_pos) {
+    double t[3];
+    cam_w2f(ref.Rcw, ref.Pcw, cur_pos, t);
+    return vm_norm3(t);
+}
+
+// (pc - last_px).norm().
+SEL_HD double vm_pixel_dist(const double* pc, const double* px) {
+    const double dx = pc[0] - px[0], dy = pc[1] - px[1];
+    return sqrt(dx * dx + dy * dy);
+}
+
+// getFurthestViewObs's distance of one observation's frame from the current one.
+SEL_HD double vm_view_dist(const double* ref_pos, const double* cur_pos) {
+    const double d[3] = {ref_pos[0] - cur_pos[0], ref_pos[1] - cur_pos[1], ref_pos[2] - cur_pos[2]};
+    return vm_norm3(d);
+}
+
+// getFurthestViewObs over the n distances in this map's list order (the
+// reference's obs_ runs the other way: its front is index n - 1): from the
+// highest index down, the first strictly above a maximum that starts at 0, so the
+// newest among equal maxima, and index n - 1 if none exceeds 0 (all zero or NaN).
+SEL_HD int vm_furthest_view(const double* dist, int n) {
+    int best = n - 1;
+    double maxdist = 0.0;
+    for (int k = n - 1; k >= 0; k--)
+        if (dist[k] > maxdist) {
+            maxdist = dist[k];
+            best = k;
+        }
+    return best;
 }
 
 }  // namespace livo

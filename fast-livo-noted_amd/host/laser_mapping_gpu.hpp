@@ -272,6 +272,26 @@ public:
         return st;
     }
 
+    // lidar_selector->addObservation(img) (lidar_selection.cpp:905-962) on the resident visual
+    // map: `points` are the records addFromSparseMap returned for this frame (sub_sparse_map's
+    // voxel_points and search_levels), frame_id the frame stored with livo_vmap_add_frame at
+    // the state after the update (new_frame_ after updateFrameState; its stored image is img).
+    // `records`, if given, takes one livo_vobs_point per point, in the same order.
+    livo_vobs_stats addObservation(int32_t frame_id, const std::vector<livo_vmatch_point>& points,
+                                   std::vector<livo_vobs_point>* records = nullptr) {
+        std::vector<int32_t> ids(points.size()), levels(points.size());
+        for (size_t k = 0; k < points.size(); k++) {
+            ids[k] = points[k].point_id;
+            levels[k] = points[k].search_level;
+        }
+        if (records) records->resize(points.size());
+        livo_vobs_stats st{};
+        check(livo_vio_observe(ctx_, frame_id, (int64_t)points.size(), ids.data(), levels.data(),
+                               records ? records->data() : nullptr, &st),
+              "livo_vio_observe");
+        return st;
+    }
+
     livo_ctx* ctx() const { return ctx_; }
     const livo_params& params() const { return params_; }
 

@@ -13,6 +13,7 @@ path:
     LidarSelector::addSparseMap          -> Context.vio_select
     feat_map / imgs_ (the visual map)    -> Context.vmap_reset / vmap_add_frame / vmap_add / vmap_dump
     LidarSelector::addFromSparseMap      -> Context.vio_match
+    LidarSelector::addObservation        -> Context.vio_observe
 
 There is no CPU fallback: loading fails loudly if the HIP library is missing,
 and every compute call raises LivoError when the GPU path fails.
@@ -206,6 +207,19 @@ class VmatchStats(C.Structure):
         "view_rejected", "ncc_rejected", "error_rejected", "warp_shared", "warp_nan", "n_out")]
 
 
+VOBS_POINT_DTYPE = np.dtype([("point_id", np.int32), ("flags", np.int32), ("n_obs", np.int32),
+                             ("deleted_index", np.int32), ("deleted_frame_id", np.int32), ("score", np.float32),
+                             ("u", np.float64), ("v", np.float64), ("delta_p", np.float64),
+                             ("pixel_dist", np.float64)])
+VOBS_BEHIND, VOBS_OUT_OF_FRAME, VOBS_POSE, VOBS_PIXEL, VOBS_DELETED, VOBS_ADDED = 1, 2, 4, 8, 16, 32  # LIVO_VOBS_*
+
+
+class VobsStats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in (
+        "n_in", "behind", "out_of_frame", "pose_flagged", "pixel_flagged", "added", "deleted", "deleted_without_add",
+        "n_obs_total")]
+
+
 def vio_params(cam: dict, Rci, Pci) -> VioParams:
     """livo_vio_params from a camera dict (fx, fy, cx, cy, d, width, height) and the extrinsics."""
     p = VioParams()
@@ -285,6 +299,7 @@ SIGNATURES = {
     "livo_vio_match": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.POINTER(VioParams), C.c_int32, C.c_int32,
                                  C.c_double, C.c_double, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64,
                                  C.POINTER(C.c_int64), C.POINTER(VmatchStats)]),
+    "livo_vio_observe": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.POINTER(VobsStats)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -942,6 +957,21 @@ class Context:
         if img is not None:
             out["image"] = img
         return out
+
+    def vio_observe(self, frame_id: int, point_ids, levels=None):
+        """LidarSelector::addObservation (livo_vio_observe): the resident visual map brought up to date with the
+        stored frame frame_id (stored at the state after vio_update).  point_ids / levels: the point_id and
+        search_level columns of vio_match's records (levels None: 0); no id twice.  Returns (records:
+        VOBS_POINT_DTYPE in input order, stats: dict)."""
+        ids = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        lev = None if levels is None else np.ascontiguousarray(levels, np.int32).reshape(-1)
+        if lev is not None and len(lev) != len(ids):
+            raise ValueError("point_ids and levels disagree in length")
+        rec = np.zeros(len(ids), VOBS_POINT_DTYPE)
+        vs = VobsStats()
+        _check("livo_vio_observe", self._L.livo_vio_observe(
+            self.h, frame_id, len(ids), _ptr(ids), _ptr(lev), _ptr(rec), C.byref(vs)))
+        return rec, {f: int(getattr(vs, f)) for f, _ in VobsStats._fields_}
 
     def scan_inherit_neighbors(self, dst: int, src: int):
         _check("livo_scan_inherit_neighbors", self._L.livo_scan_inherit_neighbors(self.h, dst, src))

@@ -604,12 +604,17 @@ int livo_vio_select(livo_ctx* ctx, int32_t scan_id, const livo_state* state, con
                     livo_vis_point* out, float* patches, int64_t cap, int64_t* n, livo_vis_stats* stats);
 /* ------------------------------------------------------------------------
  * The resident visual map (LidarSelector::feat_map, imgs_ and the features'
- * T_f_w_): plain storage with no policy.  Points hold a position, a score, a
- * voxel key and up to 20 observations (addObservation's cap, :945); an
- * observation holds its frame id, px, f = cam2world(px), level and its patch
- * pyramid (3 x patch_size^2 floats, Feature::patch layout); a frame holds its
- * gray image and pose.  addObservation's decision logic (add_flag,
- * getFurthestViewObs / deleteFeatureRef) and releasing frames are not here.
+ * T_f_w_).  Points hold a position, a score, a voxel key and up to 20
+ * observations (addObservation's cap, :945), kept in insertion order (index 0
+ * the oldest held; the reference's obs_ is filled with push_front and runs the
+ * other way); an observation holds its frame id, px, f = cam2world(px), level
+ * and its patch pyramid (3 x patch_size^2 floats, Feature::patch layout); a
+ * frame holds its gray image and pose.  livo_vmap_add stores what it is given
+ * and never deletes; addObservation's policy (add_flag, the cap,
+ * getFurthestViewObs / deleteFeatureRef, the new patch pyramid and score) is
+ * livo_vio_observe below, which edits the map on the device.  Releasing stored
+ * frames is not here: an eviction can leave a frame that no observation refers
+ * to, and it keeps its slot.
  * ------------------------------------------------------------------------ */
 typedef struct livo_vmap_counts {
     int64_t n_points, n_obs, n_frames;
@@ -721,6 +726,64 @@ int livo_vio_match(livo_ctx* ctx, int32_t scan_id, const livo_state* state, cons
                    int32_t grid_size, int32_t ncc_en, double ncc_thre, double outlier_threshold,
                    const uint8_t* gray, int32_t width, int32_t height, livo_vmatch_point* out, double* pos,
                    int32_t* search_levels, float* patches, int64_t cap, int64_t* n, livo_vmatch_stats* stats);
+/* LidarSelector::addObservation (src/lidar_selection.cpp:905-962, with
+ * Point::addFrameRef, deleteFeatureRef and getFurthestViewObs, src/point.cpp:
+ * 61-65, 88-98, 211-239): the resident visual map brought up to date with the
+ * frame just processed.  frame_id names a frame stored with livo_vmap_add_frame
+ * at the state after livo_vio_update (new_frame_ after updateFrameState): its
+ * stored Rcw / Pcw / position are new_frame_->T_f_w_ and pos(), its stored
+ * image is img; the call takes no image and no state.  point_ids and
+ * search_levels (n each; search_levels NULL: 0) are sub_sparse_map's
+ * voxel_points and search_levels: the point_id and search_level columns of
+ * livo_vio_match.  For every item, in this map's list order (index 0 = the
+ * reference's obs_.back(), index n_obs - 1 its front):
+ *   pt_cam = Rcw pos + Pcw; pt_cam.z <= 0 skips the item (a NaN passes);
+ *   pc = world2cam(pt_cam); a pc outside the border (patch_size / 2 + 1) * 8
+ *   skips it too (the reference has no such test: its getpatch and
+ *   shiTomasiScore would read outside the image there).  A skipped item leaves
+ *   its point untouched, also at 20 observations.
+ *   add_flag: delta_p = |ref.Pcw + ref.Rcw cur.pos| > 0.5, ref the frame of
+ *   observation 0, or |pc - px of observation 0| > 40.  (`delta_theta > 10`
+ *   compares an acos with 10: it never holds and is not computed.)
+ *   A point at 20 observations loses getFurthestViewObs(cur.pos)'s choice
+ *   whether add_flag is set or not: the observation whose frame lies furthest
+ *   from the current one, the newest among equals, the newest of all if no
+ *   distance exceeds 0; the later ones move down by one.
+ *   With add_flag the point's value becomes shiTomasiScore(img, (int)pc.x,
+ *   (int)pc.y) and an observation of frame_id is appended: px = pc, f =
+ *   cam2world(pc), the item's level, getpatch at levels 0, 1, 2.
+ * out (n records in input order) and stats may be NULL.  Everything is
+ * validated before anything is written: LIVO_E_INVALID for no map, an unknown
+ * frame, n < 0, an id outside the map, a level outside 0..8 and a point id
+ * listed twice (the reference has one point per grid cell).  n == 0 is
+ * LIVO_OK.  DESIGN.md §8.10 has the arithmetic.  Two calls on the same input
+ * give the same bytes. */
+#define LIVO_VOBS_BEHIND       1     /* skipped: pt_cam.z <= 0                                        */
+#define LIVO_VOBS_OUT_OF_FRAME 2     /* skipped: pc outside the border                                */
+#define LIVO_VOBS_POSE         4     /* delta_p > 0.5                                                 */
+#define LIVO_VOBS_PIXEL        8     /* pixel_dist > 40                                               */
+#define LIVO_VOBS_DELETED      16    /* an observation was evicted                                    */
+#define LIVO_VOBS_ADDED        32    /* an observation was appended                                   */
+typedef struct livo_vobs_point {     /* 56 bytes */
+    int32_t point_id;
+    int32_t flags;                   /* LIVO_VOBS_* bits                                              */
+    int32_t n_obs;                   /* the point's observations after the call                       */
+    int32_t deleted_index;           /* the evicted observation's index before the call, -1: none     */
+    int32_t deleted_frame_id;        /* ... and its frame, -1: none                                   */
+    float   score;                   /* the new Point::value, 0 if nothing was added                  */
+    double  u, v;                    /* pc; 0 for a skipped item, as delta_p and pixel_dist           */
+    double  delta_p, pixel_dist;
+} livo_vobs_point;
+typedef struct livo_vobs_stats {
+    int64_t n_in;
+    int64_t behind, out_of_frame;    /* skipped items                                                 */
+    int64_t pose_flagged, pixel_flagged;
+    int64_t added, deleted;
+    int64_t deleted_without_add;     /* points at 20 observations that lost one and gained none       */
+    int64_t n_obs_total;             /* the map's observations after the call                         */
+} livo_vobs_stats;
+int livo_vio_observe(livo_ctx* ctx, int32_t frame_id, int64_t n, const int32_t* point_ids,
+                     const int32_t* search_levels, livo_vobs_point* out, livo_vobs_stats* stats);
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
