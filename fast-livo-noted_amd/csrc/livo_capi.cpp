@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <chrono>
 #include <thread>
@@ -120,7 +121,9 @@ struct VmapDev {
     VmStore dev{};                 // the arrays in buf / img, n_points and n_frames
     CamIntrinsics K{};             // of the frames (the first one's)
     std::vector<int32_t> count;    // observations per point
-    std::vector<VmFrame> frames;   // by slot
+    std::vector<VmFrame> frames;   // by slot; id < 0: released (livo_vmap_release_frames)
+    std::vector<int32_t> free_slots;  // the released slots, descending: the lowest is taken first
+    int64_t live_frames() const { return (int64_t)frames.size() - (int64_t)free_slots.size(); }
 };
 
 // The device iVox map and its AddPoints / overflow-pass scratch.
@@ -370,7 +373,10 @@ struct livo_ctx {
     DevImage match_img;                // livo_vio_match: the last uploaded gray image (reused by gray == NULL)
     void* vm_buf = nullptr;            // ... and its voxel set, depth image, bids, records and patches
     size_t vm_bytes = 0;
-    void* prim_tmp = nullptr;          // rocPRIM scratch (sorts, scans)
+    DevImage det_img;                  // livo_vio_detect: the frame's gray image, uploaded once
+    void* det_buf = nullptr;           // ... and every stage's arrays, one carve
+    size_t det_bytes = 0;
+    void* prim_tmp = nullptr;         // rocPRIM scratch (sorts, scans)
     size_t prim_bytes = 0;
     // scans
     std::vector<ScanBuf> scans;
@@ -2022,6 +2028,8 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->vis_buf) (void)hipFree(c->vis_buf);
     dev_free(c->match_img.p);
     if (c->vm_buf) (void)hipFree(c->vm_buf);
+    dev_free(c->det_img.p);
+    if (c->det_buf) (void)hipFree(c->det_buf);
     if (c->vmap.buf) (void)hipFree(c->vmap.buf);
     if (c->vmap.img) (void)hipFree(c->vmap.img);
     dev_free(c->nodes);
@@ -4329,6 +4337,52 @@ int livo_vio_params_default(livo_vio_params* p) {
     return LIVO_OK;
 }
 
+// ---- livo_vio_update's body: the constants of p, the launches, the statistics ----
+// (pos, levels, patches, partial, perr, slot, n and nblk are the caller's)
+static VioParams update_params(const livo_vio_params* p, int32_t width, int32_t height) {
+    VioParams P{};
+    P.cam = cam_intrinsics(p->cam, width, height);
+    P.ps = p->patch_size;
+    std::memcpy(P.Rci, p->R_ci, sizeof(P.Rci));
+    std::memcpy(P.Pci, p->P_ci, sizeof(P.Pci));
+    // init() (lidar_selection.cpp:44-55): Jdphi_dR = Rci, Jdp_dR = -Rci [Pic]x, Pic = -Rci^T Pci
+    std::memcpy(P.Jdphi_dR, p->R_ci, sizeof(P.Jdphi_dR));
+    double Pic[3];
+    for (int a = 0; a < 3; a++)
+        Pic[a] = -((p->R_ci[0 * 3 + a] * p->P_ci[0] + p->R_ci[1 * 3 + a] * p->P_ci[1]) + p->R_ci[2 * 3 + a] * p->P_ci[2]);
+    const double tmp[9] = {0.0, -Pic[2], Pic[1], Pic[2], 0.0, -Pic[0], -Pic[1], Pic[0], 0.0};
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++)
+            P.Jdp_dR[a * 3 + b] = ((-p->R_ci[a * 3 + 0]) * tmp[0 * 3 + b] + (-p->R_ci[a * 3 + 1]) * tmp[1 * 3 + b]) +
+                                  (-p->R_ci[a * 3 + 2]) * tmp[2 * 3 + b];
+    P.img_cov = p->img_point_cov;
+    P.max_iter = p->max_iterations;
+    return P;
+}
+// Queues ComputeJ on c->stream: the slot holds state and prior, P.perr is cleared here.
+static int update_queue(livo_ctx* c, VioParams P) {
+    if (P.n > 0) HIP_TRY(hipMemsetAsync(P.perr, 0, (size_t)P.n * 4, c->stream));  // errors: 0 until an iteration runs
+    int rc = LIVO_OK;
+    for (int level = 2; level >= 0 && !rc; level--) {  // ComputeJ (:970-974)
+        P.level = level;
+        rc = launch_vio_begin(P, level, c->stream);
+        for (int it = 0; it < P.max_iter && !rc; it++) rc = launch_vio_iter(P, c->stream);
+    }
+    if (!rc) rc = launch_vio_end(P, c->stream);
+    return rc;
+}
+static void update_stats(const VioSlot& hs, livo_vio_stats* stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    for (int k = 0; k < 3; k++) {
+        stats->iterations[k] = hs.ctrl.iters[k];
+        stats->updates[k] = hs.ctrl.updates[k];
+        stats->last_error[k] = hs.ctrl.level_error[k];
+    }
+    stats->cov_updated = hs.ctrl.cov_updated;
+    stats->n_meas = hs.ctrl.n_meas;
+    stats->out_of_frame = (int64_t)hs.ctrl.oof;
+}
+
 int livo_vio_update(livo_ctx* c, const livo_vio_params* p, const uint8_t* image, int32_t width, int32_t height,
                     const double* pos, const int32_t* levels, const float* patches, int64_t n, livo_state* state,
                     const livo_state* prior, float* errors, livo_vio_stats* stats) {
@@ -4371,56 +4425,22 @@ int livo_vio_update(livo_ctx* c, const livo_vio_params* p, const uint8_t* image,
         HIP_TRY(hipMemcpyAsync(d_pat, patches, (size_t)n * 3 * pst * 4, hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(d_slot, &hs, sizeof(hs), hipMemcpyHostToDevice, c->stream));
-    if (n > 0) HIP_TRY(hipMemsetAsync(d_err, 0, (size_t)n * 4, c->stream));  // errors: 0 until an iteration runs
-    VioParams P{};
+    VioParams P = update_params(p, width, height);
     P.img = d_img;
-    P.cam = cam_intrinsics(p->cam, width, height);
     P.n = (int32_t)n;
-    P.ps = p->patch_size;
     P.pos = d_pos;
     P.levels = d_lev;
     P.patches = d_pat;
-    std::memcpy(P.Rci, p->R_ci, sizeof(P.Rci));
-    std::memcpy(P.Pci, p->P_ci, sizeof(P.Pci));
-    // init() (lidar_selection.cpp:44-55): Jdphi_dR = Rci, Jdp_dR = -Rci [Pic]x, Pic = -Rci^T Pci
-    std::memcpy(P.Jdphi_dR, p->R_ci, sizeof(P.Jdphi_dR));
-    double Pic[3];
-    for (int a = 0; a < 3; a++)
-        Pic[a] = -((p->R_ci[0 * 3 + a] * p->P_ci[0] + p->R_ci[1 * 3 + a] * p->P_ci[1]) + p->R_ci[2 * 3 + a] * p->P_ci[2]);
-    const double tmp[9] = {0.0, -Pic[2], Pic[1], Pic[2], 0.0, -Pic[0], -Pic[1], Pic[0], 0.0};
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++)
-            P.Jdp_dR[a * 3 + b] = ((-p->R_ci[a * 3 + 0]) * tmp[0 * 3 + b] + (-p->R_ci[a * 3 + 1]) * tmp[1 * 3 + b]) +
-                                  (-p->R_ci[a * 3 + 2]) * tmp[2 * 3 + b];
-    P.img_cov = p->img_point_cov;
-    P.max_iter = p->max_iterations;
     P.nblk = nblk;
     P.partial = d_par;
     P.perr = d_err;
     P.slot = d_slot;
-    int rc = LIVO_OK;
-    for (int level = 2; level >= 0 && !rc; level--) {  // ComputeJ (:970-974)
-        P.level = level;
-        rc = launch_vio_begin(P, level, c->stream);
-        for (int it = 0; it < p->max_iterations && !rc; it++) rc = launch_vio_iter(P, c->stream);
-    }
-    if (!rc) rc = launch_vio_end(P, c->stream);
-    if (rc) return rc;
+    RC_TRY(update_queue(c, P));
     HIP_TRY(hipMemcpyAsync(&hs, d_slot, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
     if (errors && n > 0) HIP_TRY(hipMemcpyAsync(errors, d_err, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n > 0) *state = hs.state;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        for (int k = 0; k < 3; k++) {
-            stats->iterations[k] = hs.ctrl.iters[k];
-            stats->updates[k] = hs.ctrl.updates[k];
-            stats->last_error[k] = hs.ctrl.level_error[k];
-        }
-        stats->cov_updated = hs.ctrl.cov_updated;
-        stats->n_meas = hs.ctrl.n_meas;
-        stats->out_of_frame = (int64_t)hs.ctrl.oof;
-    }
+    if (stats) update_stats(hs, stats);
     return LIVO_OK;
 }
 
@@ -4646,14 +4666,18 @@ int livo_cloud_colorize(livo_ctx* c, int32_t scan_id, const livo_state* state, c
     return LIVO_OK;
 }
 
-int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
-                    int32_t grid_size, const uint8_t* gray, int32_t width, int32_t height, livo_vis_point* out,
-                    float* patches, int64_t cap, int64_t* n_out, livo_vis_stats* stats) {
-    if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
-    if (grid_size < 1 || p->patch_size < 1 || p->patch_size > 8 || cap < 0) return LIVO_E_INVALID;
-    if (width <= 0 || height <= 0 || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
-    if (out ? !patches : cap != 0) return LIVO_E_INVALID;
+// ---- livo_vio_select's body: the checks and the grid, the arrays, the launches, the statistics ----
+struct SelectStage {
     VisParams V{};
+    int64_t length = 0;
+    int pst3 = 0;
+};
+// Everything of livo_vio_select that needs no device (image_ok: there is an image to read).
+static int select_prepare(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                          int32_t grid_size, int32_t width, int32_t height, bool image_ok, SelectStage* S) {
+    if (grid_size < 1 || p->patch_size < 1 || p->patch_size > 8) return LIVO_E_INVALID;
+    if (width <= 0 || height <= 0 || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
+    VisParams& V = S->V;
     V.grid.ps = p->patch_size;
     V.grid.border = (p->patch_size / 2 + 1) * 8;
     V.grid.grid_size = grid_size;
@@ -4664,39 +4688,70 @@ int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const
     const int64_t length = (int64_t)(width / grid_size) * V.grid.grid_n_height;
     if (length > (int64_t)0x7FFFFFFF - kVisBlock) return LIVO_E_RANGE;
     V.grid.length = (int32_t)length;
-    if (!gray && !image_reusable(c->gray_img, width, height)) return LIVO_E_INVALID;
+    if (!image_ok) return LIVO_E_INVALID;
     RC_TRY(frame_cloud(c, scan_id, &V.cloud));  // in the caller's point order (iperm)
+    if (V.cloud.n > (int64_t)0x7FFFFFFF - kVisBlock) return LIVO_E_RANGE;
+    S->length = length;
+    S->pst3 = 3 * p->patch_size * p->patch_size;
+    V.W = world_params(c, *state);
+    V.cam = frame_cam(*p, *state);  // once per call
+    return LIVO_OK;
+}
+static void select_layout(SelectStage& S, Carve& k) {
+    VisParams& V = S.V;
+    const size_t length = (size_t)S.length;
+    V.table = k.take<unsigned long long>(length);
+    V.ctr = k.take<unsigned long long>(kVisCtrN);  // (behind the table: one clear for both)
+    V.flag = k.take<uint32_t>(length);
+    V.slot = k.take<uint32_t>(length);
+    V.out = k.take<livo_vis_point>(length);
+    V.patches = k.take<float>(length * S.pst3);
+}
+// Queues the selection of img on c->stream; emit: the records and patches too (V.ctr holds the counts).
+static int select_queue(livo_ctx* c, SelectStage& S, const uint8_t* img, bool emit) {
+    VisParams& V = S.V;
+    V.img = img;
+    if (V.cloud.n <= 0) return LIVO_OK;
+    HIP_TRY(hipMemsetAsync(V.table, 0, (size_t)((char*)(V.ctr + kVisCtrN) - (char*)V.table), c->stream));
+    RC_TRY(launch_vis_score(V, c->stream));
+    RC_TRY(launch_vis_flags(V, c->stream));
+    if (emit) {  // (the table bounds the result: the records are written before their count is known)
+        RC_TRY(ivox_scan(c, V.flag, const_cast<uint32_t*>(V.slot), S.length));
+        RC_TRY(launch_vis_emit(V, c->stream));
+    }
+    return LIVO_OK;
+}
+static void select_stats(const SelectStage& S, const unsigned long long* ctr, livo_vis_stats* stats) {
+    stats->n_in = S.V.cloud.n;
+    stats->in_frame = (int64_t)ctr[kVisCtrInFrame];
+    stats->behind_in_frame = (int64_t)ctr[kVisCtrBehind];
+    stats->cell_overflow = (int64_t)ctr[kVisCtrOverflow];
+    stats->n_out = (int64_t)ctr[kVisCtrOut];
+    stats->n_cells = S.length;
+}
+
+int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                    int32_t grid_size, const uint8_t* gray, int32_t width, int32_t height, livo_vis_point* out,
+                    float* patches, int64_t cap, int64_t* n_out, livo_vis_stats* stats) {
+    if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
+    if (cap < 0 || (out ? !patches : cap != 0)) return LIVO_E_INVALID;
+    SelectStage S;
+    RC_TRY(select_prepare(c, scan_id, state, p, grid_size, width, height,
+                          gray || image_reusable(c->gray_img, width, height), &S));
+    VisParams& V = S.V;
     const int64_t n = V.cloud.n;
-    if (n > (int64_t)0x7FFFFFFF - kVisBlock) return LIVO_E_RANGE;
     if (set_device(c)) return LIVO_E_HIP;
     if (gray) RC_TRY(image_stage(c->gray_img, gray, (size_t)width * (size_t)height, c->stream));
-    const int pst3 = 3 * p->patch_size * p->patch_size;
-    uint32_t* d_slot;
+    const int pst3 = S.pst3;
     auto layout = [&](Carve k) {
-        V.table = k.take<unsigned long long>((size_t)length);
-        V.ctr = k.take<unsigned long long>(kVisCtrN);  // (behind the table: one clear for both)
-        V.flag = k.take<uint32_t>((size_t)length);
-        V.slot = d_slot = k.take<uint32_t>((size_t)length);
-        V.out = k.take<livo_vis_point>((size_t)length);
-        V.patches = k.take<float>((size_t)length * pst3);
+        select_layout(S, k);
         return k.total();
     };
     RC_TRY(ensure_dev_bytes(&c->vis_buf, &c->vis_bytes, layout(Carve{nullptr})));
     layout(Carve{(char*)c->vis_buf});
-    V.W = world_params(c, *state);
-    V.cam = frame_cam(*p, *state);  // once per call
-    V.img = c->gray_img.p;
     unsigned long long ctr[kVisCtrN] = {0, 0, 0, 0};
-    if (n > 0) {
-        HIP_TRY(hipMemsetAsync(V.table, 0, (size_t)((char*)(V.ctr + kVisCtrN) - (char*)V.table), c->stream));
-        RC_TRY(launch_vis_score(V, c->stream));
-        RC_TRY(launch_vis_flags(V, c->stream));
-        if (out) {  // (the table bounds the result: the records are written before their count is known)
-            RC_TRY(ivox_scan(c, V.flag, d_slot, length));
-            RC_TRY(launch_vis_emit(V, c->stream));
-        }
-        HIP_TRY(hipMemcpyAsync(ctr, V.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
-    }
+    RC_TRY(select_queue(c, S, c->gray_img.p, out != nullptr));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(ctr, V.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (gray) {  // the upload is done: later calls may reuse it
         c->gray_img.w = width;
@@ -4704,14 +4759,7 @@ int livo_vio_select(livo_ctx* c, int32_t scan_id, const livo_state* state, const
     }
     const int64_t sel = (int64_t)ctr[kVisCtrOut];
     *n_out = sel;
-    if (stats) {
-        stats->n_in = n;
-        stats->in_frame = (int64_t)ctr[kVisCtrInFrame];
-        stats->behind_in_frame = (int64_t)ctr[kVisCtrBehind];
-        stats->cell_overflow = (int64_t)ctr[kVisCtrOverflow];
-        stats->n_out = sel;
-        stats->n_cells = length;
-    }
+    if (stats) select_stats(S, ctr, stats);
     if (out && cap < sel) return LIVO_E_CAPACITY;
     if (out && sel > 0) {
         HIP_TRY(hipMemcpyAsync(out, V.out, (size_t)sel * sizeof(livo_vis_point), hipMemcpyDeviceToHost, c->stream));
@@ -4751,14 +4799,50 @@ int livo_vmap_reset(livo_ctx* c, int64_t max_points, int64_t max_frames, int32_t
     m.n_obs = 0;
     m.count.clear();
     m.frames.clear();
+    m.free_slots.clear();
     m.ready = true;
     return LIVO_OK;
 }
 
 static int vmap_frame_slot(const VmapDev& m, int32_t frame_id) {
+    if (frame_id < 0) return -1;  // (a released slot holds id -1)
     for (size_t k = 0; k < m.frames.size(); k++)
         if (m.frames[k].id == frame_id) return (int)k;
     return -1;
+}
+
+// livo_vmap_add_frame's checks (cam = frame_cam(p, state): only its intrinsics are tested).
+static int frame_check(const VmapDev& m, const FrameCam& cam, int32_t width, int32_t height) {
+    if (cam.distortion) return LIVO_E_INVALID;
+    if (!m.frames.empty() && (width != m.w || height != m.h || cam.fx != m.K.fx || cam.fy != m.K.fy ||
+                              cam.cx != m.K.cx || cam.cy != m.K.cy))
+        return LIVO_E_INVALID;
+    return LIVO_OK;
+}
+// The slot the next frame takes (a released one before a fresh one) and, before the first
+// frame, the image store sized by it.  The caller has checked the capacity.
+static int frame_take_slot(livo_ctx* c, const FrameCam& cam, int32_t width, int32_t height, int* slot) {
+    VmapDev& m = c->vmap;
+    if (m.frames.empty()) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        RC_TRY(ensure_dev_bytes(&m.img, &m.img_bytes, (size_t)width * (size_t)height * (size_t)m.max_frames));
+        m.dev.img = (const uint8_t*)m.img;
+        m.w = width;
+        m.h = height;
+        m.K = cam;
+    }
+    *slot = m.free_slots.empty() ? (int)m.frames.size() : m.free_slots.back();
+    return LIVO_OK;
+}
+// The host's copy after the frame's image and VmFrame are in `slot`.
+static void frame_commit(VmapDev& m, int slot, const VmFrame& f) {
+    if (slot == (int)m.frames.size()) {
+        m.frames.push_back(f);
+    } else {
+        m.free_slots.pop_back();
+        m.frames[(size_t)slot] = f;
+    }
+    m.dev.n_frames = (int32_t)m.frames.size();
 }
 
 int livo_vmap_add_frame(livo_ctx* c, int32_t frame_id, const livo_state* state, const livo_vio_params* p,
@@ -4767,36 +4851,21 @@ int livo_vmap_add_frame(livo_ctx* c, int32_t frame_id, const livo_state* state, 
     VmapDev& m = c->vmap;
     if (!m.ready || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
     const FrameCam cam = frame_cam(*p, *state);
-    if (cam.distortion) return LIVO_E_INVALID;
-    if (!m.frames.empty() && (width != m.w || height != m.h || cam.fx != m.K.fx || cam.fy != m.K.fy ||
-                              cam.cx != m.K.cx || cam.cy != m.K.cy))
-        return LIVO_E_INVALID;
+    RC_TRY(frame_check(m, cam, width, height));
     if (!gray && !image_reusable(c->gray_img, width, height)) return LIVO_E_INVALID;
     if (vmap_frame_slot(m, frame_id) >= 0) return LIVO_E_INVALID;
-    if ((int64_t)m.frames.size() >= m.max_frames) return LIVO_E_CAPACITY;
+    if (m.live_frames() >= m.max_frames) return LIVO_E_CAPACITY;
     if (set_device(c)) return LIVO_E_HIP;
     const size_t bytes = (size_t)width * (size_t)height;
-    if (m.frames.empty()) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        RC_TRY(ensure_dev_bytes(&m.img, &m.img_bytes, bytes * (size_t)m.max_frames));
-        m.dev.img = (const uint8_t*)m.img;
-        m.w = width;
-        m.h = height;
-        m.K = cam;
-    }
-    VmFrame f{};
-    f.id = frame_id;
-    std::memcpy(f.Rcw, cam.Rcw, sizeof(f.Rcw));
-    std::memcpy(f.Pcw, cam.Pcw, sizeof(f.Pcw));
-    vm_frame_pos(f.Rcw, f.Pcw, f.pos);
-    const size_t slot = m.frames.size();
-    uint8_t* dst = (uint8_t*)m.img + slot * bytes;
+    int slot;
+    RC_TRY(frame_take_slot(c, cam, width, height, &slot));
+    const VmFrame f = vm_make_frame(frame_id, cam);
+    uint8_t* dst = (uint8_t*)m.img + (size_t)slot * bytes;
     HIP_TRY(hipMemcpyAsync(dst, gray ? gray : c->gray_img.p, bytes, gray ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                            c->stream));
     HIP_TRY(hipMemcpyAsync((VmFrame*)m.dev.frame + slot, &f, sizeof(f), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    m.frames.push_back(f);
-    m.dev.n_frames = (int32_t)m.frames.size();
+    frame_commit(m, slot, f);
     return LIVO_OK;
 }
 
@@ -4829,24 +4898,8 @@ int livo_vmap_add(livo_ctx* c, int32_t frame_id, int64_t n, const int32_t* point
     std::vector<VmObs> obs((size_t)n);
     std::vector<VmPoint> fresh(point_ids ? 0 : (size_t)n);
     for (int64_t i = 0; i < n; i++) {
-        VmObs& o = obs[(size_t)i];
-        o = VmObs{};
-        o.frame_id = frame_id;
-        o.level = point_ids && levels ? levels[i] : 0;
-        o.slot = slot;
-        o.px[0] = pts[i].u;
-        o.px[1] = pts[i].v;
-        vm_cam2world(m.K, o.px[0], o.px[1], o.f);
-        if (!point_ids) {
-            VmPoint& q = fresh[(size_t)i];
-            q = VmPoint{};
-            q.pos[0] = (double)pts[i].x;
-            q.pos[1] = (double)pts[i].y;
-            q.pos[2] = (double)pts[i].z;
-            q.value = pts[i].score;
-            q.n_obs = 1;
-            for (int k = 0; k < 3; k++) q.voxel[k] = pts[i].voxel[k];
-        }
+        obs[(size_t)i] = vm_make_obs(m.K, frame_id, slot, point_ids && levels ? levels[i] : 0, pts[i].u, pts[i].v);
+        if (!point_ids) fresh[(size_t)i] = vm_make_point(pts[i]);
     }
     if (set_device(c)) return LIVO_E_HIP;
     const int pst3 = 3 * m.ps * m.ps;
@@ -4897,7 +4950,7 @@ int livo_vmap_info(livo_ctx* c, livo_vmap_counts* info) {
     std::memset(info, 0, sizeof(*info));
     info->n_points = (int64_t)m.count.size();
     info->n_obs = m.n_obs;
-    info->n_frames = (int64_t)m.frames.size();
+    info->n_frames = m.live_frames();
     info->max_points = m.max_points;
     info->max_frames = m.max_frames;
     info->patch_size = m.ps;
@@ -4956,17 +5009,22 @@ int livo_vmap_dump(livo_ctx* c, livo_vmap_point* points, int64_t cap_points, liv
     return LIVO_OK;
 }
 
-int livo_vio_match(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
-                   int32_t grid_size, int32_t ncc_en, double ncc_thre, double outlier_threshold,
-                   const uint8_t* gray, int32_t width, int32_t height, livo_vmatch_point* out, double* pos,
-                   int32_t* search_levels, float* patches, int64_t cap, int64_t* n_out, livo_vmatch_stats* stats) {
-    if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
-    if (grid_size < 1 || p->patch_size < 2 || p->patch_size > 8 || p->patch_size % 2 || cap < 0) return LIVO_E_INVALID;
+// ---- livo_vio_match's body: the checks and the grid, the arrays, the launches, the statistics ----
+struct MatchStage {
+    VmatchParams V{};
+    int64_t length = 0, np = 0;
+    int pst3 = 0;
+    char* clear_end = nullptr;
+};
+// Everything of livo_vio_match that needs no device (image_ok: there is an image to read).
+static int match_prepare(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                         int32_t grid_size, int32_t ncc_en, double ncc_thre, double outlier_threshold, int32_t width,
+                         int32_t height, bool image_ok, MatchStage* M) {
+    if (grid_size < 1 || p->patch_size < 2 || p->patch_size > 8 || p->patch_size % 2) return LIVO_E_INVALID;
     if (width <= 0 || height <= 0 || width != p->cam.width || height != p->cam.height) return LIVO_E_INVALID;
-    if (out ? !(pos && search_levels && patches) : cap != 0) return LIVO_E_INVALID;
     VmapDev& m = c->vmap;
     if (!m.ready || p->patch_size != m.ps) return LIVO_E_INVALID;
-    VmatchParams V{};
+    VmatchParams& V = M->V;
     V.cam = frame_cam(*p, *state);  // once per call
     if (V.cam.distortion) return LIVO_E_INVALID;
     if (!m.frames.empty() && (width != m.w || height != m.h)) return LIVO_E_INVALID;
@@ -4979,64 +5037,103 @@ int livo_vio_match(livo_ctx* c, int32_t scan_id, const livo_state* state, const 
     const int64_t length = (int64_t)(width / grid_size) * V.grid.grid_n_height;
     if (length > (int64_t)0x7FFFFFFF - kVmBlock) return LIVO_E_RANGE;
     V.grid.length = (int32_t)length;
-    if (!gray && !image_reusable(c->match_img, width, height)) return LIVO_E_INVALID;
+    if (!image_ok) return LIVO_E_INVALID;
     RC_TRY(frame_cloud(c, scan_id, &V.cloud));  // in the caller's point order (iperm)
     const int64_t n = V.cloud.n;
     if (n > ((int64_t)1 << 30)) return LIVO_E_RANGE;
-    if (set_device(c)) return LIVO_E_HIP;
-    if (gray) RC_TRY(image_stage(c->match_img, gray, (size_t)width * (size_t)height, c->stream));
-    const int pst3 = 3 * p->patch_size * p->patch_size;
-    const int64_t np = (int64_t)m.count.size();
+    M->length = length;
+    M->np = (int64_t)m.count.size();
+    M->pst3 = 3 * p->patch_size * p->patch_size;
     int log2 = 6;  // two slots per cloud point at least: a probe always ends
     while (((int64_t)1 << log2) < 2 * n) log2++;
     V.vset_log2 = log2;
-    const size_t npix = (size_t)width * (size_t)height;
-    uint32_t* d_slot;
-    char* clear_end;
+    V.W = world_params(c, *state);
+    vm_frame_pos(V.cam.Rcw, V.cam.Pcw, V.fpos);
+    V.map = m.dev;
+    V.ncc_en = ncc_en ? 1 : 0;
+    V.ncc_thre = ncc_thre;
+    V.err_thre = outlier_threshold * (double)(p->patch_size * p->patch_size);
+    return LIVO_OK;
+}
+static void match_layout(MatchStage& M, Carve& k, int64_t max_frames) {
+    VmatchParams& V = M.V;
+    const size_t length = (size_t)M.length, npix = (size_t)V.cam.w * (size_t)V.cam.h;
+    // cleared to 0xFF: the set, the bids, the warp owners
+    V.vset = k.take<unsigned long long>((size_t)1 << V.vset_log2);
+    V.bid = k.take<unsigned long long>(length);
+    V.owner = k.take<uint32_t>((size_t)max_frames);
+    M.clear_end = (char*)k.take<char>(0);
+    // cleared to 0: the depth image, the counters
+    V.depth = k.take<uint32_t>(npix);
+    V.ctr = k.take<unsigned long long>(kVmCtrN);
+    V.cand = k.take<int32_t>(length);
+    V.keep = k.take<uint32_t>(length);
+    V.slot = k.take<uint32_t>(length);
+    V.rec = k.take<livo_vmatch_point>(length);
+    V.cpatch = k.take<float>(length * M.pst3);
+    V.out = k.take<livo_vmatch_point>(length);
+    V.pos = k.take<double>(length * 3);
+    V.levels = k.take<int32_t>(length);
+    V.patches = k.take<float>(length * M.pst3);
+}
+// Queues the match of img on c->stream; store: the warped patches into the map and the
+// survivors' arrays (V.ctr holds the counts).  Nothing runs on an empty map (:334).
+static int match_queue(livo_ctx* c, MatchStage& M, const uint8_t* img, bool store) {
+    VmatchParams& V = M.V;
+    V.img = img;
+    V.store = store ? 1 : 0;
+    if (M.np <= 0) return LIVO_OK;
+    HIP_TRY(hipMemsetAsync(V.vset, 0xFF, (size_t)(M.clear_end - (char*)V.vset), c->stream));
+    HIP_TRY(hipMemsetAsync(V.depth, 0, (size_t)((char*)(V.ctr + kVmCtrN) - (char*)V.depth), c->stream));
+    RC_TRY(launch_vm_cloud(V, c->stream));
+    RC_TRY(launch_vm_map(V, c->stream));
+    RC_TRY(launch_vm_cell(V, c->stream));
+    RC_TRY(launch_vm_warp(V, c->stream));
+    if (store) {  // (the cells bound the result: the survivors are written before their count is known)
+        RC_TRY(ivox_scan(c, V.keep, const_cast<uint32_t*>(V.slot), M.length));
+        RC_TRY(launch_vm_scatter(V, c->stream));
+    }
+    return LIVO_OK;
+}
+static void match_stats(const MatchStage& M, const unsigned long long* ctr, livo_vmatch_stats* stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->n_in = M.V.cloud.n;
+    stats->n_voxels = (int64_t)ctr[kVmCtrVoxels];
+    stats->map_tested = (int64_t)ctr[kVmCtrTested];
+    stats->in_frame = (int64_t)ctr[kVmCtrInFrame];
+    stats->cell_overflow = (int64_t)ctr[kVmCtrOverflow];
+    stats->cells_marked = (int64_t)ctr[kVmCtrMarked];
+    stats->depth_rejected = (int64_t)ctr[kVmCtrDepth];
+    stats->view_rejected = (int64_t)ctr[kVmCtrView];
+    stats->ncc_rejected = (int64_t)ctr[kVmCtrNcc];
+    stats->error_rejected = (int64_t)ctr[kVmCtrError];
+    stats->warp_shared = (int64_t)ctr[kVmCtrShared];
+    stats->warp_nan = (int64_t)ctr[kVmCtrNan];
+    stats->n_out = (int64_t)ctr[kVmCtrOut];
+}
+
+int livo_vio_match(livo_ctx* c, int32_t scan_id, const livo_state* state, const livo_vio_params* p,
+                   int32_t grid_size, int32_t ncc_en, double ncc_thre, double outlier_threshold,
+                   const uint8_t* gray, int32_t width, int32_t height, livo_vmatch_point* out, double* pos,
+                   int32_t* search_levels, float* patches, int64_t cap, int64_t* n_out, livo_vmatch_stats* stats) {
+    if (!c || !state || !p || !n_out) return LIVO_E_INVALID;
+    if (cap < 0 || (out ? !(pos && search_levels && patches) : cap != 0)) return LIVO_E_INVALID;
+    MatchStage M;
+    RC_TRY(match_prepare(c, scan_id, state, p, grid_size, ncc_en, ncc_thre, outlier_threshold, width, height,
+                         gray || image_reusable(c->match_img, width, height), &M));
+    VmatchParams& V = M.V;
+    if (set_device(c)) return LIVO_E_HIP;
+    if (gray) RC_TRY(image_stage(c->match_img, gray, (size_t)width * (size_t)height, c->stream));
+    const int pst3 = M.pst3;
     auto layout = [&](Carve k) {
-        // cleared to 0xFF: the set, the bids, the warp owners
-        V.vset = k.take<unsigned long long>((size_t)1 << log2);
-        V.bid = k.take<unsigned long long>((size_t)length);
-        V.owner = k.take<uint32_t>((size_t)m.max_frames);
-        clear_end = (char*)k.take<char>(0);
-        // cleared to 0: the depth image, the counters
-        V.depth = k.take<uint32_t>(npix);
-        V.ctr = k.take<unsigned long long>(kVmCtrN);
-        V.cand = k.take<int32_t>((size_t)length);
-        V.keep = k.take<uint32_t>((size_t)length);
-        V.slot = d_slot = k.take<uint32_t>((size_t)length);
-        V.rec = k.take<livo_vmatch_point>((size_t)length);
-        V.cpatch = k.take<float>((size_t)length * pst3);
-        V.out = k.take<livo_vmatch_point>((size_t)length);
-        V.pos = k.take<double>((size_t)length * 3);
-        V.levels = k.take<int32_t>((size_t)length);
-        V.patches = k.take<float>((size_t)length * pst3);
+        match_layout(M, k, c->vmap.max_frames);
         return k.total();
     };
     RC_TRY(ensure_dev_bytes(&c->vm_buf, &c->vm_bytes, layout(Carve{nullptr})));
     layout(Carve{(char*)c->vm_buf});
-    V.W = world_params(c, *state);
-    vm_frame_pos(V.cam.Rcw, V.cam.Pcw, V.fpos);
-    V.map = m.dev;
-    V.img = c->match_img.p;
-    V.ncc_en = ncc_en ? 1 : 0;
-    V.store = out ? 1 : 0;
-    V.ncc_thre = ncc_thre;
-    V.err_thre = outlier_threshold * (double)(p->patch_size * p->patch_size);
     unsigned long long ctr[kVmCtrN] = {};
-    if (np > 0) {  // (:334: an empty map returns at once)
-        HIP_TRY(hipMemsetAsync(V.vset, 0xFF, (size_t)(clear_end - (char*)V.vset), c->stream));
-        HIP_TRY(hipMemsetAsync(V.depth, 0, (size_t)((char*)(V.ctr + kVmCtrN) - (char*)V.depth), c->stream));
-        RC_TRY(launch_vm_cloud(V, c->stream));
-        RC_TRY(launch_vm_map(V, c->stream));
-        RC_TRY(launch_vm_cell(V, c->stream));
-        RC_TRY(launch_vm_warp(V, c->stream));
-        if (out) {  // (the cells bound the result: the survivors are written before their count is known)
-            RC_TRY(ivox_scan(c, V.keep, d_slot, length));
-            RC_TRY(launch_vm_scatter(V, c->stream));
-        }
-        HIP_TRY(hipMemcpyAsync(ctr, V.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
-    }
+    RC_TRY(match_queue(c, M, c->match_img.p, out != nullptr));
+    if (M.np > 0) HIP_TRY(hipMemcpyAsync(ctr, V.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (gray) {  // the upload is done: later calls may reuse it
         c->match_img.w = width;
@@ -5044,22 +5141,7 @@ int livo_vio_match(livo_ctx* c, int32_t scan_id, const livo_state* state, const 
     }
     const int64_t sel = (int64_t)ctr[kVmCtrOut];
     *n_out = sel;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_in = n;
-        stats->n_voxels = (int64_t)ctr[kVmCtrVoxels];
-        stats->map_tested = (int64_t)ctr[kVmCtrTested];
-        stats->in_frame = (int64_t)ctr[kVmCtrInFrame];
-        stats->cell_overflow = (int64_t)ctr[kVmCtrOverflow];
-        stats->cells_marked = (int64_t)ctr[kVmCtrMarked];
-        stats->depth_rejected = (int64_t)ctr[kVmCtrDepth];
-        stats->view_rejected = (int64_t)ctr[kVmCtrView];
-        stats->ncc_rejected = (int64_t)ctr[kVmCtrNcc];
-        stats->error_rejected = (int64_t)ctr[kVmCtrError];
-        stats->warp_shared = (int64_t)ctr[kVmCtrShared];
-        stats->warp_nan = (int64_t)ctr[kVmCtrNan];
-        stats->n_out = sel;
-    }
+    if (stats) match_stats(M, ctr, stats);
     if (out && cap < sel) return LIVO_E_CAPACITY;
     if (out && sel > 0) {
         HIP_TRY(hipMemcpyAsync(out, V.out, (size_t)sel * sizeof(livo_vmatch_point), hipMemcpyDeviceToHost, c->stream));
@@ -5069,6 +5151,40 @@ int livo_vio_match(livo_ctx* c, int32_t scan_id, const livo_state* state, const 
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return LIVO_OK;
+}
+
+// ---- livo_vio_observe's body: the parameter block, the host's counts, the statistics ----
+// (the frame's pose, the ids and levels, rec and ctr are the caller's)
+static VmObserveParams observe_params(const VmapDev& m, int slot, int32_t frame_id, int64_t n) {
+    VmObserveParams P{};
+    static_cast<CamIntrinsics&>(P.cam) = m.K;
+    P.map = m.dev;
+    P.n = (int32_t)n;
+    P.ps = m.ps;
+    P.border = (m.ps / 2 + 1) * 8;
+    P.slot = slot;
+    P.frame_id = frame_id;
+    return P;
+}
+// The device decided the counts: the host's copy follows.
+static void observe_follow(VmapDev& m, const livo_vobs_point* rec, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        int32_t& cnt = m.count[(size_t)rec[i].point_id];
+        m.n_obs += (int64_t)rec[i].n_obs - cnt;
+        cnt = rec[i].n_obs;
+    }
+}
+static void observe_stats(const VmapDev& m, const unsigned long long* ctr, int64_t n, livo_vobs_stats* stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->n_in = n;
+    stats->behind = (int64_t)ctr[kVoCtrBehind];
+    stats->out_of_frame = (int64_t)ctr[kVoCtrOutOfFrame];
+    stats->pose_flagged = (int64_t)ctr[kVoCtrPose];
+    stats->pixel_flagged = (int64_t)ctr[kVoCtrPixel];
+    stats->added = (int64_t)ctr[kVoCtrAdded];
+    stats->deleted = (int64_t)ctr[kVoCtrDeleted];
+    stats->deleted_without_add = (int64_t)ctr[kVoCtrBare];
+    stats->n_obs_total = m.n_obs;
 }
 
 int livo_vio_observe(livo_ctx* c, int32_t frame_id, int64_t n, const int32_t* point_ids, const int32_t* search_levels,
@@ -5095,18 +5211,11 @@ int livo_vio_observe(livo_ctx* c, int32_t frame_id, int64_t n, const int32_t* po
     unsigned long long ctr[kVoCtrN] = {};
     if (n > 0) {
         if (set_device(c)) return LIVO_E_HIP;
-        VmObserveParams P{};
-        static_cast<CamIntrinsics&>(P.cam) = m.K;
+        VmObserveParams P = observe_params(m, slot, frame_id, n);
         const VmFrame& f = m.frames[(size_t)slot];
         std::memcpy(P.cam.Rcw, f.Rcw, sizeof(f.Rcw));
         std::memcpy(P.cam.Pcw, f.Pcw, sizeof(f.Pcw));
         std::memcpy(P.cpos, f.pos, sizeof(f.pos));
-        P.map = m.dev;
-        P.n = (int32_t)n;
-        P.ps = m.ps;
-        P.border = (m.ps / 2 + 1) * 8;
-        P.slot = slot;
-        P.frame_id = frame_id;
         int32_t *d_point, *d_level;
         auto layout = [&](Carve k) {
             P.ctr = k.take<unsigned long long>(kVoCtrN);
@@ -5125,25 +5234,170 @@ int livo_vio_observe(livo_ctx* c, int32_t frame_id, int64_t n, const int32_t* po
         HIP_TRY(hipMemcpyAsync(rec.data(), P.rec, (size_t)n * sizeof(livo_vobs_point), hipMemcpyDeviceToHost,
                                c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (const livo_vobs_point& r : rec) {  // the device decided the counts: the host's copy follows
-            int32_t& cnt = m.count[(size_t)r.point_id];
-            m.n_obs += (int64_t)r.n_obs - cnt;
-            cnt = r.n_obs;
-        }
+        observe_follow(m, rec.data(), n);
         if (out) std::memcpy(out, rec.data(), (size_t)n * sizeof(livo_vobs_point));
     }
+    if (stats) observe_stats(m, ctr, n, stats);
+    return LIVO_OK;
+}
+
+// LidarSelector::detect (src/lidar_selection.cpp:1024-1073) behind the image conversion: the
+// stage bodies above in the order match, select, update, frame, observe, new points, over one
+// carve of c->det_buf and one uploaded image.  What the host reads: the counters behind the
+// select (the survivor and selected counts size the later launches), and at the end the
+// update's slot, the observe's counters and records and the stored VmFrame.
+int livo_vio_detect(livo_ctx* c, int32_t scan_id, int32_t frame_id, livo_state* state, const livo_state* prior,
+                    const livo_vio_params* p, const livo_vdetect_params* d, const uint8_t* gray, int32_t width,
+                    int32_t height, livo_vdetect_stats* stats) {
+    if (!c || !state || !p || !d || !gray || frame_id < 0) return LIVO_E_INVALID;
+    if (p->max_iterations < 0 || !(p->img_point_cov > 0.0)) return LIVO_E_INVALID;  // (livo_vio_update's)
+    VmapDev& m = c->vmap;
+    MatchStage M;
+    SelectStage S;
+    RC_TRY(match_prepare(c, scan_id, state, p, d->grid_size, d->ncc_en, d->ncc_thre, d->outlier_threshold, width,
+                         height, true, &M));
+    RC_TRY(select_prepare(c, scan_id, state, p, d->grid_size, width, height, true, &S));
+    RC_TRY(frame_check(m, M.V.cam, width, height));
+    if (vmap_frame_slot(m, frame_id) >= 0) return LIVO_E_INVALID;
+    if (m.live_frames() >= m.max_frames) return LIVO_E_CAPACITY;
+    if (M.length > (int64_t)0x7FFFFFFF - 256) return LIVO_E_RANGE;  // (the update's block count)
+    if (set_device(c)) return LIVO_E_HIP;
+    const size_t bytes = (size_t)width * (size_t)height;
+    int slot;
+    RC_TRY(frame_take_slot(c, M.V.cam, width, height, &slot));
+    RC_TRY(image_stage(c->det_img, gray, bytes, c->stream));
+    const int pst3 = M.pst3;
+    const size_t cells = (size_t)M.length;  // bounds the survivors and, as S.length, the selected
+    VioParams U = update_params(p, width, height);
+    VmObserveParams O = observe_params(m, slot, frame_id, 0);
+    auto layout = [&](Carve k) {
+        match_layout(M, k, m.max_frames);
+        select_layout(S, k);
+        U.partial = k.take<double>((cells + 255) / 256 * kVioCols + kVioCols);
+        U.perr = k.take<float>(cells);
+        U.slot = k.take<VioSlot>(1);
+        O.ctr = k.take<unsigned long long>(kVoCtrN);
+        O.rec = k.take<livo_vobs_point>(cells);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&c->det_buf, &c->det_bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)c->det_buf});
+    VioSlot hs;
+    std::memset(&hs, 0, sizeof(hs));
+    hs.state = *state;
+    hs.prior = prior ? *prior : *state;
+    HIP_TRY(hipMemcpyAsync(U.slot, &hs, sizeof(hs), hipMemcpyHostToDevice, c->stream));
+    // 1, 2: the match and the select at the state given, on the one image
+    RC_TRY(match_queue(c, M, c->det_img.p, true));
+    RC_TRY(select_queue(c, S, c->det_img.p, true));
+    unsigned long long mctr[kVmCtrN] = {}, sctr[kVisCtrN] = {}, octr[kVoCtrN] = {};
+    if (M.np > 0) HIP_TRY(hipMemcpyAsync(mctr, M.V.ctr, sizeof(mctr), hipMemcpyDeviceToHost, c->stream));
+    if (S.V.cloud.n > 0) HIP_TRY(hipMemcpyAsync(sctr, S.V.ctr, sizeof(sctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int64_t n_s = (int64_t)mctr[kVmCtrOut], n_new = (int64_t)sctr[kVisCtrOut], np0 = M.np;
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
-        stats->n_in = n;
-        stats->behind = (int64_t)ctr[kVoCtrBehind];
-        stats->out_of_frame = (int64_t)ctr[kVoCtrOutOfFrame];
-        stats->pose_flagged = (int64_t)ctr[kVoCtrPose];
-        stats->pixel_flagged = (int64_t)ctr[kVoCtrPixel];
-        stats->added = (int64_t)ctr[kVoCtrAdded];
-        stats->deleted = (int64_t)ctr[kVoCtrDeleted];
-        stats->deleted_without_add = (int64_t)ctr[kVoCtrBare];
-        stats->n_obs_total = m.n_obs;
+        match_stats(M, mctr, &stats->match);
+        select_stats(S, sctr, &stats->select);
+        stats->n_matched = n_s;
+        stats->n_new = n_new;
+        stats->first_new_id = n_new > 0 ? (int32_t)np0 : -1;
     }
+    if (np0 + n_new > m.max_points) {  // (livo_vmap_add's; the match has rewarped)
+        if (m.frames.empty()) m.w = m.h = 0;  // no first frame after all
+        return LIVO_E_CAPACITY;
+    }
+    // 3: the update on the survivors where the scatter left them
+    U.img = c->det_img.p;
+    U.n = (int32_t)n_s;
+    U.pos = M.V.pos;
+    U.levels = M.V.levels;
+    U.patches = M.V.patches;
+    U.nblk = (int)std::max<int64_t>(1, (n_s + 255) / 256);
+    RC_TRY(update_queue(c, U));
+    // 4: the frame of the updated state (the state given if nothing matched: the update leaves it)
+    VmFrame* d_frame = (VmFrame*)m.dev.frame + slot;
+    VmFrameParams F{};
+    F.dst = d_frame;
+    F.state = &U.slot->state;
+    F.vio = *p;
+    F.frame_id = frame_id;
+    RC_TRY(launch_vm_frame(F, c->stream));
+    HIP_TRY(hipMemcpyAsync((uint8_t*)m.img + (size_t)slot * bytes, c->det_img.p, bytes, hipMemcpyDeviceToDevice,
+                           c->stream));
+    // 5: the observe on the match's records (one point per cell, ids from the map: no id twice)
+    std::vector<livo_vobs_point> rec((size_t)n_s);
+    if (n_s > 0) {
+        O.n = (int32_t)n_s;
+        O.match = M.V.out;
+        HIP_TRY(hipMemsetAsync(O.ctr, 0, sizeof(octr), c->stream));
+        RC_TRY(launch_vm_observe_resident(O, c->stream));
+        HIP_TRY(hipMemcpyAsync(octr, O.ctr, sizeof(octr), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(rec.data(), O.rec, (size_t)n_s * sizeof(livo_vobs_point), hipMemcpyDeviceToHost,
+                               c->stream));
+    }
+    // 6: the selected points, behind the observe: their ids are beyond those it was given
+    if (n_new > 0) {
+        VmFreshParams N{};
+        N.map = m.dev;
+        N.K = m.K;
+        N.n = (int32_t)n_new;
+        N.pst3 = pst3;
+        N.frame_id = frame_id;
+        N.slot = slot;
+        N.base = (int32_t)np0;
+        N.pts = S.V.out;
+        N.patches = S.V.patches;
+        RC_TRY(launch_vm_fresh(N, c->stream));
+    }
+    VmFrame f;
+    HIP_TRY(hipMemcpyAsync(&hs, U.slot, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&f, d_frame, sizeof(f), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n_s > 0) *state = hs.state;
+    frame_commit(m, slot, f);
+    observe_follow(m, rec.data(), n_s);
+    if (stats) {
+        update_stats(hs, &stats->update);
+        observe_stats(m, octr, n_s, &stats->observe);
+    }
+    m.count.resize((size_t)(np0 + n_new), 1);
+    m.n_obs += n_new;
+    m.dev.n_points = (int32_t)m.count.size();
+    return LIVO_OK;
+}
+
+// The frames no observation names are released: their slots go to the next frames stored.
+int livo_vmap_release_frames(livo_ctx* c, int32_t* released, int64_t cap, int64_t* n_out) {
+    if (!c || !n_out || cap < 0 || (!released && cap != 0)) return LIVO_E_INVALID;
+    VmapDev& m = c->vmap;
+    if (!m.ready) return LIVO_E_INVALID;
+    *n_out = 0;
+    const size_t n_slots = m.frames.size();
+    if (n_slots == 0) return LIVO_OK;
+    if (n_slots > (size_t)65535 * kVmRefTile) return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    RC_TRY(ensure_scratch(c, n_slots * sizeof(uint32_t)));
+    uint32_t* d_refs = (uint32_t*)c->scratch;
+    std::vector<uint32_t> refs(n_slots);
+    HIP_TRY(hipMemsetAsync(d_refs, 0, n_slots * sizeof(uint32_t), c->stream));
+    RC_TRY(launch_vm_frame_refs(m.dev, (int32_t)n_slots, d_refs, c->stream));
+    HIP_TRY(hipMemcpyAsync(refs.data(), d_refs, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<std::pair<int32_t, int32_t>> idle;  // (frame id, slot)
+    for (size_t k = 0; k < n_slots; k++)
+        if (m.frames[k].id >= 0 && refs[k] == 0u) idle.emplace_back(m.frames[k].id, (int32_t)k);
+    std::sort(idle.begin(), idle.end());
+    *n_out = (int64_t)idle.size();
+    if (!released) return LIVO_OK;  // the sizing form
+    if (cap < (int64_t)idle.size()) return LIVO_E_CAPACITY;
+    for (size_t i = 0; i < idle.size(); i++) {
+        released[i] = idle[i].first;
+        m.frames[(size_t)idle[i].second].id = -1;
+        m.free_slots.push_back(idle[i].second);
+    }
+    std::sort(m.free_slots.begin(), m.free_slots.end(), std::greater<int32_t>());
     return LIVO_OK;
 }
 

@@ -743,8 +743,38 @@ struct VmObserveParams {
     const int32_t* level;     // n search levels
     livo_vobs_point* rec;     // n records, input order
     unsigned long long* ctr;  // kVoCtrN counters, zeroed by the caller
+    const livo_vmatch_point* match;  // launch_vm_observe_resident: n survivors of the match (point_id, search_level)
 };
 int launch_vm_observe(const VmObserveParams& p, void* stream);
+// The same kernel inside livo_vio_detect: the frame's Rcw, Pcw and position are
+// read from map.frame[slot] (written by launch_vm_frame on this stream), the ids
+// and levels from the match's records; cam's pose, cpos, point and level are unused.
+int launch_vm_observe_resident(const VmObserveParams& p, void* stream);
+// livo_vio_detect: the frame of the updated state, map.frame[slot] = vm_make_frame(frame_id,
+// frame_cam(vio, *state)) with *state on the device (VioSlot::state).  One thread.
+struct VmFrameParams {
+    VmFrame* dst;
+    const livo_state* state;
+    livo_vio_params vio;
+    int32_t frame_id, pad_;
+};
+int launch_vm_frame(const VmFrameParams& p, void* stream);
+// livo_vio_detect: n selected records become the points base .. base + n - 1, each with its
+// one observation from the frame in `slot` and its patch pyramid; one wave per point.
+struct VmFreshParams {
+    VmStore map;
+    CamIntrinsics K;
+    int32_t n, pst3;
+    int32_t frame_id, slot;
+    int32_t base, pad_;
+    const livo_vis_point* pts;  // n
+    const float* patches;       // n x pst3
+};
+int launch_vm_fresh(const VmFreshParams& p, void* stream);
+// livo_vmap_release_frames: refs[s] += observations of the map's points that name slot s
+// (n_slots counters, zeroed by the caller).
+constexpr int kVmRefTile = 4096;  // slots counted in LDS by one block
+int launch_vm_frame_refs(const VmStore& map, int32_t n_slots, uint32_t* refs, void* stream);
 // laserCloudOri / corr_normvect compaction in the caller's order (stored-order sel / normvec / points).
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream);
 int launch_ori_scatter(const float* pts4, const float* normvec, const uint8_t* sel, const int32_t* perm,

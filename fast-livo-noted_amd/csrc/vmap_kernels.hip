@@ -28,6 +28,12 @@
 //   k_vm_observe  livo_vio_observe (addObservation, :905-962): one wave per
 //                 matched point; the add decision, the eviction at 20
 //                 observations and the new observation, in the map.
+//   k_vm_frame    livo_vio_detect: the stored frame of the updated state, from
+//                 the update's slot on the device (one thread).
+//   k_vm_fresh    livo_vio_detect: one wave per selected record: the new
+//                 point, its observation and its patch pyramid.
+//   k_vm_frame_refs  livo_vmap_release_frames: observations per frame slot,
+//                 counted in LDS, one add per slot and block.
 // No position is decided by an atomic: two calls give the same bytes.
 // Numerics as livo_kernels.hip: -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -305,6 +311,10 @@ __device__ __forceinline__ void vm_shift_down(vm_word* p, int total, int s, int 
 // (vm_furthest_view) read from there; the 3 ps^2 samples of the new patch
 // pyramid spread over the lanes; the eviction's compaction by the whole wave.
 // Everything the item reads of its point is read before the first write.
+// kResident (livo_vio_detect): the frame's pose comes from its stored VmFrame,
+// which k_vm_frame wrote from the updated state, and the ids and levels from the
+// match's records: nothing of either has been on the host.
+template <bool kResident>
 __global__ __launch_bounds__(kVmBlock) void k_vm_observe(VmObserveParams P) {
     static_assert(sizeof(VmObs) % 4 == 0 && sizeof(livo_vobs_point) == 56, "whole words; a 56-B record");
     constexpr int kObsWords = (int)(sizeof(VmObs) / 4);
@@ -316,8 +326,16 @@ __global__ __launch_bounds__(kVmBlock) void k_vm_observe(VmObserveParams P) {
     int id = 0, n_obs = 0, fate = kVmObsBehind;
     double pc[2] = {0.0, 0.0}, delta_p = 0.0, pixel_dist = 0.0;
     VmObs* obs = nullptr;
+    if (kResident) {
+        const VmFrame& f = P.map.frame[P.slot];
+        for (int k = 0; k < 9; k++) P.cam.Rcw[k] = f.Rcw[k];
+        for (int k = 0; k < 3; k++) {
+            P.cam.Pcw[k] = f.Pcw[k];
+            P.cpos[k] = f.pos[k];
+        }
+    }
     if (live) {
-        id = P.point[i];
+        id = kResident ? P.match[i].point_id : P.point[i];
         const VmPoint& pt = P.map.pt[id];
         n_obs = pt.n_obs;  // (1 .. kVmMaxObs: the host keeps the counts)
         obs = P.map.obs + (size_t)id * kVmMaxObs;
@@ -369,7 +387,7 @@ __global__ __launch_bounds__(kVmBlock) void k_vm_observe(VmObserveParams P) {
             if (lane == 0) {
                 VmObs o{};
                 o.frame_id = P.frame_id;
-                o.level = P.level[i];
+                o.level = kResident ? P.match[i].search_level : P.level[i];
                 o.slot = P.slot;
                 o.px[0] = pc[0];
                 o.px[1] = pc[1];
@@ -405,6 +423,56 @@ __global__ __launch_bounds__(kVmBlock) void k_vm_observe(VmObserveParams P) {
     if (threadIdx.x < 7 && v) atomicAdd(P.ctr + threadIdx.x, (unsigned long long)v);
 }
 
+// livo_vio_detect: the stored frame of the state the update left in its slot.
+__global__ __launch_bounds__(64) void k_vm_frame(VmFrameParams P) {
+    if (threadIdx.x != 0) return;
+    *P.dst = vm_make_frame(P.frame_id, frame_cam(P.vio, *P.state));
+}
+
+// livo_vio_detect: one wave per selected record: lane 0 writes the point and its
+// observation 0 (vm_make_point, vm_make_obs), the wave copies the patch pyramid.
+__global__ __launch_bounds__(kVmBlock) void k_vm_fresh(VmFreshParams P) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kVmWaves + (threadIdx.x >> 6);
+    if (i >= P.n) return;
+    const int id = P.base + i;  // (< max_points: checked by the host)
+    const size_t at = (size_t)id * kVmMaxObs;
+    if (lane == 0) {
+        const livo_vis_point r = P.pts[i];
+        P.map.pt[id] = vm_make_point(r);
+        P.map.obs[at] = vm_make_obs(P.K, P.frame_id, P.slot, 0, r.u, r.v);
+    }
+    const float* src = P.patches + (size_t)i * P.pst3;
+    float* dst = P.map.patch + at * P.pst3;
+    for (int e = lane; e < P.pst3; e += 64) dst[e] = src[e];
+}
+
+// livo_vmap_release_frames: the observations that name each frame slot.  Block
+// (x, y) counts kVmRefPer observation places a thread, those of slots
+// [y * kVmRefTile, (y + 1) * kVmRefTile), in LDS; then one add per slot it met.
+constexpr int kVmRefPer = 8;
+__global__ __launch_bounds__(kVmBlock) void k_vm_frame_refs(VmStore map, int32_t n_slots, uint32_t* refs) {
+    __shared__ uint32_t s_cnt[kVmRefTile];
+    for (int t = threadIdx.x; t < kVmRefTile; t += kVmBlock) s_cnt[t] = 0u;
+    __syncthreads();
+    const int lo = (int)blockIdx.y * kVmRefTile;
+    const int64_t items = (int64_t)map.n_points * kVmMaxObs;
+    const int64_t first = (int64_t)blockIdx.x * (kVmBlock * kVmRefPer) + threadIdx.x;
+    for (int q = 0; q < kVmRefPer; q++) {
+        const int64_t e = first + (int64_t)q * kVmBlock;
+        if (e >= items) break;
+        const int64_t point = e / kVmMaxObs;
+        if ((int)(e - point * kVmMaxObs) >= map.pt[point].n_obs) continue;
+        const int s = map.obs[e].slot - lo;
+        if (s >= 0 && s < kVmRefTile && s + lo < n_slots) atomicAdd(&s_cnt[s], 1u);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < kVmRefTile; t += kVmBlock) {
+        const uint32_t v = s_cnt[t];
+        if (v) atomicAdd(refs + lo + t, v);  // (lo + t < n_slots: counted above)
+    }
+}
+
 static inline unsigned vm_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 #define VM_LAUNCH(kernel, count, per)                                                                        \
@@ -420,6 +488,23 @@ int launch_vm_scatter(const VmatchParams& p, void* stream) {
     VM_LAUNCH(k_vm_scatter, (int64_t)p.grid.length, kVmWaves);
 }
 int launch_vm_put(const VmPutParams& p, void* stream) { VM_LAUNCH(k_vm_put, (int64_t)p.n, kVmWaves); }
-int launch_vm_observe(const VmObserveParams& p, void* stream) { VM_LAUNCH(k_vm_observe, (int64_t)p.n, kVmWaves); }
+int launch_vm_observe(const VmObserveParams& p, void* stream) {
+    VM_LAUNCH(k_vm_observe<false>, (int64_t)p.n, kVmWaves);
+}
+int launch_vm_observe_resident(const VmObserveParams& p, void* stream) {
+    VM_LAUNCH(k_vm_observe<true>, (int64_t)p.n, kVmWaves);
+}
+int launch_vm_frame(const VmFrameParams& p, void* stream) {
+    hipLaunchKernelGGL(k_vm_frame, dim3(1), dim3(64), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
+}
+int launch_vm_fresh(const VmFreshParams& p, void* stream) { VM_LAUNCH(k_vm_fresh, (int64_t)p.n, kVmWaves); }
+int launch_vm_frame_refs(const VmStore& map, int32_t n_slots, uint32_t* refs, void* stream) {
+    const int64_t items = (int64_t)map.n_points * kVmMaxObs;  // (below 2^31: livo_vmap_reset)
+    if (items <= 0 || n_slots <= 0) return LIVO_OK;
+    const dim3 grid(vm_blocks(items, kVmBlock * kVmRefPer), vm_blocks(n_slots, kVmRefTile));
+    hipLaunchKernelGGL(k_vm_frame_refs, grid, dim3(kVmBlock), 0, (hipStream_t)stream, map, n_slots, refs);
+    return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
+}
 
 }  // namespace livo

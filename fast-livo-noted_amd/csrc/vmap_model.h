@@ -14,6 +14,10 @@
 // distance and the observation to evict.  The reference's `delta_theta > 10`
 // compares an acos (at most pi; NaN compares false) with 10: it never holds and
 // is not computed.  tests/native/vobserve_point_check.cpp runs these on the CPU.
+// vm_make_frame, vm_make_obs and vm_make_point build what the store holds of a
+// frame, an observation and a new point: the host path (livo_vmap_add_frame,
+// livo_vmap_add) and livo_vio_detect's kernels (k_vm_frame, k_vm_fresh) call the
+// same functions; tests/native/vdetect_point_check.cpp runs them on the CPU.
 #pragma once
 #include "cam_model.h"
 
@@ -56,6 +60,41 @@ SEL_HD void vm_cam2world(const CamIntrinsics& K, double u, double v, double* f) 
     f[0] = x / n;
     f[1] = y / n;
     f[2] = 1.0 / n;
+}
+
+// The frame stored under `id` at camera C: its Rcw, Pcw and position.
+SEL_HD VmFrame vm_make_frame(int32_t id, const FrameCam& C) {
+    VmFrame f{};
+    f.id = id;
+    for (int k = 0; k < 9; k++) f.Rcw[k] = C.Rcw[k];
+    for (int k = 0; k < 3; k++) f.Pcw[k] = C.Pcw[k];
+    vm_frame_pos(f.Rcw, f.Pcw, f.pos);
+    return f;
+}
+
+// The observation of pixel (u, v) from the frame stored in `slot` (Feature).
+SEL_HD VmObs vm_make_obs(const CamIntrinsics& K, int32_t frame_id, int32_t slot, int32_t level, double u, double v) {
+    VmObs o{};
+    o.frame_id = frame_id;
+    o.level = level;
+    o.slot = slot;
+    o.px[0] = u;
+    o.px[1] = v;
+    vm_cam2world(K, u, v, o.f);
+    return o;
+}
+
+// A new map point from a selected record (addSparseMap's tail): the float
+// position widened, value = score, the voxel key copied, one observation.
+SEL_HD VmPoint vm_make_point(const livo_vis_point& r) {
+    VmPoint q{};
+    q.pos[0] = (double)r.x;
+    q.pos[1] = (double)r.y;
+    q.pos[2] = (double)r.z;
+    q.value = r.score;
+    q.n_obs = 1;
+    for (int k = 0; k < 3; k++) q.voxel[k] = r.voxel[k];
+    return q;
 }
 
 // isInFrame(px.cast<int>(), border) taken in double (a NaN fails it), as vis_project.

@@ -292,6 +292,39 @@ public:
         return st;
     }
 
+    // lidar_selector->detect(img, pg) (lidar_selection.cpp:1024-1073) behind its image
+    // conversion, as one call on the resident visual map: addFromSparseMap and addSparseMap at
+    // `state`, ComputeJ on the matches (state_propagat the prior; `state` is updated in place),
+    // the frame stored under frame_id at the updated state with img, addObservation of the
+    // matches and the new points added, pg and img as addSparseMap takes them (img is
+    // required).  Nothing of the stages' results comes to the host; the statistics do.
+    livo_vdetect_stats detect(const livo_vio_params& vio, const uint8_t* img, int32_t width, int32_t height,
+                              int32_t frame_id, int32_t grid_size, bool ncc_en, double ncc_thre,
+                              double outlier_threshold, bool dense_map_en = true) {
+        if (!dense_map_en && scan_id_ < 0) throw Error("detect", LIVO_E_NOSCAN);
+        livo_vdetect_params d{};
+        d.grid_size = grid_size;
+        d.ncc_en = ncc_en ? 1 : 0;
+        d.ncc_thre = ncc_thre;
+        d.outlier_threshold = outlier_threshold;
+        livo_vdetect_stats st{};
+        check(livo_vio_detect(ctx_, dense_map_en ? -1 : scan_id_, frame_id, &state, &state_propagat, &vio, &d, img,
+                              width, height, &st),
+              "livo_vio_detect");
+        return st;
+    }
+
+    // The stored frames that no observation refers to any more give their slots back (the
+    // reference never frees imgs_; this map has a fixed frame store).  -> their ids, ascending
+    std::vector<int32_t> releaseFrames() {
+        int64_t n = 0;
+        check(livo_vmap_release_frames(ctx_, nullptr, 0, &n), "livo_vmap_release_frames");
+        std::vector<int32_t> ids((size_t)n);
+        if (n > 0) check(livo_vmap_release_frames(ctx_, ids.data(), n, &n), "livo_vmap_release_frames");
+        ids.resize((size_t)n);
+        return ids;
+    }
+
     livo_ctx* ctx() const { return ctx_; }
     const livo_params& params() const { return params_; }
 

@@ -14,6 +14,7 @@ path:
     feat_map / imgs_ (the visual map)    -> Context.vmap_reset / vmap_add_frame / vmap_add / vmap_dump
     LidarSelector::addFromSparseMap      -> Context.vio_match
     LidarSelector::addObservation        -> Context.vio_observe
+    LidarSelector::detect (one frame)    -> Context.vio_detect, Context.vmap_release_frames
 
 There is no CPU fallback: loading fails loudly if the HIP library is missing,
 and every compute call raises LivoError when the GPU path fails.
@@ -220,6 +221,25 @@ class VobsStats(C.Structure):
         "n_obs_total")]
 
 
+class VdetectParams(C.Structure):
+    _fields_ = [("grid_size", C.c_int32), ("ncc_en", C.c_int32), ("ncc_thre", C.c_double),
+                ("outlier_threshold", C.c_double)]
+
+
+class VdetectStats(C.Structure):
+    _fields_ = [("match", VmatchStats), ("select", VisStats), ("update", VioStats), ("observe", VobsStats),
+                ("n_matched", C.c_int64), ("n_new", C.c_int64), ("first_new_id", C.c_int32), ("pad_", C.c_int32)]
+
+
+def _stats_dict(st) -> dict:
+    """A stats struct as a dict (arrays as lists)."""
+    out = {}
+    for f, _ in st._fields_:
+        v = getattr(st, f)
+        out[f] = list(v) if hasattr(v, "__len__") else v
+    return out
+
+
 def vio_params(cam: dict, Rci, Pci) -> VioParams:
     """livo_vio_params from a camera dict (fx, fy, cx, cy, d, width, height) and the extrinsics."""
     p = VioParams()
@@ -300,6 +320,9 @@ SIGNATURES = {
                                  C.c_double, C.c_double, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64,
                                  C.POINTER(C.c_int64), C.POINTER(VmatchStats)]),
     "livo_vio_observe": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.POINTER(VobsStats)]),
+    "livo_vmap_release_frames": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "livo_vio_detect": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(State), C.POINTER(State), C.POINTER(VioParams),
+                                  C.POINTER(VdetectParams), _P, C.c_int32, C.c_int32, C.POINTER(VdetectStats)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -972,6 +995,40 @@ class Context:
         _check("livo_vio_observe", self._L.livo_vio_observe(
             self.h, frame_id, len(ids), _ptr(ids), _ptr(lev), _ptr(rec), C.byref(vs)))
         return rec, {f: int(getattr(vs, f)) for f, _ in VobsStats._fields_}
+
+    def vio_detect(self, frame_id: int, state: dict, gray, vio_params: VioParams, grid_size: int,
+                   ncc_en: bool = False, ncc_thre: float = 0.0, outlier_threshold: float = 100.0, scan_id: int = -1,
+                   prior: dict | None = None):
+        """LidarSelector::detect (livo_vio_detect): one camera frame in one call, equal to vio_match and
+        vio_select at `state`, vio_update on the survivors, vmap_add_frame(frame_id) at the updated state,
+        vio_observe of the survivors and vmap_add of the selected points, with nothing but counters, the state
+        and the observe's records crossing to the host.  vio_params carries max_iterations and img_point_cov.
+        Returns (state, {"match", "select", "update", "observe": the stages' stats dicts, "n_matched", "n_new",
+        "first_new_id"})."""
+        img = np.ascontiguousarray(gray, np.uint8)
+        if img.ndim != 2:
+            raise ValueError("gray must be (height, width)")
+        st = state_to_c(state)
+        pr = state_to_c(prior) if prior is not None else None
+        d = VdetectParams(int(grid_size), int(bool(ncc_en)), float(ncc_thre), float(outlier_threshold))
+        vs = VdetectStats()
+        _check("livo_vio_detect", self._L.livo_vio_detect(
+            self.h, scan_id, frame_id, C.byref(st), C.byref(pr) if pr is not None else None, C.byref(vio_params),
+            C.byref(d), _ptr(img), img.shape[1], img.shape[0], C.byref(vs)))
+        stats = {k: _stats_dict(getattr(vs, k)) for k in ("match", "select", "update", "observe")}
+        stats.update(n_matched=int(vs.n_matched), n_new=int(vs.n_new), first_new_id=int(vs.first_new_id))
+        return state_from_c(st), stats
+
+    def vmap_release_frames(self) -> np.ndarray:
+        """Releases the stored frames that no observation refers to (livo_vmap_release_frames); their slots go
+        to the frames stored next.  Returns the released frame ids, ascending."""
+        n = C.c_int64()
+        _check("livo_vmap_release_frames", self._L.livo_vmap_release_frames(self.h, None, 0, C.byref(n)))
+        ids = np.zeros(n.value, np.int32)
+        if n.value > 0:
+            _check("livo_vmap_release_frames", self._L.livo_vmap_release_frames(self.h, _ptr(ids), len(ids),
+                                                                                C.byref(n)))
+        return ids[:n.value]
 
     def scan_inherit_neighbors(self, dst: int, src: int):
         _check("livo_scan_inherit_neighbors", self._L.livo_scan_inherit_neighbors(self.h, dst, src))

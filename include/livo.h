@@ -612,9 +612,10 @@ int livo_vio_select(livo_ctx* ctx, int32_t scan_id, const livo_state* state, con
  * frame holds its gray image and pose.  livo_vmap_add stores what it is given
  * and never deletes; addObservation's policy (add_flag, the cap,
  * getFurthestViewObs / deleteFeatureRef, the new patch pyramid and score) is
- * livo_vio_observe below, which edits the map on the device.  Releasing stored
- * frames is not here: an eviction can leave a frame that no observation refers
- * to, and it keeps its slot.
+ * livo_vio_observe below, which edits the map on the device.  An eviction can
+ * leave a stored frame that no observation refers to; such a frame can never be
+ * referred to again (observations are made from the current frame only), and
+ * livo_vmap_release_frames gives its slot back to the frames stored later.
  * ------------------------------------------------------------------------ */
 typedef struct livo_vmap_counts {
     int64_t n_points, n_obs, n_frames;
@@ -646,7 +647,8 @@ int livo_vmap_reset(livo_ctx* ctx, int64_t max_points, int64_t max_frames, int32
  * image device to device.  Every frame of a map has the first one's size and
  * intrinsics source p->cam (undistorted: |d0| <= 1e-7).  LIVO_E_INVALID: no map,
  * a distorted camera, a size mismatch, no retained image, a duplicate id;
- * LIVO_E_CAPACITY: the store is full. */
+ * LIVO_E_CAPACITY: max_frames frames are live (livo_vmap_release_frames may
+ * free some).  A released slot is taken before a fresh one. */
 int livo_vmap_add_frame(livo_ctx* ctx, int32_t frame_id, const livo_state* state, const livo_vio_params* p,
                         const uint8_t* gray, int32_t width, int32_t height);
 /* Adds n observations seen from stored frame frame_id.  point_ids == NULL
@@ -663,7 +665,16 @@ int livo_vmap_add_frame(livo_ctx* ctx, int32_t frame_id, const livo_state* state
  * written on an error. */
 int livo_vmap_add(livo_ctx* ctx, int32_t frame_id, int64_t n, const int32_t* point_ids, const livo_vis_point* pts,
                   const int32_t* levels, const float* patches, int32_t* ids_out);
+/* n_frames counts the live frames: those stored and not released. */
 int livo_vmap_info(livo_ctx* ctx, livo_vmap_counts* info);
+/* Releases every stored frame that no observation refers to. released (cap ids, ascending
+ * frame id; may be NULL with cap == 0 to count) and *n = frames released (set on LIVO_OK
+ * and LIVO_E_CAPACITY; cap < *n releases nothing).  A released id may be stored again.
+ * The counting form (released == NULL, cap == 0) returns LIVO_OK with *n = the frames a
+ * releasing call would release now, and releases nothing; cap < *n with a buffer returns
+ * LIVO_E_CAPACITY.  The references are counted on the device over every point's
+ * observations; nothing that livo_vmap_dump shows changes.  LIVO_E_INVALID: no map. */
+int livo_vmap_release_frames(livo_ctx* ctx, int32_t* released, int64_t cap, int64_t* n);
 /* The map in id / list order: points (cap_points), obs (cap_obs) and patches
  * (cap_obs x 3 x patch_size^2) may all be NULL to query *n_points and *n_obs,
  * else the capacities must suffice (LIVO_E_RANGE otherwise, the counts set). */
@@ -784,6 +795,54 @@ typedef struct livo_vobs_stats {
 } livo_vobs_stats;
 int livo_vio_observe(livo_ctx* ctx, int32_t frame_id, int64_t n, const int32_t* point_ids,
                      const int32_t* search_levels, livo_vobs_point* out, livo_vobs_stats* stats);
+/* LidarSelector::detect(img, pg) (src/lidar_selection.cpp:1024-1073) behind its image
+ * conversion: one camera frame through every stage above, resident from stage to stage.
+ * The call equals this chain of calls, byte for byte in *state, stats, livo_vmap_dump and
+ * livo_vmap_info:
+ *   1. livo_vio_match(scan_id, *state, gray) with d's grid_size, ncc_en, ncc_thre and
+ *      outlier_threshold                         -> the survivors S
+ *   2. livo_vio_select(scan_id, *state, gray) with d->grid_size -> the new points N
+ *   3. livo_vio_update(gray, S.pos, S.search_levels, S.patches, state, prior); without
+ *      survivors *state is left as it is (ComputeJ returns at total_points == 0)
+ *   4. livo_vmap_add_frame(frame_id, *state after 3, gray)
+ *   5. livo_vio_observe(frame_id, S.point_id, S.search_level)
+ *   6. livo_vmap_add(frame_id, N, point_ids = NULL)
+ * The reference inserts addSparseMap's points before ComputeJ, their Feature holding
+ * T_f_w_ at the state before the update; this map holds one pose per frame, the updated
+ * one, and creates the points behind the observe, so that their ids cannot be among the
+ * observed ones.
+ * gray is required (a frame is a new image): it is uploaded once, serves 1 to 3 and
+ * becomes the stored frame's image by a device copy.  No stage's result array is copied to
+ * the host: behind 2 the counters are read (the survivor and selected counts size the
+ * later launches), at the end the updated state, the observe's records and counters and
+ * the stored frame.  livo_vio_select's and livo_vio_match's retained images are untouched.
+ * Refused before any launch, with nothing changed: LIVO_E_INVALID for no map, gray == NULL,
+ * frame_id < 0 or stored already, and whatever the six calls refuse in p, d, width and
+ * height; LIVO_E_NOSCAN; LIVO_E_CAPACITY for a full frame store.  LIVO_E_CAPACITY too when
+ * the map's points and N together exceed max_points, known behind 2: then *state is
+ * untouched, no frame is stored, no observation and no point is added, stats holds match,
+ * select, n_matched, n_new and first_new_id, and the map's level-0 patches are left
+ * rewarped, exactly as livo_vio_match's own capacity error leaves them.  stats may be
+ * NULL.  Two calls on the same input give the same bytes. */
+typedef struct livo_vdetect_params {
+    int32_t grid_size;          /* match and select */
+    int32_t ncc_en;
+    double  ncc_thre;
+    double  outlier_threshold;
+} livo_vdetect_params;
+typedef struct livo_vdetect_stats {
+    livo_vmatch_stats match;
+    livo_vis_stats    select;
+    livo_vio_stats    update;
+    livo_vobs_stats   observe;
+    int64_t n_matched;          /* survivors handed to the update and the observe */
+    int64_t n_new;              /* points created                                  */
+    int32_t first_new_id;       /* -1 if n_new == 0                                */
+    int32_t pad_;
+} livo_vdetect_stats;
+int livo_vio_detect(livo_ctx* ctx, int32_t scan_id, int32_t frame_id, livo_state* state, const livo_state* prior,
+                    const livo_vio_params* p, const livo_vdetect_params* d, const uint8_t* gray, int32_t width,
+                    int32_t height, livo_vdetect_stats* stats);
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
