@@ -21,7 +21,7 @@
 #include <thread>
 #include <vector>
 
-#include "carve.h"
+#include "host_layouts.h"
 #include "livo_internal.h"
 
 using namespace livo;
@@ -154,7 +154,9 @@ struct IvoxDev {
     unsigned long long* tlast = nullptr;
     uint32_t *first = nullptr, *lastp1 = nullptr;
     uint8_t* evict = nullptr;
-    // eviction scratch (allocated the first time the capacity is reached)
+    // eviction scratch (allocated the first time the capacity is reached): ev_cap of each, carved from ev_buf
+    void* ev_buf = nullptr;
+    size_t ev_bytes = 0;
     unsigned long long *ev_k = nullptr, *ev_k2 = nullptr;
     uint32_t *ev_a = nullptr, *ev_b = nullptr, *ev_c = nullptr, *ev_d = nullptr;
     int64_t ev_cap = 0;
@@ -171,6 +173,8 @@ struct DynDev {
     unsigned long long *keys = nullptr, *skeys = nullptr;
     uint32_t *iota = nullptr, *svals = nullptr, *heads = nullptr, *runid = nullptr, *starts = nullptr;
     int64_t sort_cap = 0;
+    void* add_buf = nullptr;     // Add_Points' scratch: add_cap points of each array below, one carve
+    size_t add_bytes = 0;
     float *W = nullptr, *seq = nullptr, *Ws = nullptr;
     uint32_t *defer = nullptr, *dpos = nullptr, *dlist = nullptr, *keep = nullptr, *apos = nullptr;
     int64_t add_cap = 0;
@@ -814,12 +818,13 @@ static int ensure_nn_records(livo_ctx* c, ScanBuf* s, hipStream_t st) {
     std::memcpy(pose.rot, s->nn_pose, 9 * sizeof(double));
     std::memcpy(pose.pos, s->nn_pose + 9, 3 * sizeof(double));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (an earlier user of the staging slot)
-    const size_t plane_b = ((size_t)s->n * 16 + 255) & ~(size_t)255;
-    RC_TRY(ensure_dev_bytes(&c->rec_tmp, &c->rec_tmp_bytes, plane_b + (size_t)s->n));
+    RC_TRY(ensure_dev_bytes(&c->rec_tmp, &c->rec_tmp_bytes, carve_bytes(plane_tmp_layout, (size_t)s->n)));
+    Carve k{(char*)c->rec_tmp};
+    const PlaneTmp T = plane_tmp_layout(k, (size_t)s->n);
     init_slot(c->h_slots[0], pose, pose, c->params.max_iterations);
     fill_job(c->h_jobs[0], *s, c->d_slots);
-    c->h_jobs[0].plane = (float*)c->rec_tmp;
-    c->h_jobs[0].pstate = (uint8_t*)c->rec_tmp + plane_b;
+    c->h_jobs[0].plane = T.plane;
+    c->h_jobs[0].pstate = T.pstate;
     HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(c->d_jobs, c->h_jobs, sizeof(HsJob), hipMemcpyHostToDevice, st));
     KnnParams kp = make_knn_params(c);
@@ -852,8 +857,7 @@ static void ivox_free(IvoxDev& v) {
     dev_free(v.src); dev_free(v.slot_of); dev_free(v.iota); dev_free(v.skeys); dev_free(v.svals);
     dev_free(v.big);
     dev_free(v.tlast); dev_free(v.first); dev_free(v.lastp1); dev_free(v.evict);
-    dev_free(v.ev_k); dev_free(v.ev_k2);
-    dev_free(v.ev_a); dev_free(v.ev_b); dev_free(v.ev_c); dev_free(v.ev_d);
+    dev_free(v.ev_buf);
     v = IvoxDev{};
 }
 
@@ -934,13 +938,55 @@ static int ensure_prim(livo_ctx* c, size_t bytes) {
 }
 
 // Exclusive scan of n u32 through rocPRIM (out != in).
-static int ivox_scan(livo_ctx* c, const uint32_t* in, uint32_t* out, int64_t n) {
+static int scan_u32(livo_ctx* c, const uint32_t* in, uint32_t* out, int64_t n) {
     size_t tb = 0;
     int rc = prim_exclusive_scan_u32(nullptr, &tb, in, out, n, c->stream);
     if (!rc) rc = ensure_prim(c, tb);
     tb = c->prim_bytes;
     if (!rc) rc = prim_exclusive_scan_u32(c->prim_tmp, &tb, in, out, n, c->stream);
     return rc;
+}
+
+// The count behind an exclusive scan, pos[n - 1] + flags[n - 1]: read() enqueues
+// the two copies (none for n == 0), sum() holds once the caller has synchronised.
+struct ScanCount {
+    uint32_t w[2] = {0u, 0u};
+    int read(const uint32_t* pos, const uint32_t* flags, int64_t n, hipStream_t st) {
+        if (n <= 0) return LIVO_OK;
+        HIP_TRY(hipMemcpyAsync(&w[0], pos + n - 1, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&w[1], flags + n - 1, 4, hipMemcpyDeviceToHost, st));
+        return LIVO_OK;
+    }
+    int64_t sum() const { return (int64_t)w[0] + w[1]; }
+};
+
+// Stable radix sort of n (key, value) pairs through rocPRIM (`sort`: prim_sort_pairs_u32 /
+// _u64) on `st`: sized with a null scratch, the scratch grown, then run.  drain: the stream
+// is synchronised before its scratch grows (the upload streams, which may still be sorting in it).
+template <class K>
+static int sort_pairs_on(int (*sort)(void*, size_t*, const K*, K*, const uint32_t*, uint32_t*, int64_t, int, void*),
+                         hipStream_t st, void** prim, size_t* prim_bytes, bool drain, const K* kin, K* kout,
+                         const uint32_t* vin, uint32_t* vout, int64_t n, int bits) {
+    size_t tb = 0;
+    int rc = sort(nullptr, &tb, kin, kout, vin, vout, n, bits, st);
+    if (!rc && drain && tb > *prim_bytes && hipStreamSynchronize(st) != hipSuccess) rc = LIVO_E_HIP;
+    if (!rc) rc = ensure_dev_bytes(prim, prim_bytes, tb);
+    tb = *prim_bytes;
+    if (!rc) rc = sort(*prim, &tb, kin, kout, vin, vout, n, bits, st);
+    return rc;
+}
+static int sort_u32_on(hipStream_t st, void** prim, size_t* prim_bytes, bool drain, const uint32_t* kin, uint32_t* kout,
+                       const uint32_t* vin, uint32_t* vout, int64_t n, int bits) {
+    return sort_pairs_on(prim_sort_pairs_u32, st, prim, prim_bytes, drain, kin, kout, vin, vout, n, bits);
+}
+// ... on the context's stream and scratch
+static int sort_u32(livo_ctx* c, const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout, int64_t n,
+                    int bits) {
+    return sort_u32_on(c->stream, &c->prim_tmp, &c->prim_bytes, false, kin, kout, vin, vout, n, bits);
+}
+static int sort_u64(livo_ctx* c, const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin,
+                    uint32_t* vout, int64_t n) {
+    return sort_pairs_on(prim_sort_pairs_u64, c->stream, &c->prim_tmp, &c->prim_bytes, false, kin, kout, vin, vout, n, 64);
 }
 
 static IvoxParams ivox_params(livo_ctx* c) {
@@ -997,13 +1043,19 @@ static int ivox_ensure_big(livo_ctx* c) {
 static int ivox_ev_scratch(livo_ctx* c, int64_t need) {
     IvoxDev& v = c->iv;
     if (need <= v.ev_cap) return LIVO_OK;
-    dev_free(v.ev_k); dev_free(v.ev_k2);
-    dev_free(v.ev_a); dev_free(v.ev_b); dev_free(v.ev_c); dev_free(v.ev_d);
     v.ev_cap = 0;
     const size_t cap = (size_t)need;
-    if (dev_alloc(&v.ev_k, cap) || dev_alloc(&v.ev_k2, cap) || dev_alloc(&v.ev_a, cap) || dev_alloc(&v.ev_b, cap) ||
-        dev_alloc(&v.ev_c, cap) || dev_alloc(&v.ev_d, cap))
-        return LIVO_E_OOM;
+    auto layout = [&](Carve k) {
+        v.ev_k = k.take<unsigned long long>(cap);
+        v.ev_k2 = k.take<unsigned long long>(cap);
+        v.ev_a = k.take<uint32_t>(cap);
+        v.ev_b = k.take<uint32_t>(cap);
+        v.ev_c = k.take<uint32_t>(cap);
+        v.ev_d = k.take<uint32_t>(cap);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&v.ev_buf, &v.ev_bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)v.ev_buf});
     v.ev_cap = need;
     return LIVO_OK;
 }
@@ -1077,11 +1129,7 @@ static int ivox_add_part(livo_ctx* c, int64_t off, int64_t n, int64_t* done) {
         unsigned long long* cnt = v.ctr + 3;  // (scratch counter; ctr[3] is set again below)
         HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), c->stream));
         rc = launch_ivox_newfirst(P, v.ev_a, cnt, c->stream);
-        size_t tb = 0;
-        if (!rc) rc = prim_sort_pairs_u32(nullptr, &tb, v.ev_a, v.ev_b, v.ev_a, v.ev_c, N_new, 32, c->stream);
-        if (!rc) rc = ensure_prim(c, tb);
-        tb = c->prim_bytes;
-        if (!rc) rc = prim_sort_pairs_u32(c->prim_tmp, &tb, v.ev_a, v.ev_b, v.ev_a, v.ev_c, N_new, 32, c->stream);
+        if (!rc) rc = sort_u32(c, v.ev_a, v.ev_b, v.ev_a, v.ev_c, N_new, 32);
         if (rc) return rc;
         // creation index of each new grid from the (C - 1 - E)-th: the eviction times
         const int64_t c0 = std::max<int64_t>(0, C - 1 - E);
@@ -1092,23 +1140,15 @@ static int ivox_add_part(livo_ctx* c, int64_t off, int64_t n, int64_t* done) {
         rc = launch_ivox_oldkeys(P, v.ev_k, v.ev_a, cnt, c->stream);
         if (rc) return rc;
         const int64_t n_old = E;
-        tb = 0;
-        rc = prim_sort_pairs_u64(nullptr, &tb, v.ev_k, v.ev_k2, v.ev_a, v.ev_b, n_old, 64, c->stream);
-        if (!rc) rc = ensure_prim(c, tb);
-        tb = c->prim_bytes;
-        if (!rc) rc = prim_sort_pairs_u64(c->prim_tmp, &tb, v.ev_k, v.ev_k2, v.ev_a, v.ev_b, n_old, 64, c->stream);
+        rc = sort_u64(c, v.ev_k, v.ev_k2, v.ev_a, v.ev_b, n_old);
         if (!rc) rc = launch_ivox_untouched(P, v.ev_b, n_old, v.ev_c, c->stream);
-        if (!rc) rc = ivox_scan(c, v.ev_c, v.ev_d, n_old);
+        if (!rc) rc = scan_u32(c, v.ev_c, v.ev_d, n_old);
+        ScanCount untouched;
+        if (!rc) rc = untouched.read(v.ev_d, v.ev_c, n_old, c->stream);
         if (rc) return rc;
-        uint32_t tail[2] = {0u, 0u};
-        if (n_old > 0) {
-            HIP_TRY(hipMemcpyAsync(&tail[0], v.ev_d + n_old - 1, 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(&tail[1], v.ev_c + n_old - 1, 4, hipMemcpyDeviceToHost, c->stream));
-        }
         HIP_TRY(hipStreamSynchronize(c->stream));
         const uint32_t j_first = t_ev[0];
-        const int64_t untouched = (int64_t)tail[0] + tail[1];
-        bool conflict = ev > untouched;
+        bool conflict = ev > untouched.sum();
         if (!conflict) {
             HIP_TRY(hipMemsetAsync(v.ctr + 3, 0, sizeof(unsigned long long), c->stream));
             rc = launch_ivox_victims(P, v.ev_b, v.ev_d, n_old, ev, j_first, c->stream);
@@ -1130,7 +1170,7 @@ static int ivox_add_part(livo_ctx* c, int64_t off, int64_t n, int64_t* done) {
                 HIP_TRY(hipMemsetAsync(v.ctr, 0, 5 * sizeof(unsigned long long), c->stream));
                 rc = launch_ivox_insert(P, c->stream);
                 if (!rc) rc = launch_ivox_untouched(P, v.ev_b, n_old, v.ev_c, c->stream);
-                if (!rc) rc = ivox_scan(c, v.ev_c, v.ev_d, n_old);
+                if (!rc) rc = scan_u32(c, v.ev_c, v.ev_d, n_old);
                 // (the victims kernel's conflict flag is conservative -- it also flags
                 // an older grid touched between two evictions -- the scan is exact: off)
                 if (!rc) rc = launch_ivox_victims(P, v.ev_b, v.ev_d, n_old, evs, 0xFFFFFFFFu, c->stream);
@@ -1179,17 +1219,12 @@ static int ivox_add_part(livo_ctx* c, int64_t off, int64_t n, int64_t* done) {
         P.npts = v.pts[other];
     }
     rc = launch_ivox_prepare(P, c->stream);
-    if (!rc) rc = ivox_scan(c, v.tot, v.newstart, v.table);
-    if (!rc) rc = ivox_scan(c, v.addcnt, v.addstart, v.table);
+    if (!rc) rc = scan_u32(c, v.tot, v.newstart, v.table);
+    if (!rc) rc = scan_u32(c, v.addcnt, v.addstart, v.table);
     if (!rc) {
         int bits = 1;
         while (((int64_t)1 << bits) <= v.table) bits++;  // the out-of-range key `table` included
-        size_t tb = 0;
-        rc = prim_sort_pairs_u32(nullptr, &tb, v.slot_of, v.skeys, v.iota, v.svals, consumed, bits, c->stream);
-        if (!rc) rc = ensure_prim(c, tb);
-        tb = c->prim_bytes;
-        if (!rc)
-            rc = prim_sort_pairs_u32(c->prim_tmp, &tb, v.slot_of, v.skeys, v.iota, v.svals, consumed, bits, c->stream);
+        rc = sort_u32(c, v.slot_of, v.skeys, v.iota, v.svals, consumed, bits);
     }
     if (!rc) rc = launch_ivox_move(P, c->stream);
     if (!rc) rc = launch_ivox_place(P, c->stream);
@@ -1198,19 +1233,12 @@ static int ivox_add_part(livo_ctx* c, int64_t off, int64_t n, int64_t* done) {
     if (!rc && ev > 0) rc = launch_ivox_drop(P, c->stream);
     if (rc) return rc;
     // the number of points the evicted grids held leaves the map
-    unsigned long long gone = 0;
-    int64_t npts_new = 0;
-    {
-        uint32_t tail[2];
-        HIP_TRY(hipMemcpyAsync(&tail[0], v.newstart + v.table - 1, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&tail[1], v.tot + v.table - 1, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(ctr, v.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        npts_new = (int64_t)tail[0] + tail[1];
-        (void)gone;
-    }
+    ScanCount npts_new;
+    RC_TRY(npts_new.read(v.newstart, v.tot, v.table, c->stream));
+    HIP_TRY(hipMemcpyAsync(ctr, v.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     v.cur = other;
-    v.npts = npts_new;
+    v.npts = npts_new.sum();
     v.ngrids += N_new_b - ev;
     v.next_id += consumed;
     v.max_grid = (int64_t)ctr[2];
@@ -1262,8 +1290,7 @@ static void dyn_free(DynDev& d) {
     dev_free(d.all); dev_free(d.alive);
     dev_free(d.keys); dev_free(d.skeys); dev_free(d.iota); dev_free(d.svals);
     dev_free(d.heads); dev_free(d.runid); dev_free(d.starts);
-    dev_free(d.W); dev_free(d.seq); dev_free(d.Ws);
-    dev_free(d.defer); dev_free(d.dpos); dev_free(d.dlist); dev_free(d.keep); dev_free(d.apos);
+    dev_free(d.add_buf);
     dev_free(d.boxes); dev_free(d.ctr);  // (d.dirty lives in d.ctr's allocation)
     dev_free(d.rpts); dev_free(d.rpos); dev_free(d.dslots); dev_free(d.dpts);
     dev_free(d.dvslots); dev_free(d.dvidx); dev_free(d.gpts_alt);
@@ -1314,15 +1341,22 @@ static int dyn_sort_scratch(livo_ctx* c, int64_t n) {
 static int dyn_add_scratch(livo_ctx* c, int64_t n) {
     DynDev& d = c->dyn;
     if (n <= d.add_cap) return LIVO_OK;
-    const int64_t cap = std::max<int64_t>(n + (n >> 2), 4096);
-    dev_free(d.W); dev_free(d.seq); dev_free(d.Ws);
-    dev_free(d.defer); dev_free(d.dpos); dev_free(d.dlist); dev_free(d.keep); dev_free(d.apos);
+    const size_t cap = (size_t)std::max<int64_t>(n + (n >> 2), 4096);
     d.add_cap = 0;
-    if (dev_alloc(&d.W, (size_t)cap * 4) || dev_alloc(&d.seq, (size_t)cap * 4) || dev_alloc(&d.Ws, (size_t)cap * 4) ||
-        dev_alloc(&d.defer, cap) ||
-        dev_alloc(&d.dpos, cap) || dev_alloc(&d.dlist, cap) || dev_alloc(&d.keep, cap) || dev_alloc(&d.apos, cap))
-        return LIVO_E_OOM;
-    d.add_cap = cap;
+    auto layout = [&](Carve k) {
+        d.W = k.take<float>(cap * 4);
+        d.seq = k.take<float>(cap * 4);
+        d.Ws = k.take<float>(cap * 4);
+        d.defer = k.take<uint32_t>(cap);
+        d.dpos = k.take<uint32_t>(cap);
+        d.dlist = k.take<uint32_t>(cap);
+        d.keep = k.take<uint32_t>(cap);
+        d.apos = k.take<uint32_t>(cap);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&d.add_buf, &d.add_bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)d.add_buf});
+    d.add_cap = (int64_t)cap;
     return LIVO_OK;
 }
 
@@ -1346,24 +1380,6 @@ static int dyn_scan_ready(livo_ctx* c, int64_t n) {
         sc.status_cap = cap;
     }
     return LIVO_OK;
-}
-static int sort_u32(livo_ctx* c, const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout, int64_t n,
-                    int bits) {
-    size_t tb = 0;
-    int rc = prim_sort_pairs_u32(nullptr, &tb, kin, kout, vin, vout, n, bits, c->stream);
-    if (!rc) rc = ensure_prim(c, tb);
-    tb = c->prim_bytes;
-    if (!rc) rc = prim_sort_pairs_u32(c->prim_tmp, &tb, kin, kout, vin, vout, n, bits, c->stream);
-    return rc;
-}
-static int sort_u64(livo_ctx* c, const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin,
-                    uint32_t* vout, int64_t n) {
-    size_t tb = 0;
-    int rc = prim_sort_pairs_u64(nullptr, &tb, kin, kout, vin, vout, n, 64, c->stream);
-    if (!rc) rc = ensure_prim(c, tb);
-    tb = c->prim_bytes;
-    if (!rc) rc = prim_sort_pairs_u64(c->prim_tmp, &tb, kin, kout, vin, vout, n, 64, c->stream);
-    return rc;
 }
 
 // The runs' base point set = the current cell grid (c->gpts, c->map_points
@@ -1468,7 +1484,7 @@ static int dyn_runs_update(livo_ctx* c) {
         d.dpts_cap = cap;
     }
     rc = launch_dyn_gather(d.skeys, d.svals, nd, d.all + 4 * d.base_ids, d.dpts, d.heads, c->stream);
-    if (!rc) rc = ivox_scan(c, d.heads, d.runid, nd);
+    if (!rc) rc = scan_u32(c, d.heads, d.runid, nd);
     if (!rc) rc = launch_dyn_runs(d.heads, d.runid, nd, d.starts, d.ctr + kDynRuns, c->stream);
     if (rc) return rc;
     unsigned long long cells = 0;
@@ -1593,7 +1609,7 @@ static int dyn_rebuild(livo_ctx* c) {
         if (!rc) rc = sort_u64(c, d.keys, d.skeys, d.iota, d.svals, d.n_ids);
     }
     if (!rc) rc = launch_dyn_gather(d.skeys, d.svals, na, d.all, c->gpts, d.heads, c->stream);
-    if (!rc && na > 0) rc = ivox_scan(c, d.heads, d.runid, na);
+    if (!rc && na > 0) rc = scan_u32(c, d.heads, d.runid, na);
     if (!rc && na > 0) rc = launch_dyn_runs(d.heads, d.runid, na, d.starts, d.ctr + kDynRuns, c->stream);
     if (rc) return rc;
     unsigned long long h[kDynCtrN];
@@ -2114,7 +2130,7 @@ static int build_index_runs(livo_ctx* c, int64_t n, const unsigned long long* sk
                             unsigned long long* nruns_dev, uint32_t* plen, uint32_t* pstart, uint32_t** out,
                             GridSlot** slots, int* log2_out, int64_t* words) {
     int rc = launch_run_heads(skeys, n, heads, c->stream);
-    if (!rc) rc = ivox_scan(c, heads, runid, n);
+    if (!rc) rc = scan_u32(c, heads, runid, n);
     if (!rc) rc = launch_dyn_runs(heads, runid, n, starts, nruns_dev, c->stream);
     unsigned long long runs = 0;
     if (!rc && hipMemcpyAsync(&runs, nruns_dev, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LIVO_E_HIP;
@@ -2122,15 +2138,12 @@ static int build_index_runs(livo_ctx* c, int64_t n, const unsigned long long* sk
     if (rc) return rc;
     if (runs == 0) return LIVO_E_INVALID;
     rc = launch_run_plen(starts, (int64_t)runs, plen, c->stream);
-    if (!rc) rc = ivox_scan(c, plen, pstart, (int64_t)runs);
-    uint32_t tail[2] = {0u, 0u};
-    if (!rc && hipMemcpyAsync(&tail[0], pstart + runs - 1, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = LIVO_E_HIP;
-    if (!rc && hipMemcpyAsync(&tail[1], plen + runs - 1, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = LIVO_E_HIP;
+    if (!rc) rc = scan_u32(c, plen, pstart, (int64_t)runs);
+    ScanCount padded;
+    if (!rc) rc = padded.read(pstart, plen, (int64_t)runs, c->stream);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
     if (rc) return rc;
-    const int64_t total = (int64_t)tail[0] + tail[1];  // (u32 lengths: the scan wraps beyond 2^32 words)
+    const int64_t total = padded.sum();  // (u32 lengths: the scan wraps beyond 2^32 words)
     if (total < n || total + kRunPad >= (int64_t)0xFFFFFFFFll) return LIVO_E_RANGE;
     if (dev_alloc(out, (size_t)(total + kRunPad))) return LIVO_E_OOM;
     rc = hipMemsetAsync(*out, 0, (size_t)(total + kRunPad) * sizeof(uint32_t), c->stream) == hipSuccess ? LIVO_OK
@@ -2171,35 +2184,17 @@ static int build_cell_runs_into(livo_ctx* c, const float* pts, int64_t M, GridSl
     if (M <= 0) return LIVO_OK;
     const int64_t n = M * 27;
     if (n + 8 >= (int64_t)kRunPosLimit) return LIVO_E_RANGE;  // 31-bit run positions (kRunPos)
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b4 = al((size_t)n * 4), b8 = al((size_t)n * 8);
     char* scr = nullptr;
-    if (hipMalloc((void**)&scr, 7 * b4 + 2 * b8 + al(((size_t)n + 1) * 4) + 256) != hipSuccess) return LIVO_E_OOM;
-    char* p = scr;
-    uint32_t* rho = (uint32_t*)p; p += b4;
-    uint32_t* iota = (uint32_t*)p; p += b4;
-    uint32_t* srho = (uint32_t*)p; p += b4;
-    uint32_t* e1 = (uint32_t*)p; p += b4;
-    uint32_t* e2 = (uint32_t*)p; p += b4;
-    uint32_t* heads = (uint32_t*)p; p += b4;
-    uint32_t* runid = (uint32_t*)p; p += b4;
-    unsigned long long* keys = (unsigned long long*)p; p += b8;
-    unsigned long long* skeys = (unsigned long long*)p; p += b8;
-    uint32_t* starts = (uint32_t*)p; p += al(((size_t)n + 1) * 4);
-    unsigned long long* nruns = (unsigned long long*)p;
-    int rc = launch_cr_rho(pts, n, c->gorg, c->gh, rho, iota, c->stream);
-    if (!rc) {
-        size_t tb = 0;
-        rc = prim_sort_pairs_u32(nullptr, &tb, rho, srho, iota, e1, n, 32, c->stream);
-        if (!rc) rc = ensure_prim(c, tb);
-        tb = c->prim_bytes;
-        if (!rc) rc = prim_sort_pairs_u32(c->prim_tmp, &tb, rho, srho, iota, e1, n, 32, c->stream);
-    }
-    if (!rc) rc = launch_cr_key(pts, e1, n, c->gorg, c->gh, keys, c->stream);
-    if (!rc) rc = sort_u64(c, keys, skeys, e1, e2, n);
-    // (rho, iota: dead after the sorts) the padded run lengths and their scan
-    if (!rc) rc = build_index_runs(c, n, skeys, e2, nullptr, heads, runid, starts, nruns, rho, iota, idx, slots, log2,
-                                   words);
+    if (hipMalloc((void**)&scr, carve_bytes(run_build_layout, (size_t)n, false)) != hipSuccess) return LIVO_E_OOM;
+    Carve k{scr};
+    const RunBuild L = run_build_layout(k, (size_t)n, false);
+    int rc = launch_cr_rho(pts, n, c->gorg, c->gh, L.rho, L.iota, c->stream);
+    if (!rc) rc = sort_u32(c, L.rho, L.srho, L.iota, L.e1, n, 32);
+    if (!rc) rc = launch_cr_key(pts, L.e1, n, c->gorg, c->gh, L.keys, c->stream);
+    if (!rc) rc = sort_u64(c, L.keys, L.skeys, L.e1, L.e2, n);
+    // the padded run lengths and their scan (in rho and iota, dead after the sorts)
+    if (!rc) rc = build_index_runs(c, n, L.skeys, L.e2, nullptr, L.heads, L.runid, L.starts, L.nruns, L.plen, L.pstart,
+                                   idx, slots, log2, words);
     (void)hipFree(scr);
     return rc;
 }
@@ -2217,16 +2212,19 @@ static int build_ball_runs_idx(livo_ctx* c, int64_t M, float r5, float bh, float
     int64_t cap = (int64_t)1 << 29;
     if (const char* env = std::getenv("LIVO_BR_CHUNK")) cap = std::max<int64_t>(1 << 16, std::atoll(env));
     cap = std::min<int64_t>(cap, ((int64_t)1 << 31) - 64);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     uint32_t* cnt = nullptr;
     uint32_t* off = nullptr;
     unsigned long long* tot = nullptr;
-    if (dev_alloc(&cnt, (size_t)M) || dev_alloc(&off, (size_t)M) || dev_alloc(&tot, 1)) {
+    // an early return leaves nothing behind: the counts, their scan and the run array so far
+    // (c->bpts is null on entry: build_ball_runs has freed it)
+    auto fail = [&](int rc) {
         dev_free(cnt);
         dev_free(off);
         dev_free(tot);
-        return LIVO_E_OOM;
-    }
+        dev_free(c->bpts);
+        return rc;
+    };
+    if (dev_alloc(&cnt, (size_t)M) || dev_alloc(&off, (size_t)M) || dev_alloc(&tot, 1)) return fail(LIVO_E_OOM);
     // entries of the anchors with x index in [x0, x1) (a count pass over the map)
     auto count = [&](int x0, int x1, unsigned long long* n_out) -> int {
         int rc = hipMemsetAsync(tot, 0, 8, c->stream) == hipSuccess ? LIVO_OK : LIVO_E_HIP;
@@ -2266,80 +2264,47 @@ static int build_ball_runs_idx(livo_ctx* c, int64_t M, float r5, float bh, float
         max_n = std::max(max_n, ch.n);
     }
     dev_free(tot);
-    if (rc || total_entries == 0) {
-        dev_free(cnt);
-        dev_free(off);
-        return rc;
-    }
+    if (rc || total_entries == 0) return fail(rc);
     // the run array: the entries plus the padding of every run to 4 words (grown if short)
     int64_t words_cap = total_entries + total_entries / 8 + 4096 + kRunPad;
     if (dev_alloc(&c->bpts, (size_t)words_cap) ||
-        hipMemsetAsync(c->bpts, 0, (size_t)words_cap * sizeof(uint32_t), c->stream) != hipSuccess) {
-        dev_free(cnt);
-        dev_free(off);
-        dev_free(c->bpts);
-        return LIVO_E_OOM;
-    }
-    const int64_t n = max_n;
-    const size_t b4 = al((size_t)n * 4), b8 = al((size_t)n * 8);
+        hipMemsetAsync(c->bpts, 0, (size_t)words_cap * sizeof(uint32_t), c->stream) != hipSuccess)
+        return fail(LIVO_E_OOM);
+    // one carve for the largest chunk, reused by every chunk
     char* scr = nullptr;
-    if (hipMalloc((void**)&scr, 7 * b4 + 3 * b8 + 2 * al(((size_t)n + 1) * 4) + 256) != hipSuccess) {
-        dev_free(cnt);
-        dev_free(off);
-        dev_free(c->bpts);
-        return LIVO_E_OOM;
-    }
-    char* p = scr;
-    uint32_t* rho = (uint32_t*)p; p += b4;
-    uint32_t* iota = (uint32_t*)p; p += b4;
-    uint32_t* srho = (uint32_t*)p; p += b4;
-    uint32_t* e1 = (uint32_t*)p; p += b4;
-    uint32_t* e2 = (uint32_t*)p; p += b4;
-    uint32_t* pt = (uint32_t*)p; p += b4;
-    uint32_t* heads = (uint32_t*)p; p += b4;
-    unsigned long long* keys = (unsigned long long*)p; p += b8;
-    unsigned long long* key1 = (unsigned long long*)p; p += b8;
-    unsigned long long* skeys = (unsigned long long*)p; p += b8;
-    uint32_t* starts = (uint32_t*)p; p += al(((size_t)n + 1) * 4);
-    uint32_t* plen = (uint32_t*)p; p += al(((size_t)n + 1) * 4);
-    unsigned long long* nruns_dev = (unsigned long long*)p;
-    uint32_t* runid = rho;    // (rho is dead after the first sort)
-    uint32_t* pstart = srho;  // (srho too)
+    if (hipMalloc((void**)&scr, carve_bytes(run_build_layout, (size_t)max_n, true)) != hipSuccess)
+        return fail(LIVO_E_OOM);
+    Carve k{scr};
+    const RunBuild L = run_build_layout(k, (size_t)max_n, true);
     GridSlot* trip = nullptr;
     int64_t trip_cap = 0, runs_total = 0, base = 0;
     for (const Chunk& ch : chunks) {
         const int64_t nc = ch.n;
-        rc = launch_br_count(c->gpts, M, c->gorg, bh, brmax, cnt, nruns_dev, c->stream, ch.x0, ch.x1);
-        if (!rc) rc = ivox_scan(c, cnt, off, M);
-        if (!rc) rc = launch_br_emit(c->gpts, M, c->gorg, bh, brmax, off, rho, keys, pt, iota, c->stream, ch.x0, ch.x1);
-        if (!rc) {
-            size_t tb = 0;
-            rc = prim_sort_pairs_u32(nullptr, &tb, rho, srho, iota, e1, nc, 32, c->stream);
-            if (!rc) rc = ensure_prim(c, tb);
-            tb = c->prim_bytes;
-            if (!rc) rc = prim_sort_pairs_u32(c->prim_tmp, &tb, rho, srho, iota, e1, nc, 32, c->stream);
-        }
-        if (!rc) rc = launch_br_gather_keys(keys, e1, nc, key1, c->stream);
-        if (!rc) rc = sort_u64(c, key1, skeys, e1, e2, nc);
-        // runs: heads, starts, lengths padded to 4 and their scan
-        if (!rc) rc = launch_run_heads(skeys, nc, heads, c->stream);
-        if (!rc) rc = ivox_scan(c, heads, runid, nc);
-        if (!rc && hipMemsetAsync(nruns_dev, 0, 8, c->stream) != hipSuccess) rc = LIVO_E_HIP;
-        if (!rc) rc = launch_dyn_runs(heads, runid, nc, starts, nruns_dev, c->stream);
+        rc = launch_br_count(c->gpts, M, c->gorg, bh, brmax, cnt, L.nruns, c->stream, ch.x0, ch.x1);
+        if (!rc) rc = scan_u32(c, cnt, off, M);
+        if (!rc)
+            rc = launch_br_emit(c->gpts, M, c->gorg, bh, brmax, off, L.rho, L.keys, L.pt, L.iota, c->stream, ch.x0, ch.x1);
+        if (!rc) rc = sort_u32(c, L.rho, L.srho, L.iota, L.e1, nc, 32);
+        if (!rc) rc = launch_br_gather_keys(L.keys, L.e1, nc, L.key1, c->stream);
+        if (!rc) rc = sort_u64(c, L.key1, L.skeys, L.e1, L.e2, nc);
+        // runs: heads, starts, lengths padded to 4 and their scan (runid, pstart: in rho and
+        // srho, dead after the first sort)
+        if (!rc) rc = launch_run_heads(L.skeys, nc, L.heads, c->stream);
+        if (!rc) rc = scan_u32(c, L.heads, L.runid, nc);
+        if (!rc && hipMemsetAsync(L.nruns, 0, 8, c->stream) != hipSuccess) rc = LIVO_E_HIP;
+        if (!rc) rc = launch_dyn_runs(L.heads, L.runid, nc, L.starts, L.nruns, c->stream);
         unsigned long long runs = 0;
-        if (!rc && hipMemcpyAsync(&runs, nruns_dev, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LIVO_E_HIP;
+        if (!rc && hipMemcpyAsync(&runs, L.nruns, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LIVO_E_HIP;
         if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
         if (rc) break;
         if (runs == 0) continue;
-        rc = launch_run_plen(starts, (int64_t)runs, plen, c->stream);
-        if (!rc) rc = ivox_scan(c, plen, pstart, (int64_t)runs);
-        uint32_t tail[2] = {0u, 0u};
-        if (!rc && (hipMemcpyAsync(&tail[0], pstart + runs - 1, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipMemcpyAsync(&tail[1], plen + runs - 1, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess))
-            rc = LIVO_E_HIP;
+        rc = launch_run_plen(L.starts, (int64_t)runs, L.plen, c->stream);
+        if (!rc) rc = scan_u32(c, L.plen, L.pstart, (int64_t)runs);
+        ScanCount padded;
+        if (!rc) rc = padded.read(L.pstart, L.plen, (int64_t)runs, c->stream);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LIVO_E_HIP;
         if (rc) break;
-        const int64_t words = (int64_t)tail[0] + tail[1];
+        const int64_t words = padded.sum();
         if (words < nc || words >= (int64_t)0xFFFFFFFFll) {
             rc = LIVO_E_RANGE;
             break;
@@ -2378,8 +2343,8 @@ static int build_ball_runs_idx(livo_ctx* c, int64_t M, float r5, float bh, float
             trip_cap = ncap;
             if (rc) break;
         }
-        rc = launch_run_place(e2, pt, heads, runid, starts, pstart, nc, c->bpts + base, c->stream);
-        if (!rc) rc = launch_run_trip(skeys, starts, pstart, (int64_t)runs, (unsigned long long)base,
+        rc = launch_run_place(L.e2, L.pt, L.heads, L.runid, L.starts, L.pstart, nc, c->bpts + base, c->stream);
+        if (!rc) rc = launch_run_trip(L.skeys, L.starts, L.pstart, (int64_t)runs, (unsigned long long)base,
                                       trip + runs_total, c->stream);
         if (rc) break;
         base += words;
@@ -2562,11 +2527,10 @@ int livo_knn(livo_ctx* c, const float* q, int64_t n, int32_t k, int32_t* idx, fl
     int rc = ensure_slot(c);
     if (rc) return rc;
     const size_t qb = (size_t)n * 4 * sizeof(float), rb = (size_t)n * sizeof(NNRec);
-    rc = ensure_scratch(c, qb + rb + 256);
+    rc = ensure_scratch(c, carve_bytes(knn_query_layout<NNRec>, (size_t)n));
     if (rc) return rc;
-    char* base = (char*)c->scratch;
-    float* dq = (float*)base;
-    NNRec* dr = (NNRec*)(base + ((qb + 255) & ~(size_t)255));
+    Carve cv{(char*)c->scratch};
+    const KnnQuery<NNRec> Q = knn_query_layout<NNRec>(cv, (size_t)n);
     std::vector<float> hq((size_t)n * 4);
     for (int64_t i = 0; i < n; i++) {
         hq[4 * i] = q[3 * i]; hq[4 * i + 1] = q[3 * i + 1]; hq[4 * i + 2] = q[3 * i + 2]; hq[4 * i + 3] = 0.f;
@@ -2576,8 +2540,8 @@ int livo_knn(livo_ctx* c, const float* q, int64_t n, int32_t k, int32_t* idx, fl
     c->h_slots[0] = zero;
     HsJob& j = c->h_jobs[0];
     j = HsJob{};
-    j.pts = dq; j.nn = dr; j.slot = c->d_slots; j.n = (int32_t)n; j.nblk = 0;
-    HIP_TRY(hipMemcpyAsync(dq, hq.data(), qb, hipMemcpyHostToDevice, c->stream));
+    j.pts = Q.q; j.nn = Q.rec; j.slot = c->d_slots; j.n = (int32_t)n; j.nblk = 0;
+    HIP_TRY(hipMemcpyAsync(Q.q, hq.data(), qb, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_jobs, c->h_jobs, sizeof(HsJob), hipMemcpyHostToDevice, c->stream));
     rc = ensure_replay(c, n);
@@ -2588,7 +2552,7 @@ int livo_knn(livo_ctx* c, const float* q, int64_t n, int32_t k, int32_t* idx, fl
     rc = knn_pass(kp, 1, n, c->stream);
     if (rc) return rc;
     std::vector<NNRec> hr((size_t)n);
-    HIP_TRY(hipMemcpyAsync(hr.data(), dr, rb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hr.data(), Q.rec, rb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n; i++)
         for (int t = 0; t < k; t++) {
@@ -2686,15 +2650,15 @@ static void release_scan_buf(livo_ctx* c, ScanBuf& s) {
     s = ScanBuf{};
 }
 
-// Upload scratch of N points: [keys | sorted keys | iota | perm | bounds], then
-// (livo_scan_upload) the packed source points.
-static size_t up_tmp_bytes(int64_t N) { return (size_t)N * (4 + 4 + 4 + 4) + 256; }
+// Upload scratch of N points: scan_build_layout's arrays, then (livo_scan_upload,
+// livo_scan_upload_async) the packed source points (scan_upload_layout).
+static size_t up_tmp_bytes(int64_t N, bool src = false) { return carve_bytes(scan_upload_layout, (size_t)N, src); }
 static int ensure_up_tmp(livo_ctx* c, size_t bytes) {
     return ensure_dev_bytes(&c->up_tmp, &c->up_tmp_bytes, bytes);  // (synchronous: no upload is in flight)
 }
 
-// Where a scan is built: the stream, the sort scratch (keys, sorted keys, iota,
-// perm, bounds: up_tmp_bytes) and the rocPRIM scratch, grown on demand.
+// Where a scan is built: the stream, the sort scratch (up_tmp_bytes) and the
+// rocPRIM scratch, grown on demand.
 struct UpTarget {
     hipStream_t st;
     void** tmp;
@@ -2708,31 +2672,19 @@ struct UpTarget {
 // enqueues; the caller synchronises or records an event.
 static int scan_build_on(const UpTarget& U, const float* d_src, int stride, int64_t N, ScanBuf& s) {
     if (N <= 0) return LIVO_OK;
-    char* base = (char*)*U.tmp;
-    auto* codes = (uint32_t*)base;
-    auto* scodes = codes + N;
-    auto* iota = scodes + N;
-    auto* perm = iota + N;
-    auto* mm = (unsigned*)(((uintptr_t)(perm + N) + 15) & ~(uintptr_t)15);
+    Carve k{(char*)*U.tmp};
+    const ScanBuild L = scan_build_layout(k, (size_t)N, 6);
     int rc = LIVO_OK;
     // bounds start at (+max, -max) in the order-preserving encoding
-    if (hipMemsetD32Async((hipDeviceptr_t)mm, 0xFFFFFFFFu, 3, U.st) != hipSuccess ||
-        hipMemsetD32Async((hipDeviceptr_t)(mm + 3), 0u, 3, U.st) != hipSuccess)
+    if (hipMemsetD32Async((hipDeviceptr_t)L.bounds, 0xFFFFFFFFu, 3, U.st) != hipSuccess ||
+        hipMemsetD32Async((hipDeviceptr_t)(L.bounds + 3), 0u, 3, U.st) != hipSuccess)
         rc = LIVO_E_HIP;
-    if (!rc) rc = launch_fe_minmax(d_src, N, stride, mm, U.st);
-    if (!rc) rc = launch_fe_morton(d_src, N, stride, mm, morton_scale(), codes, iota, U.st);
-    if (!rc) {
-        size_t tb = 0;
-        rc = prim_sort_pairs_u32(nullptr, &tb, codes, scodes, iota, perm, N, 27, U.st);
-        if (!rc && tb > *U.prim_bytes) {
-            if (hipStreamSynchronize(U.st) != hipSuccess) rc = LIVO_E_HIP;
-            if (!rc) rc = ensure_dev_bytes(U.prim, U.prim_bytes, tb);
-        }
-        tb = *U.prim_bytes;
-        if (!rc) rc = prim_sort_pairs_u32(*U.prim, &tb, codes, scodes, iota, perm, N, 27, U.st);
-    }
-    if (!rc) rc = launch_fe_gather(d_src, N, stride, perm, s.pts, s.d_iperm, U.st);
-    if (!rc && (hipMemcpyAsync(s.d_perm, perm, (size_t)N * 4, hipMemcpyDeviceToDevice, U.st) != hipSuccess ||
+    if (!rc) rc = launch_fe_minmax(d_src, N, stride, L.bounds, U.st);
+    if (!rc) rc = launch_fe_morton(d_src, N, stride, L.bounds, morton_scale(), L.keys, L.iota, U.st);
+    // (the stream drained before its rocPRIM scratch grows: an earlier build may still sort in it)
+    if (!rc) rc = sort_u32_on(U.st, U.prim, U.prim_bytes, true, L.keys, L.skeys, L.iota, L.svals, N, 27);
+    if (!rc) rc = launch_fe_gather(d_src, N, stride, L.svals, s.pts, s.d_iperm, U.st);
+    if (!rc && (hipMemcpyAsync(s.d_perm, L.svals, (size_t)N * 4, hipMemcpyDeviceToDevice, U.st) != hipSuccess ||
                 hipMemsetAsync(s.nn, 0, (size_t)N * sizeof(NNRec), U.st) != hipSuccess ||
                 hipMemsetAsync(s.pstate, 0, (size_t)N, U.st) != hipSuccess))
         rc = LIVO_E_HIP;
@@ -2779,10 +2731,10 @@ int livo_scan_upload(livo_ctx* c, const float* xyz, int64_t N, int64_t stride_by
     // scratch, then Morton-ordered on the device (scan_create_device)
     float* d_src = nullptr;
     if (N > 0) {
-        const size_t off = (up_tmp_bytes(N) + 255) & ~(size_t)255;
-        int rc = ensure_up_tmp(c, off + (size_t)N * 3 * sizeof(float));
+        int rc = ensure_up_tmp(c, up_tmp_bytes(N, true));
         if (rc) return rc;
-        d_src = (float*)((char*)c->up_tmp + off);
+        Carve k{(char*)c->up_tmp};
+        d_src = scan_upload_layout(k, (size_t)N, true).src;
         float* h = nullptr;
         const bool packed = stride_bytes == (int64_t)(3 * sizeof(float));
         if (!packed) {
@@ -2815,10 +2767,10 @@ int livo_scan_upload_async(livo_ctx* c, const float* xyz, int64_t N, int64_t str
         c->up_stream = nullptr;
         return LIVO_E_HIP;
     }
-    const size_t off = (up_tmp_bytes(N) + 255) & ~(size_t)255, bytes = (size_t)N * 3 * sizeof(float);
-    if (off + bytes > c->aup_tmp_bytes) {  // (growing: the uploads queued on it finish first)
+    const size_t need = up_tmp_bytes(N, true), bytes = (size_t)N * 3 * sizeof(float);
+    if (need > c->aup_tmp_bytes) {  // (growing: the uploads queued on it finish first)
         if (hipStreamSynchronize(c->up_stream) != hipSuccess) return LIVO_E_HIP;
-        const int rc = ensure_dev_bytes(&c->aup_tmp, &c->aup_tmp_bytes, off + bytes);
+        const int rc = ensure_dev_bytes(&c->aup_tmp, &c->aup_tmp_bytes, need);
         if (rc) return rc;
     }
     // a pinned staging buffer whose last copy is done (the ring's oldest)
@@ -2849,7 +2801,8 @@ int livo_scan_upload_async(livo_ctx* c, const float* xyz, int64_t N, int64_t str
         release_scan_buf(c, s);
         return LIVO_E_HIP;
     }
-    float* d_src = (float*)((char*)c->aup_tmp + off);
+    Carve k{(char*)c->aup_tmp};
+    float* d_src = scan_upload_layout(k, (size_t)N, true).src;
     if (hipMemcpyAsync(d_src, P.h, bytes, hipMemcpyHostToDevice, c->up_stream) != hipSuccess ||
         hipEventRecord(P.copied, c->up_stream) != hipSuccess)
         rc = LIVO_E_HIP;
@@ -2960,11 +2913,9 @@ static int upload_batch_chunks(livo_ctx* c, const float* const* xyz, const int64
             continue;
         }
         if (tot > (int64_t)0xFFFFFFFF - kBlock) return LIVO_E_RANGE;  // (32-bit positions in the batch sort)
-        // build scratch (up_stream): [keys | sorted keys | iota | sorted iota | bounds (6 per scan)];
-        // the packed points in the staging buffer of this pass (cp_stream copies into it)
-        const size_t kb = (size_t)tot * 4, vb = (size_t)tot * 4;
-        const size_t mm_off = 2 * kb + 2 * vb;
-        const size_t tmp_need = mm_off + 6 * sizeof(unsigned) * kFeSegMax;
+        // build scratch (up_stream): scan_build_layout with 6 bounds per scan; the packed points
+        // in the staging buffer of this pass (cp_stream copies into it)
+        const size_t tmp_need = carve_bytes(scan_build_layout, (size_t)tot, (size_t)6 * kFeSegMax);
         const size_t bytes = (size_t)tot * 3 * sizeof(float);
         const int sl = c->bsrc_next;
         c->bsrc_next ^= 1;
@@ -2975,12 +2926,8 @@ static int upload_batch_chunks(livo_ctx* c, const float* const* xyz, const int64
             if (!rc) rc = ensure_dev_bytes(&c->bsrc[sl], &c->bsrc_bytes[sl], bytes);
             if (rc) return rc;
         }
-        char* base = (char*)c->aup_tmp;
-        auto* codes = (uint32_t*)base;
-        auto* scodes = (uint32_t*)(base + kb);
-        auto* iota = (uint32_t*)(base + 2 * kb);
-        auto* sorted = (uint32_t*)(base + 2 * kb + vb);
-        auto* mm = (unsigned*)(base + mm_off);
+        Carve cv{(char*)c->aup_tmp};
+        const ScanBuild L = scan_build_layout(cv, (size_t)tot, (size_t)6 * kFeSegMax);
         float* d_src = (float*)c->bsrc[sl];
         // the copy into this buffer waits for the build that last read it
         if (c->bsrc_used[sl] && hipStreamWaitEvent(c->cp_stream, c->bsrc_free[sl], 0) != hipSuccess) return LIVO_E_HIP;
@@ -3106,22 +3053,15 @@ static int upload_batch_chunks(livo_ctx* c, const float* const* xyz, const int64
             o += N[b0 + b];
         }
         // bounds start at +max (mins) and ~(-max) (maxes, stored inverted) in the order-preserving encoding
-        if (!rc && (hipMemsetD32Async((hipDeviceptr_t)mm, 0xFFFFFFFFu, 6 * kFeSegMax, c->up_stream) != hipSuccess))
+        if (!rc && (hipMemsetD32Async((hipDeviceptr_t)L.bounds, 0xFFFFFFFFu, 6 * kFeSegMax, c->up_stream) != hipSuccess))
             rc = LIVO_E_HIP;
-        if (!rc) rc = launch_fe_build_seg(d_src, S, m, max_n, mm, morton_scale(), codes, iota, c->up_stream);
+        if (!rc) rc = launch_fe_build_seg(d_src, S, m, max_n, L.bounds, morton_scale(), L.keys, L.iota, c->up_stream);
         int key_bits = 27;  // + the scan index's bits
         while ((1 << (key_bits - 27)) < m) key_bits++;
-        if (!rc) {
-            size_t tb = 0;
-            rc = prim_sort_pairs_u32(nullptr, &tb, codes, scodes, iota, sorted, tot, key_bits, c->up_stream);
-            if (!rc && tb > c->aup_prim_bytes) {
-                if (hipStreamSynchronize(c->up_stream) != hipSuccess) rc = LIVO_E_HIP;
-                if (!rc) rc = ensure_dev_bytes(&c->aup_prim, &c->aup_prim_bytes, tb);
-            }
-            tb = c->aup_prim_bytes;
-            if (!rc) rc = prim_sort_pairs_u32(c->aup_prim, &tb, codes, scodes, iota, sorted, tot, key_bits, c->up_stream);
-        }
-        if (!rc) rc = launch_fe_gather_seg(d_src, S, m, max_n, sorted, c->up_stream);
+        if (!rc)
+            rc = sort_u32_on(c->up_stream, &c->aup_prim, &c->aup_prim_bytes, true, L.keys, L.skeys, L.iota, L.svals, tot,
+                             key_bits);
+        if (!rc) rc = launch_fe_gather_seg(d_src, S, m, max_n, L.svals, c->up_stream);
         if (!rc && hipEventRecord(c->bsrc_free[sl], c->up_stream) != hipSuccess) rc = LIVO_E_HIP;
         c->bsrc_used[sl] = true;
         for (int32_t b = 0; b < m && !rc; b++)
@@ -3239,13 +3179,10 @@ int livo_h_share(livo_ctx* c, int32_t id, const livo_state* state, int search_en
     const int64_t N = s->n;
     // debug scratch: normvec N*4, world N*3, sel N; laserCloudOri compaction: flags N, pos N, ori N*3, corr N*4
     const bool want_ori = out && (out->ori_xyz || out->corr_normvec || out->n_ori);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nvb = al((size_t)N * 16), wb = al((size_t)N * 12), sb = al((size_t)N);
-    const size_t fb = want_ori ? al((size_t)N * 4) : 0, ob = want_ori ? al((size_t)N * 12) : 0,
-                 cb = want_ori ? al((size_t)N * 16) : 0;
-    rc = ensure_scratch(c, nvb + wb + sb + 2 * fb + ob + cb + 64);
+    rc = ensure_scratch(c, carve_bytes(hshare_dbg_layout, (size_t)N, want_ori));
     if (rc) return rc;
-    char* base = (char*)c->scratch;
+    Carve cv{(char*)c->scratch};
+    const HShareDbg D = hshare_dbg_layout(cv, (size_t)N, want_ori);
     rc = ensure_nn_coords(c, s, c->stream);  // (cached neighbours may be read: search_en 0, iVox queries out of range)
     if (rc) return rc;
     init_slot(c->h_slots[0], *state, *state, c->params.max_iterations);
@@ -3255,9 +3192,9 @@ int livo_h_share(livo_ctx* c, int32_t id, const livo_state* state, int search_en
     HsParams hp = make_hs_params(c);
     hp.force = search_en ? 1 : 0;
     const bool want_nv = out && out->normvec, want_sel = out && out->selected, want_w = out && out->world_xyz;
-    hp.dbg.normvec = (want_nv || want_ori) ? (float*)base : nullptr;
-    hp.dbg.world = want_w ? (float*)(base + nvb) : nullptr;
-    hp.dbg.sel = (want_sel || want_ori) ? (uint8_t*)(base + nvb + wb) : nullptr;
+    hp.dbg.normvec = (want_nv || want_ori) ? D.normvec : nullptr;
+    hp.dbg.world = want_w ? D.world : nullptr;
+    hp.dbg.sel = (want_sel || want_ori) ? D.sel : nullptr;
     if (search_en) {
         rc = ensure_replay(c, N);
         if (rc) return rc;
@@ -3279,25 +3216,19 @@ int livo_h_share(livo_ctx* c, int32_t id, const livo_state* state, int search_en
     if (rc) return rc;
     // laserCloudOri / corr_normvect: the effective points in the caller's order (:547-561)
     int64_t n_ori = 0;
-    float *d_ori = nullptr, *d_corr = nullptr;
     if (want_ori && N > 0) {
-        uint32_t* flags = (uint32_t*)(base + nvb + wb + sb);
-        uint32_t* pos = (uint32_t*)(base + nvb + wb + sb + fb);
-        d_ori = (float*)(base + nvb + wb + sb + 2 * fb);
-        d_corr = (float*)(base + nvb + wb + sb + 2 * fb + ob);
-        rc = launch_ori_flags(hp.dbg.sel, s->d_perm, N, flags, c->stream);
-        if (!rc) rc = ivox_scan(c, flags, pos, N);
-        if (!rc) rc = launch_ori_scatter(s->pts, hp.dbg.normvec, hp.dbg.sel, s->d_perm, pos, N, d_ori, d_corr, c->stream);
+        rc = launch_ori_flags(hp.dbg.sel, s->d_perm, N, D.flags, c->stream);
+        if (!rc) rc = scan_u32(c, D.flags, D.pos, N);
+        if (!rc) rc = launch_ori_scatter(s->pts, hp.dbg.normvec, hp.dbg.sel, s->d_perm, D.pos, N, D.ori, D.corr, c->stream);
+        ScanCount cnt;
+        if (!rc) rc = cnt.read(D.pos, D.flags, N, c->stream);
         if (rc) return rc;
-        uint32_t tail[2];
-        HIP_TRY(hipMemcpyAsync(&tail[0], pos + N - 1, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&tail[1], flags + N - 1, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        n_ori = (int64_t)tail[0] + tail[1];
+        n_ori = cnt.sum();
         if (out->ori_xyz && n_ori > 0)
-            HIP_TRY(hipMemcpyAsync(out->ori_xyz, d_ori, (size_t)n_ori * 12, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(out->ori_xyz, D.ori, (size_t)n_ori * 12, hipMemcpyDeviceToHost, c->stream));
         if (out->corr_normvec && n_ori > 0)
-            HIP_TRY(hipMemcpyAsync(out->corr_normvec, d_corr, (size_t)n_ori * 16, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(out->corr_normvec, D.corr, (size_t)n_ori * 16, hipMemcpyDeviceToHost, c->stream));
     }
     if (want_ori && out->n_ori) *out->n_ori = n_ori;
     // the last plane-pass block has reduced the sums into slot->red (hp.solve = 0)
@@ -3985,12 +3916,11 @@ int livo_ivox_knn(livo_ctx* c, const float* q, int64_t n, int32_t max_num, doubl
     int rc = ensure_slot(c);
     if (rc) return rc;
     const size_t qb = (size_t)n * 4 * sizeof(float), rb = (size_t)n * sizeof(NNRec);
-    rc = ensure_scratch(c, qb + rb + 256);
+    rc = ensure_scratch(c, carve_bytes(knn_query_layout<NNRec>, (size_t)n));
     if (!rc) rc = ensure_replay(c, n);
     if (rc) return rc;
-    char* base = (char*)c->scratch;
-    float* dq = (float*)base;
-    NNRec* dr = (NNRec*)(base + ((qb + 255) & ~(size_t)255));
+    Carve cv{(char*)c->scratch};
+    const KnnQuery<NNRec> Q = knn_query_layout<NNRec>(cv, (size_t)n);
     std::vector<float> hq((size_t)n * 4);
     for (int64_t i = 0; i < n; i++) {
         hq[4 * i] = q[3 * i]; hq[4 * i + 1] = q[3 * i + 1]; hq[4 * i + 2] = q[3 * i + 2]; hq[4 * i + 3] = 0.f;
@@ -3998,9 +3928,9 @@ int livo_ivox_knn(livo_ctx* c, const float* q, int64_t n, int32_t max_num, doubl
     std::memset(&c->h_slots[0], 0, sizeof(IekfSlot));
     HsJob& j = c->h_jobs[0];
     j = HsJob{};
-    j.pts = dq; j.nn = dr; j.slot = c->d_slots; j.n = (int32_t)n; j.nblk = 0;
-    HIP_TRY(hipMemcpyAsync(dq, hq.data(), qb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(dr, 0xFF, rb, c->stream));  // cnt = -1: left alone = nothing found
+    j.pts = Q.q; j.nn = Q.rec; j.slot = c->d_slots; j.n = (int32_t)n; j.nblk = 0;
+    HIP_TRY(hipMemcpyAsync(Q.q, hq.data(), qb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(Q.rec, 0xFF, rb, c->stream));  // cnt = -1: left alone = nothing found
     HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_jobs, c->h_jobs, sizeof(HsJob), hipMemcpyHostToDevice, c->stream));
     KnnParams kp = make_knn_params(c);
@@ -4013,7 +3943,7 @@ int livo_ivox_knn(livo_ctx* c, const float* q, int64_t n, int32_t max_num, doubl
     rc = launch_ivox_knn(kp, 1, n, false, c->iv.big_threads, c->stream);
     if (rc) return rc;
     std::vector<NNRec> hr((size_t)n);
-    HIP_TRY(hipMemcpyAsync(hr.data(), dr, rb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hr.data(), Q.rec, rb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < n; i++) {
         cnt[i] = rec_host_cnt(hr[i]);
@@ -4089,21 +4019,16 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
     if (N == 0) return LIVO_OK;
     int rc = ensure_slot(c);
     if (rc) return rc;
-    // scratch: ordered 2N x 16 B, flags 2N x 4, pos 2N x 4, cat N
-    const size_t ob = (size_t)N * 32, fb = (size_t)N * 8, cb = (size_t)N;
-    rc = ensure_scratch(c, ob + 2 * fb + cb + 1024);
+    rc = ensure_scratch(c, carve_bytes(map_incr_layout, (size_t)N));
     if (!rc) rc = ivox_ensure_src(c, N);
     if (rc) return rc;
-    char* base = (char*)c->scratch;
-    float* ordered = (float*)base;
-    uint32_t* flags = (uint32_t*)(base + ob);
-    uint32_t* pos = (uint32_t*)(base + ob + fb);
-    uint8_t* dcat = (uint8_t*)(base + ob + 2 * fb);
+    Carve cv{(char*)c->scratch};
+    const MapIncr W = map_incr_layout(cv, (size_t)N);
     rc = ensure_nn_coords(c, s, c->stream);  // (first: rebuilding skipped records takes the staging slot)
     if (rc) return rc;
     init_slot(c->h_slots[0], *state, *state, c->params.max_iterations);
     HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(flags, 0, fb, c->stream));
+    HIP_TRY(hipMemsetAsync(W.flags, 0, (size_t)N * 8, c->stream));
     MapIncrParams mp{};
     mp.pts = s->pts;
     mp.nn = s->nn;
@@ -4112,27 +4037,27 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
     mp.slot = c->d_slots;
     std::memcpy(mp.R_LI, c->params.R_LI, sizeof(mp.R_LI));
     std::memcpy(mp.t_LI, c->params.t_LI, sizeof(mp.t_LI));
-    mp.ordered = ordered;
-    mp.flags = flags;
-    mp.cat = cat ? dcat : nullptr;
+    mp.ordered = W.ordered;
+    mp.flags = W.flags;
+    mp.cat = cat ? W.cat : nullptr;
     mp.fs = fs;
     mp.n = (int32_t)N;
     mp.ekf_inited = ekf_inited ? 1 : 0;
     rc = launch_map_incr(mp, c->stream);
-    if (!rc) rc = ivox_scan(c, flags, pos, 2 * N);
-    if (!rc) rc = launch_compact(ordered, flags, pos, 2 * N, c->iv.src, c->stream);
+    if (!rc) rc = scan_u32(c, W.flags, W.pos, 2 * N);
+    if (!rc) rc = launch_compact(W.ordered, W.flags, W.pos, 2 * N, c->iv.src, c->stream);
+    ScanCount kept;
+    if (!rc) rc = kept.read(W.pos, W.flags, 2 * N, c->stream);
     if (rc) return rc;
-    uint32_t tail[3];  // pos[N], pos[2N-1], flags[2N-1]
-    HIP_TRY(hipMemcpyAsync(&tail[0], pos + N, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&tail[1], pos + 2 * N - 1, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&tail[2], flags + 2 * N - 1, 4, hipMemcpyDeviceToHost, c->stream));
+    uint32_t added = 0;  // pos[N]: the first half's count
+    HIP_TRY(hipMemcpyAsync(&added, W.pos + N, 4, hipMemcpyDeviceToHost, c->stream));
     std::vector<uint8_t> hcat;
     if (cat) {
         hcat.resize((size_t)N);
-        HIP_TRY(hipMemcpyAsync(hcat.data(), dcat, cb, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hcat.data(), W.cat, (size_t)N, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const int64_t total = (int64_t)tail[1] + tail[2], n_add = tail[0];
+    const int64_t total = kept.sum(), n_add = added;
     if (cat) {
         if (host_perm(s)) return LIVO_E_HIP;
         for (int64_t k = 0; k < N; k++) cat[s->perm[(size_t)k]] = hcat[(size_t)k];
@@ -4284,21 +4209,14 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
             int bits = 1;
             while (bits < 32 && ((int64_t)1 << bits) < cells) bits++;
             rc = launch_fe_leaf(F, c->stream);
-            if (!rc) {
-                size_t tb = 0;
-                rc = prim_sort_pairs_u32(nullptr, &tb, F.keys, skeys, F.iota, svals, n, bits, c->stream);
-                if (!rc) rc = ensure_prim(c, tb);
-                tb = c->prim_bytes;
-                if (!rc) rc = prim_sort_pairs_u32(c->prim_tmp, &tb, F.keys, skeys, F.iota, svals, n, bits, c->stream);
-            }
+            if (!rc) rc = sort_u32(c, F.keys, skeys, F.iota, svals, n, bits);
             if (!rc) rc = launch_fe_runs(F, c->stream);
-            if (!rc) rc = ivox_scan(c, F.flags, F.vid, n);
+            if (!rc) rc = scan_u32(c, F.flags, F.vid, n);
+            ScanCount vox;
+            if (!rc) rc = vox.read(F.vid, F.flags, n, c->stream);
             if (rc) return rc;
-            uint32_t tail[2];
-            HIP_TRY(hipMemcpyAsync(&tail[0], F.vid + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(&tail[1], F.flags + n - 1, 4, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
-            const int64_t n_vox = (int64_t)tail[0] + tail[1];
+            const int64_t n_vox = vox.sum();
             rc = launch_fe_starts(F, c->stream);
             if (!rc) rc = launch_fe_centroid(F, n_vox, c->stream);
             if (rc) return rc;
@@ -4636,7 +4554,7 @@ int livo_cloud_colorize(livo_ctx* c, int32_t scan_id, const livo_state* state, c
         HIP_TRY(hipMemsetAsync(R.ctr, 0, sizeof(ctr), c->stream));
         RC_TRY(launch_rgb_points(R, c->stream));
         if (compact) {
-            RC_TRY(ivox_scan(c, R.blk_cnt, d_off, nblk));
+            RC_TRY(scan_u32(c, R.blk_cnt, d_off, nblk));
             RC_TRY(launch_rgb_scatter(R, c->stream));
         }
         HIP_TRY(hipMemcpyAsync(ctr, R.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
@@ -4716,7 +4634,7 @@ static int select_queue(livo_ctx* c, SelectStage& S, const uint8_t* img, bool em
     RC_TRY(launch_vis_score(V, c->stream));
     RC_TRY(launch_vis_flags(V, c->stream));
     if (emit) {  // (the table bounds the result: the records are written before their count is known)
-        RC_TRY(ivox_scan(c, V.flag, const_cast<uint32_t*>(V.slot), S.length));
+        RC_TRY(scan_u32(c, V.flag, const_cast<uint32_t*>(V.slot), S.length));
         RC_TRY(launch_vis_emit(V, c->stream));
     }
     return LIVO_OK;
@@ -5090,7 +5008,7 @@ static int match_queue(livo_ctx* c, MatchStage& M, const uint8_t* img, bool stor
     RC_TRY(launch_vm_cell(V, c->stream));
     RC_TRY(launch_vm_warp(V, c->stream));
     if (store) {  // (the cells bound the result: the survivors are written before their count is known)
-        RC_TRY(ivox_scan(c, V.keep, const_cast<uint32_t*>(V.slot), M.length));
+        RC_TRY(scan_u32(c, V.keep, const_cast<uint32_t*>(V.slot), M.length));
         RC_TRY(launch_vm_scatter(V, c->stream));
     }
     return LIVO_OK;
