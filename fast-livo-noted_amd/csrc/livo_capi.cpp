@@ -23,25 +23,18 @@
 
 #include "host_layouts.h"
 #include "livo_internal.h"
+#include "upload_plan.h"
 
 using namespace livo;
 
 namespace {
 
-struct ScanBuf {
+// A resident scan: its device arrays (ScanArrays, upload_plan.h) and its state.
+struct ScanBuf : ScanArrays {
     bool used = false;
     int64_t n = 0;
     int32_t nblk = 0;
-    float* pts = nullptr;  // n x 4
-    NNRec* nn = nullptr;   // neighbour records (Nearest_Points cache)
-    int32_t* d_perm = nullptr;  // stored (Morton) position -> caller's point index
-    std::vector<int32_t> perm;  // the same on the host, fetched on first use (host_perm)
-    int32_t* d_iperm = nullptr; // caller's point index -> stored position
-    double* partial = nullptr;  // nblk x kIkCols (the A-path uses kRedCols of each)
-    float* plane = nullptr;     // N x 4: planes of the cached neighbours (k_hshare)
-    uint8_t* pstate = nullptr;  // N: plane state (0: not fitted since the neighbours changed)
-    double* ikrows = nullptr;   // IKFoM few-point rows (nblk x kIkFewRows x 13)
-    uint32_t* ikcnt = nullptr;  // per block
+    std::vector<int32_t> perm;  // d_perm on the host, fetched on first use (host_perm)
     bool searched = false;      // a search has filled the neighbour cache
     bool nn_compact = false;    // a fused batch may have stored hot-only records (kRecNoXyz): ensure_nn_coords
     bool nn_lazy = false;       // the last fused search skipped records: ensure_nn_records rebuilds them ...
@@ -99,8 +92,7 @@ static int image_stage(DevImage& m, const uint8_t* host, size_t bytes, hipStream
 }
 
 static void free_scan_buf(ScanBuf& s) {
-    dev_free(s.pts); dev_free(s.nn); dev_free(s.partial); dev_free(s.d_perm); dev_free(s.d_iperm);
-    dev_free(s.plane); dev_free(s.pstate); dev_free(s.ikrows); dev_free(s.ikcnt);
+    scan_arrays(s, s.cap, [](auto*& p, size_t) { dev_free(p); });
     if (s.ready) (void)hipEventDestroy(s.ready);
     s.ready = nullptr;
 }
@@ -303,6 +295,81 @@ struct BatchLane {
 
 // pinned staging buffers of livo_scan_upload_async (two batches of 8 ahead)
 constexpr int kPinRing = 16;
+// A stream / an event created on first use (null again if that fails).
+static bool lazy_stream(hipStream_t* s) {
+    if (*s || hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess) return true;
+    *s = nullptr;
+    return false;
+}
+static bool lazy_event(hipEvent_t* e) {
+    if (*e || hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess) return true;
+    *e = nullptr;
+    return false;
+}
+struct PinSlot {
+    float* h = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;  // the last copy out of h
+    bool inflight = false;        // such a copy was enqueued and not yet waited for (pin_take, pin_sent)
+};
+
+// What the asynchronous uploads keep.  livo_scan_upload_async copies and builds
+// on `up`, out of a ring of pinned staging buffers (each reused once the copy
+// out of it is done).  livo_scan_upload_batch_async copies on `cp` into two
+// alternating device staging buffers, so batch k+1's copy runs beside batch k's
+// build on `up` (Src::copied gates the build, Src::free the next copy into the
+// same buffer).  Both build in tmp and sort in prim.
+struct UploadDev {
+    hipStream_t up = nullptr, cp = nullptr;
+    void* tmp = nullptr;  // Morton keys, sort buffers, bounds (single scans: then the packed points)
+    size_t tmp_bytes = 0;
+    void* prim = nullptr;  // rocPRIM scratch
+    size_t prim_bytes = 0;
+    PinSlot pin[kPinRing];
+    int pin_next = 0;
+    struct Src {
+        void* p = nullptr;
+        size_t bytes = 0;
+        hipEvent_t copied = nullptr, free = nullptr;
+        bool used = false;  // `free` has been recorded
+    } src[2];
+    int src_next = 0;
+
+    // The upload stream and (batch) the copy stream and the staging buffers'
+    // events: whatever is missing is created.
+    // (the builds on a high-priority stream were slower: 3.8k vs 11.8k updates/s
+    // with uploads, DESIGN.md section 10)
+    int streams(bool batch) {
+        bool ok = lazy_stream(&up);
+        if (batch) {
+            ok = ok && lazy_stream(&cp);
+            for (Src& s : src) ok = ok && lazy_event(&s.copied) && lazy_event(&s.free);
+        }
+        return ok ? LIVO_OK : LIVO_E_HIP;
+    }
+    // Every queued upload done: both streams are waited for, whatever the first answers.
+    int drain() {
+        const bool a = !cp || hipStreamSynchronize(cp) == hipSuccess;
+        const bool b = !up || hipStreamSynchronize(up) == hipSuccess;
+        return a && b ? LIVO_OK : LIVO_E_HIP;
+    }
+    void destroy() {
+        (void)drain();
+        for (Src& s : src) {
+            if (s.p) (void)hipFree(s.p);
+            if (s.copied) (void)hipEventDestroy(s.copied);
+            if (s.free) (void)hipEventDestroy(s.free);
+        }
+        if (tmp) (void)hipFree(tmp);
+        if (prim) (void)hipFree(prim);
+        for (PinSlot& P : pin) {
+            if (P.h) (void)hipHostFree(P.h);
+            if (P.copied) (void)hipEventDestroy(P.copied);
+        }
+        if (cp) (void)hipStreamDestroy(cp);
+        if (up) (void)hipStreamDestroy(up);
+    }
+};
 
 struct livo_ctx {
     int device = 0;
@@ -391,31 +458,7 @@ struct livo_ctx {
     // upload scratch: Morton keys, sort buffers, bounds and the packed source points
     void* up_tmp = nullptr;
     size_t up_tmp_bytes = 0;
-    // livo_scan_upload_async: its own stream, scratch and rocPRIM scratch, and a
-    // ring of pinned staging buffers (each reused once the copy out of it is done)
-    hipStream_t up_stream = nullptr;
-    void* aup_tmp = nullptr;
-    size_t aup_tmp_bytes = 0;
-    void* aup_prim = nullptr;
-    size_t aup_prim_bytes = 0;
-    struct PinSlot {
-        float* h = nullptr;
-        size_t bytes = 0;
-        hipEvent_t copied = nullptr;
-        bool inflight = false;
-    } pin[kPinRing];
-    int pin_next = 0;
-    // livo_scan_upload_batch_async: the copies on a stream of their own into two
-    // alternating device staging buffers, so batch k+1's copy runs beside batch
-    // k's build on up_stream (bsrc_copied gates the build, bsrc_free the next
-    // copy into the same buffer)
-    hipStream_t cp_stream = nullptr;
-    void* bsrc[2] = {nullptr, nullptr};
-    size_t bsrc_bytes[2] = {0, 0};
-    hipEvent_t bsrc_copied[2] = {nullptr, nullptr};
-    hipEvent_t bsrc_free[2] = {nullptr, nullptr};
-    bool bsrc_used[2] = {false, false};
-    int bsrc_next = 0;
+    UploadDev up;  // livo_scan_upload_async, livo_scan_upload_batch_async: streams, scratch, staging
     // one slot and one job: the scratch of the single-scan entry points (ensure_slot)
     IekfSlot* d_slots = nullptr;
     // batches in flight (livo_iekf_update_batch_submit): lane 0 also carries
@@ -699,14 +742,6 @@ static HsParams make_hs_params(livo_ctx* c) {
     hp.force = -1;
     hp.keypts = c->gpts;
     return hp;
-}
-
-// doubles of a scan's block-partial buffer: the plane pass (kIkCols per
-// kBlock * kPtsPerThread points) or the fused evaluation (kRedCols per kEvalBlock)
-static size_t partial_doubles(int64_t N) {
-    const int64_t a = std::max<int64_t>(1, (N + kBlock * kPtsPerThread - 1) / (kBlock * kPtsPerThread)) * kIkCols;
-    const int64_t b = std::max<int64_t>(1, (N + kEvalBlock - 1) / kEvalBlock) * kRedCols;
-    return (size_t)std::max(a, b);
 }
 
 static void fill_job(HsJob& j, ScanBuf& s, IekfSlot* slot) {
@@ -2016,24 +2051,10 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (int k = 0; k < kMaxGroups - 1; k++)  // batches never collected: let them finish
         if (c->xstream[k]) (void)hipStreamSynchronize(c->xstream[k]);
-    if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
-    if (c->cp_stream) (void)hipStreamSynchronize(c->cp_stream);
-    for (int k = 0; k < 2; k++) {
-        if (c->bsrc[k]) (void)hipFree(c->bsrc[k]);
-        if (c->bsrc_copied[k]) (void)hipEventDestroy(c->bsrc_copied[k]);
-        if (c->bsrc_free[k]) (void)hipEventDestroy(c->bsrc_free[k]);
-    }
-    if (c->cp_stream) (void)hipStreamDestroy(c->cp_stream);
+    c->up.destroy();  // (waits for the uploads still queued)
     for (auto& s : c->scans) free_scan_buf(s);
     for (auto& s : c->spare) free_scan_buf(s);
     if (c->up_tmp) (void)hipFree(c->up_tmp);
-    if (c->aup_tmp) (void)hipFree(c->aup_tmp);
-    if (c->aup_prim) (void)hipFree(c->aup_prim);
-    for (auto& P : c->pin) {
-        if (P.h) (void)hipHostFree(P.h);
-        if (P.copied) (void)hipEventDestroy(P.copied);
-    }
-    if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
     ivox_free(c->iv);
     dyn_free(c->dyn);
     if (c->fe_buf) (void)hipFree(c->fe_buf);
@@ -2581,11 +2602,7 @@ static int32_t register_scan(livo_ctx* c, const ScanBuf& s) {
 // default 8192): a hipFree synchronises the whole device, so freeing one while
 // a farm's batches and uploads are in flight stalled the pipeline (a 12.9 ms
 // upload call; the farm with uploads at 5.4k instead of 12.4k updates/s).
-static size_t scan_buf_bytes(int64_t cap) {
-    const int64_t cblk = std::max<int64_t>(1, (cap + kBlock * kPtsPerThread - 1) / (kBlock * kPtsPerThread));
-    return (size_t)cap * (16 + sizeof(NNRec) + 4 + 4 + 16 + 1) + partial_doubles(cap) * 8 +
-           (size_t)cblk * (kIkFewRows * 13 * 8 + 4);
-}
+// (a scan's arrays and their bytes: scan_arrays, scan_buf_bytes, upload_plan.h)
 static size_t spare_budget() {
     static const size_t b = [] {
         const char* e = std::getenv("LIVO_SPARE_MB");
@@ -2604,30 +2621,20 @@ static int alloc_scan_buf(livo_ctx* c, ScanBuf& s, int64_t N) {
         s = c->spare[best];
         c->spare.erase(c->spare.begin() + best);
     } else {
-        const int64_t cap = N;
-        const int32_t cblk = (int32_t)std::max<int64_t>(1, (cap + kBlock * kPtsPerThread - 1) / (kBlock * kPtsPerThread));
         s = ScanBuf{};
         int rc = 0;
-        rc |= dev_alloc(&s.pts, (size_t)cap * 4);
-        rc |= dev_alloc(&s.nn, (size_t)cap);
-        rc |= dev_alloc(&s.partial, partial_doubles(cap));
-        rc |= dev_alloc(&s.d_perm, (size_t)cap);
-        rc |= dev_alloc(&s.d_iperm, (size_t)cap);
-        rc |= dev_alloc(&s.plane, (size_t)cap * 4);
-        rc |= dev_alloc(&s.pstate, (size_t)cap);
-        rc |= dev_alloc(&s.ikrows, (size_t)cblk * kIkFewRows * 13);
-        rc |= dev_alloc(&s.ikcnt, (size_t)cblk);
+        scan_arrays(s, N, [&](auto*& p, size_t count) { rc |= dev_alloc(&p, count); });
         if (rc) {
             free_scan_buf(s);
             return LIVO_E_OOM;
         }
-        s.cap = cap;
+        s.cap = N;
     }
     s.used = true;
     s.searched = false;
     s.nn_compact = s.nn_lazy = false;
     s.n = N;
-    s.nblk = (int32_t)std::max<int64_t>(1, (N + kBlock * kPtsPerThread - 1) / (kBlock * kPtsPerThread));
+    s.nblk = (int32_t)scan_blocks(N);
     s.pending = false;
     s.perm.clear();
     return LIVO_OK;
@@ -2721,11 +2728,17 @@ static void pack_xyz(const float* xyz, int64_t N, int64_t stride_bytes, float* o
     for (int64_t i = 0; i < N; i++) std::memcpy(out + 3 * i, base + i * stride_bytes, 3 * sizeof(float));
 }
 
-int livo_scan_upload(livo_ctx* c, const float* xyz, int64_t N, int64_t stride_bytes, int32_t* scan_id) {
-    if (!c || !scan_id || N < 0 || (N > 0 && !xyz)) return LIVO_E_INVALID;
+// What every upload entry point checks of a scan's size and stride (0: packed x, y, z).
+static int upload_args(int64_t N, int64_t& stride_bytes) {
+    if (N < 0) return LIVO_E_INVALID;
     if (N > (int64_t)0x7FFFFFFF - kBlock) return LIVO_E_RANGE;
     if (stride_bytes == 0) stride_bytes = 3 * sizeof(float);
-    if (stride_bytes < (int64_t)(3 * sizeof(float))) return LIVO_E_INVALID;
+    return stride_bytes < (int64_t)(3 * sizeof(float)) ? LIVO_E_INVALID : LIVO_OK;
+}
+
+int livo_scan_upload(livo_ctx* c, const float* xyz, int64_t N, int64_t stride_bytes, int32_t* scan_id) {
+    if (!c || !scan_id || (N > 0 && !xyz)) return LIVO_E_INVALID;
+    RC_TRY(upload_args(N, stride_bytes));
     if (set_device(c)) return LIVO_E_HIP;
     // the caller's points packed to x, y, z, copied to HBM behind the upload
     // scratch, then Morton-ordered on the device (scan_create_device)
@@ -2751,37 +2764,14 @@ int livo_scan_upload(livo_ctx* c, const float* xyz, int64_t N, int64_t stride_by
     return scan_create_device(c, d_src, 3, N, scan_id);
 }
 
-// livo_scan_upload without waiting: the points go through a pinned staging
-// buffer (the caller's array is free again on return) and are copied and
-// Morton-ordered on the context's upload stream, beside whatever the batch
-// lanes run; the scan's `ready` event gates its users (batch_enqueue waits for
-// it on the device, every other call through get_scan on the host).
-int livo_scan_upload_async(livo_ctx* c, const float* xyz, int64_t N, int64_t stride_bytes, int32_t* scan_id) {
-    if (!c || !scan_id || N < 0 || (N > 0 && !xyz)) return LIVO_E_INVALID;
-    if (N > (int64_t)0x7FFFFFFF - kBlock) return LIVO_E_RANGE;
-    if (stride_bytes == 0) stride_bytes = 3 * sizeof(float);
-    if (stride_bytes < (int64_t)(3 * sizeof(float))) return LIVO_E_INVALID;
-    if (N == 0) return livo_scan_upload(c, xyz, N, stride_bytes, scan_id);
-    if (set_device(c)) return LIVO_E_HIP;
-    if (!c->up_stream && hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking) != hipSuccess) {
-        c->up_stream = nullptr;
-        return LIVO_E_HIP;
-    }
-    const size_t need = up_tmp_bytes(N, true), bytes = (size_t)N * 3 * sizeof(float);
-    if (need > c->aup_tmp_bytes) {  // (growing: the uploads queued on it finish first)
-        if (hipStreamSynchronize(c->up_stream) != hipSuccess) return LIVO_E_HIP;
-        const int rc = ensure_dev_bytes(&c->aup_tmp, &c->aup_tmp_bytes, need);
-        if (rc) return rc;
-    }
-    // a pinned staging buffer whose last copy is done (the ring's oldest)
-    livo_ctx::PinSlot& P = c->pin[c->pin_next];
-    c->pin_next = (c->pin_next + 1) % kPinRing;
+// The ring's oldest pinned staging buffer, the copy last sent out of it done,
+// grown to `bytes`.
+static int pin_take(UploadDev& U, size_t bytes, PinSlot** out) {
+    PinSlot& P = U.pin[U.pin_next];
+    U.pin_next = (U.pin_next + 1) % kPinRing;
     if (P.inflight && hipEventSynchronize(P.copied) != hipSuccess) return LIVO_E_HIP;
     P.inflight = false;
-    if (!P.copied && hipEventCreateWithFlags(&P.copied, hipEventDisableTiming) != hipSuccess) {
-        P.copied = nullptr;
-        return LIVO_E_HIP;
-    }
+    if (!lazy_event(&P.copied)) return LIVO_E_HIP;
     if (bytes > P.bytes) {
         if (P.h) (void)hipHostFree(P.h);
         P.h = nullptr;
@@ -2792,32 +2782,75 @@ int livo_scan_upload_async(livo_ctx* c, const float* xyz, int64_t N, int64_t str
         }
         P.bytes = bytes;
     }
-    pack_xyz(xyz, N, stride_bytes, P.h);
-    ScanBuf s;
-    int rc = alloc_scan_buf(c, s, N);
-    if (rc) return rc;
-    if (!s.ready && hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) != hipSuccess) {
-        s.ready = nullptr;
-        release_scan_buf(c, s);
-        return LIVO_E_HIP;
-    }
-    Carve k{(char*)c->aup_tmp};
-    float* d_src = scan_upload_layout(k, (size_t)N, true).src;
-    if (hipMemcpyAsync(d_src, P.h, bytes, hipMemcpyHostToDevice, c->up_stream) != hipSuccess ||
-        hipEventRecord(P.copied, c->up_stream) != hipSuccess)
-        rc = LIVO_E_HIP;
-    P.inflight = rc == LIVO_OK;
-    const UpTarget U{c->up_stream, &c->aup_tmp, &c->aup_tmp_bytes, &c->aup_prim, &c->aup_prim_bytes};
-    if (!rc) rc = scan_build_on(U, d_src, 3, N, s);
-    if (!rc && hipEventRecord(s.ready, c->up_stream) != hipSuccess) rc = LIVO_E_HIP;
-    if (rc) {
-        (void)hipStreamSynchronize(c->up_stream);
-        release_scan_buf(c, s);
-        return rc;
-    }
-    s.pending = true;
-    *scan_id = register_scan(c, s);
+    *out = &P;
     return LIVO_OK;
+}
+// A copy out of P has been enqueued on st: the slot is in flight from here on,
+// whatever fails next (without the event the stream is waited for instead).
+static int pin_sent(PinSlot& P, hipStream_t st) {
+    P.inflight = true;
+    if (hipEventRecord(P.copied, st) == hipSuccess) return LIVO_OK;
+    (void)hipStreamSynchronize(st);
+    return LIVO_E_HIP;
+}
+
+// A scan about to be built by an asynchronous upload passes through three
+// steps.  pending_scan: its buffers and `ready` event, named in no launch yet.
+// publish_pending: the build is queued on st; the scan is registered, gated by
+// `ready` (s is empty afterwards).  drop_pending: the upload failed before
+// that; the upload streams are drained, then the buffers still held in s[]
+// return to the spare pool -- the only way back for a buffer that a queued
+// launch may name (release_scan_buf's rule).
+static int pending_scan(livo_ctx* c, int64_t N, ScanBuf& s) {
+    const int rc = alloc_scan_buf(c, s, N);
+    if (rc || lazy_event(&s.ready)) return rc;
+    release_scan_buf(c, s);
+    return LIVO_E_HIP;
+}
+static int publish_pending(livo_ctx* c, ScanBuf& s, hipStream_t st, int32_t* id) {
+    if (hipEventRecord(s.ready, st) != hipSuccess) return LIVO_E_HIP;
+    s.pending = true;
+    *id = register_scan(c, s);
+    s = ScanBuf{};
+    return LIVO_OK;
+}
+static void drop_pending(livo_ctx* c, ScanBuf* s, int count) {
+    (void)c->up.drain();
+    for (int k = 0; k < count; k++)
+        if (s[k].used) release_scan_buf(c, s[k]);
+}
+
+// livo_scan_upload without waiting: the points go through a pinned staging
+// buffer (the caller's array is free again on return) and are copied and
+// Morton-ordered on the context's upload stream, beside whatever the batch
+// lanes run; the scan's `ready` event gates its users (batch_enqueue waits for
+// it on the device, every other call through get_scan on the host).
+int livo_scan_upload_async(livo_ctx* c, const float* xyz, int64_t N, int64_t stride_bytes, int32_t* scan_id) {
+    if (!c || !scan_id || (N > 0 && !xyz)) return LIVO_E_INVALID;
+    RC_TRY(upload_args(N, stride_bytes));
+    if (N == 0) return livo_scan_upload(c, xyz, N, stride_bytes, scan_id);
+    UploadDev& U = c->up;
+    if (set_device(c) || U.streams(false)) return LIVO_E_HIP;
+    const size_t need = up_tmp_bytes(N, true), bytes = (size_t)N * 3 * sizeof(float);
+    if (need > U.tmp_bytes) {  // (growing: the uploads queued on it finish first)
+        HIP_TRY(hipStreamSynchronize(U.up));
+        RC_TRY(ensure_dev_bytes(&U.tmp, &U.tmp_bytes, need));
+    }
+    PinSlot* P = nullptr;
+    RC_TRY(pin_take(U, bytes, &P));
+    pack_xyz(xyz, N, stride_bytes, P->h);
+    ScanBuf s;
+    RC_TRY(pending_scan(c, N, s));
+    // nothing is queued above this line; below it every failure leaves through drop_pending
+    Carve k{(char*)U.tmp};
+    float* d_src = scan_upload_layout(k, (size_t)N, true).src;
+    int rc = hipMemcpyAsync(d_src, P->h, bytes, hipMemcpyHostToDevice, U.up) == hipSuccess ? pin_sent(*P, U.up)
+                                                                                             : LIVO_E_HIP;
+    const UpTarget T{U.up, &U.tmp, &U.tmp_bytes, &U.prim, &U.prim_bytes};
+    if (!rc) rc = scan_build_on(T, d_src, 3, N, s);
+    if (!rc) rc = publish_pending(c, s, U.up, scan_id);
+    if (rc) drop_pending(c, &s, 1);
+    return rc;
 }
 
 // True if p lies in page-locked host memory (livo_host_register, hipHostMalloc):
@@ -2852,247 +2885,195 @@ int livo_host_unregister(livo_ctx* c, void* p) {
     return hipHostUnregister(p) == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 
-// livo_scan_upload_async for a batch of scans in one pass: one staging copy
-// (or, from page-locked caller memory, one DMA per scan and no host copy), then
-// one bounds pass, one key pass, ONE stable sort of the whole batch (the scan
-// in the key's top bits) and one gather that also clears the neighbour
-// records, kFeSegMax scans at a time, on the upload stream.  Each scan is
-// stored exactly as livo_scan_upload stores it.
-static int upload_batch_chunks(livo_ctx* c, const float* const* xyz, const int64_t* N, int32_t n,
-                               int64_t stride_bytes, int32_t* scan_ids, int32_t* registered);
+// LIVO_UPLOAD_TRACE (development): the host time of a batch pass's phases to
+// stderr.  mark(k) ends phase k; a phase that is not marked takes no time.
+struct UploadTrace {
+    const bool on = std::getenv("LIVO_UPLOAD_TRACE") != nullptr;
+    double t[4] = {};
+    static double now_us() {
+        return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    }
+    void mark(int k) {
+        if (on) std::fill(t + k, t + 4, now_us());
+    }
+    void print(int m, bool direct) const {
+        if (on)
+            std::fprintf(stderr, "[upload] %d scans %s: pinned check %.1f us, ring wait %.1f, pack / copies %.1f, build %.1f\n",
+                         m, direct ? "direct" : "staged", t[1] - t[0], t[2] - t[1], t[3] - t[2], now_us() - t[3]);
+    }
+};
 
-// The scans are built in passes of kFeSegMax: a pass that fails releases the
-// scans the earlier passes of the same call registered, so a failed call leaves
-// no scan behind (scan_ids unspecified).
-int livo_scan_upload_batch_async(livo_ctx* c, const float* const* xyz, const int64_t* N, int32_t n,
-                                 int64_t stride_bytes, int32_t* scan_ids) {
-    int32_t registered = 0;
-    const int rc = upload_batch_chunks(c, xyz, N, n, stride_bytes, scan_ids, &registered);
-    if (rc)
-        for (int32_t b = 0; b < registered; b++) (void)livo_scan_release(c, scan_ids[b]);
+// livo_scan_upload_async for a batch of scans, kFeSegMax scans to a pass
+// (upload_pass, upload_plan.h; xyz, N and sb below are the pass's own scans):
+// one staging copy (pass_source), then one bounds pass, one key pass, ONE
+// stable sort of the whole pass (the scan in the key's top bits) and one
+// gather that also clears the neighbour records, on the upload stream
+// (pass_build); then the scans get their ids (pass_register).  Each scan is
+// stored exactly as livo_scan_upload stores it.
+
+// The pass's points packed into the staging buffer S, on the copy stream; the
+// upload stream waits for them.  The pass's scratch grows here, before anything
+// of the pass is queued.  *direct: read from the caller's page-locked arrays.
+static int pass_source(livo_ctx* c, const float* const* xyz, const int64_t* N, int64_t stride_bytes,
+                       const UploadPass& P, UploadDev::Src& S, UploadTrace& T, bool* direct) {
+    UploadDev& U = c->up;
+    // build scratch (up): scan_build_layout with 6 bounds per scan; the packed points in S (cp copies into it)
+    const size_t tmp_need = carve_bytes(scan_build_layout, (size_t)P.tot, (size_t)6 * kFeSegMax);
+    const size_t bytes = (size_t)P.tot * 3 * sizeof(float);
+    if (tmp_need > U.tmp_bytes || bytes > S.bytes) {  // (growing: the uploads in flight finish first)
+        RC_TRY(U.drain());
+        RC_TRY(ensure_dev_bytes(&U.tmp, &U.tmp_bytes, tmp_need));
+        RC_TRY(ensure_dev_bytes(&S.p, &S.bytes, bytes));
+    }
+    float* d_src = (float*)S.p;
+    // the copy into this buffer waits for the build that last read it
+    if (S.used) HIP_TRY(hipStreamWaitEvent(U.cp, S.free, 0));
+    // the points: straight from page-locked caller memory, else through a
+    // pinned staging buffer of the ring (the caller's arrays are free on return)
+    T.mark(0);
+    *direct = stride_bytes == (int64_t)(3 * sizeof(float));
+    for (int32_t b = 0; b < P.m && *direct; b++)
+        if (N[b] > 0 && !host_pinned_range(xyz[b], (size_t)N[b] * 3 * sizeof(float))) *direct = false;
+    T.mark(1);
+    int rc = LIVO_OK;
+    if (!*direct) {
+        PinSlot* H = nullptr;
+        RC_TRY(pin_take(U, bytes, &H));
+        T.mark(2);
+        // one host thread per scan (up to 8): a single thread's copy into pinned
+        // memory ran at ~9 GB/s (1.07 ms per 8 x 100k batch)
+        auto pack = [&](int32_t b) {
+            if (N[b] > 0) pack_xyz(xyz[b], N[b], stride_bytes, H->h + 3 * P.off[b]);
+        };
+        if (bytes < ((size_t)1 << 20) || P.m == 1) {
+            for (int32_t b = 0; b < P.m; b++) pack(b);
+        } else {
+            const int nt = std::min<int>(8, P.m);
+            std::vector<std::thread> th;
+            for (int t = 1; t < nt; t++)
+                th.emplace_back([&, t] {
+                    for (int32_t b = t; b < P.m; b += nt) pack(b);
+                });
+            for (int32_t b = 0; b < P.m; b += nt) pack(b);
+            for (auto& x : th) x.join();
+        }
+        T.mark(3);
+        HIP_TRY(hipMemcpyAsync(d_src, H->h, bytes, hipMemcpyHostToDevice, U.cp));
+        rc = pin_sent(*H, U.cp);
+    } else {
+        // page-locked caller arrays: one kernel reads them through their mapped
+        // device addresses (no DMA command per scan: a hipMemcpyAsync of one
+        // held the host 13-16 ms now and then inside a running farm); an
+        // array without a device mapping: DMA copies
+        FeSrc F{};
+        bool mapped = true;
+        for (int32_t b = 0; b < P.m; b++) {
+            F.off[b] = P.off[b];
+            F.n[b] = N[b];
+            void* dp = nullptr;
+            if (mapped && N[b] > 0 &&
+                (hipHostGetDevicePointer(&dp, const_cast<float*>(xyz[b]), 0) != hipSuccess || !dp)) {
+                (void)hipGetLastError();
+                mapped = false;
+            }
+            F.src[b] = (const float*)dp;
+        }
+        if (mapped) {
+            rc = launch_fe_copy_seg(F, P.m, P.max_n, d_src, U.cp);
+        } else {
+            for (int32_t b = 0; b < P.m && !rc; b++)
+                if (N[b] > 0 && hipMemcpyAsync(d_src + 3 * P.off[b], xyz[b], (size_t)N[b] * 3 * sizeof(float),
+                                               hipMemcpyHostToDevice, U.cp) != hipSuccess)
+                    rc = LIVO_E_HIP;
+        }
+        T.mark(3);  // (the copies' host time)
+    }
+    if (!rc && (hipEventRecord(S.copied, U.cp) != hipSuccess || hipStreamWaitEvent(U.up, S.copied, 0) != hipSuccess))
+        rc = LIVO_E_HIP;
     return rc;
 }
 
-static int upload_batch_chunks(livo_ctx* c, const float* const* xyz, const int64_t* N, int32_t n,
-                               int64_t stride_bytes, int32_t* scan_ids, int32_t* registered) {
-    if (!c || !xyz || !N || !scan_ids || n < 0) return LIVO_E_INVALID;
-    if (stride_bytes == 0) stride_bytes = 3 * sizeof(float);
-    if (stride_bytes < (int64_t)(3 * sizeof(float))) return LIVO_E_INVALID;
-    for (int32_t b = 0; b < n; b++) {
-        if (N[b] < 0 || (N[b] > 0 && !xyz[b])) return LIVO_E_INVALID;
-        if (N[b] > (int64_t)0x7FFFFFFF - kBlock) return LIVO_E_RANGE;
+// The non-empty scans' buffers (sb) and their build out of S on the upload
+// stream; S.free marks the end of the build's reads of S.
+static int pass_build(livo_ctx* c, const int64_t* N, const UploadPass& P, UploadDev::Src& S, ScanBuf* sb) {
+    UploadDev& U = c->up;
+    Carve cv{(char*)U.tmp};
+    const ScanBuild L = scan_build_layout(cv, (size_t)P.tot, (size_t)6 * kFeSegMax);
+    const float* d_src = (const float*)S.p;
+    FeSegs G{};
+    int rc = LIVO_OK;
+    for (int32_t b = 0; b < P.m && !rc; b++) {
+        G.off[b] = P.off[b];
+        G.n[b] = N[b];
+        if (N[b] == 0) continue;  // (nothing to build: the kernels read none of its pointers)
+        rc = pending_scan(c, N[b], sb[b]);
+        G.pts4[b] = sb[b].pts;
+        G.iperm[b] = sb[b].d_iperm;
+        G.perm[b] = sb[b].d_perm;
+        G.nn[b] = sb[b].nn;
+        G.pstate[b] = sb[b].pstate;
     }
-    if (set_device(c)) return LIVO_E_HIP;
-    // (the builds on a high-priority stream were slower: 3.8k vs 11.8k updates/s
-    // with uploads, DESIGN.md section 10)
-    if (!c->up_stream && hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking) != hipSuccess) {
-        c->up_stream = nullptr;
-        return LIVO_E_HIP;
-    }
-    if (!c->cp_stream && hipStreamCreateWithFlags(&c->cp_stream, hipStreamNonBlocking) != hipSuccess) {
-        c->cp_stream = nullptr;
-        return LIVO_E_HIP;
-    }
-    for (int k = 0; k < 2; k++)
-        if ((!c->bsrc_copied[k] && hipEventCreateWithFlags(&c->bsrc_copied[k], hipEventDisableTiming) != hipSuccess) ||
-            (!c->bsrc_free[k] && hipEventCreateWithFlags(&c->bsrc_free[k], hipEventDisableTiming) != hipSuccess))
-            return LIVO_E_HIP;
-    for (int32_t b0 = 0; b0 < n; b0 += kFeSegMax) {
-        const int32_t m = std::min<int32_t>(kFeSegMax, n - b0);
-        int64_t tot = 0, max_n = 0;
-        for (int32_t b = 0; b < m; b++) {
-            tot += N[b0 + b];
-            max_n = std::max(max_n, N[b0 + b]);
-        }
-        if (tot == 0) {  // (empty scans only)
-            for (int32_t b = 0; b < m; b++) {
-                const int rc = livo_scan_upload(c, xyz[b0 + b], 0, stride_bytes, scan_ids + b0 + b);
-                if (rc) return rc;
-                *registered = b0 + b + 1;
-            }
+    // bounds start at +max (mins) and ~(-max) (maxes, stored inverted) in the order-preserving encoding
+    if (!rc && hipMemsetD32Async((hipDeviceptr_t)L.bounds, 0xFFFFFFFFu, 6 * kFeSegMax, U.up) != hipSuccess)
+        rc = LIVO_E_HIP;
+    if (!rc) rc = launch_fe_build_seg(d_src, G, P.m, P.max_n, L.bounds, morton_scale(), L.keys, L.iota, U.up);
+    if (!rc)
+        rc = sort_u32_on(U.up, &U.prim, &U.prim_bytes, true, L.keys, L.skeys, L.iota, L.svals, P.tot, P.key_bits);
+    if (!rc) rc = launch_fe_gather_seg(d_src, G, P.m, P.max_n, L.svals, U.up);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(S.free, U.up));
+    S.used = true;
+    return LIVO_OK;
+}
+
+// The pass's scans get their ids, in order: a built one behind its `ready`
+// event, an empty one as livo_scan_upload registers it.  *done counts them.
+static int pass_register(livo_ctx* c, const int64_t* N, const UploadPass& P, ScanBuf* sb, int32_t* ids, int32_t* done) {
+    for (int32_t b = 0; b < P.m; b++, ++*done) {
+        if (N[b] > 0) {
+            RC_TRY(publish_pending(c, sb[b], c->up.up, ids + b));
             continue;
         }
-        if (tot > (int64_t)0xFFFFFFFF - kBlock) return LIVO_E_RANGE;  // (32-bit positions in the batch sort)
-        // build scratch (up_stream): scan_build_layout with 6 bounds per scan; the packed points
-        // in the staging buffer of this pass (cp_stream copies into it)
-        const size_t tmp_need = carve_bytes(scan_build_layout, (size_t)tot, (size_t)6 * kFeSegMax);
-        const size_t bytes = (size_t)tot * 3 * sizeof(float);
-        const int sl = c->bsrc_next;
-        c->bsrc_next ^= 1;
-        if (tmp_need > c->aup_tmp_bytes || bytes > c->bsrc_bytes[sl]) {  // (growing: the uploads in flight finish first)
-            if (hipStreamSynchronize(c->cp_stream) != hipSuccess || hipStreamSynchronize(c->up_stream) != hipSuccess)
-                return LIVO_E_HIP;
-            int rc = ensure_dev_bytes(&c->aup_tmp, &c->aup_tmp_bytes, tmp_need);
-            if (!rc) rc = ensure_dev_bytes(&c->bsrc[sl], &c->bsrc_bytes[sl], bytes);
-            if (rc) return rc;
-        }
-        Carve cv{(char*)c->aup_tmp};
-        const ScanBuild L = scan_build_layout(cv, (size_t)tot, (size_t)6 * kFeSegMax);
-        float* d_src = (float*)c->bsrc[sl];
-        // the copy into this buffer waits for the build that last read it
-        if (c->bsrc_used[sl] && hipStreamWaitEvent(c->cp_stream, c->bsrc_free[sl], 0) != hipSuccess) return LIVO_E_HIP;
-        // the points: straight from page-locked caller memory, else through a
-        // pinned staging buffer of the ring (the caller's arrays are free on return)
-        const bool trace = std::getenv("LIVO_UPLOAD_TRACE") != nullptr;  // (development: host phases to stderr)
-        auto now_us = [] {
-            return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        };
-        const double t_a = trace ? now_us() : 0.0;
-        bool direct = stride_bytes == (int64_t)(3 * sizeof(float));
-        for (int32_t b = 0; b < m && direct; b++)
-            if (N[b0 + b] > 0 && !host_pinned_range(xyz[b0 + b], (size_t)N[b0 + b] * 3 * sizeof(float))) direct = false;
-        const double t_b = trace ? now_us() : 0.0;
-        double t_c = t_b, t_d = t_b;
-        int rc = LIVO_OK;
-        livo_ctx::PinSlot* P = nullptr;
-        if (!direct) {
-            P = &c->pin[c->pin_next];
-            c->pin_next = (c->pin_next + 1) % kPinRing;
-            if (P->inflight && hipEventSynchronize(P->copied) != hipSuccess) return LIVO_E_HIP;
-            P->inflight = false;
-            t_c = trace ? now_us() : 0.0;
-            if (bytes > P->bytes) {
-                if (P->h) (void)hipHostFree(P->h);
-                P->h = nullptr;
-                P->bytes = 0;
-                if (hipHostMalloc((void**)&P->h, bytes, hipHostMallocDefault) != hipSuccess) {
-                    P->h = nullptr;
-                    return LIVO_E_OOM;
-                }
-                P->bytes = bytes;
-            }
-            if (!P->copied && hipEventCreateWithFlags(&P->copied, hipEventDisableTiming) != hipSuccess) {
-                P->copied = nullptr;
-                return LIVO_E_HIP;
-            }
-            // one host thread per scan (up to 8): a single thread's copy into pinned
-            // memory ran at ~9 GB/s (1.07 ms per 8 x 100k batch)
-            int64_t offs[kFeSegMax];
-            int64_t o = 0;
-            for (int32_t b = 0; b < m; b++) {
-                offs[b] = o;
-                o += N[b0 + b];
-            }
-            auto pack = [&](int32_t b) {
-                if (N[b0 + b] > 0) pack_xyz(xyz[b0 + b], N[b0 + b], stride_bytes, P->h + 3 * offs[b]);
-            };
-            if (bytes < ((size_t)1 << 20) || m == 1) {
-                for (int32_t b = 0; b < m; b++) pack(b);
-            } else {
-                const int nt = std::min<int>(8, m);
-                std::vector<std::thread> th;
-                for (int t = 1; t < nt; t++)
-                    th.emplace_back([&, t] {
-                        for (int32_t b = t; b < m; b += nt) pack(b);
-                    });
-                for (int32_t b = 0; b < m; b += nt) pack(b);
-                for (auto& x : th) x.join();
-            }
-            t_d = trace ? now_us() : 0.0;
-            if (hipMemcpyAsync(d_src, P->h, bytes, hipMemcpyHostToDevice, c->cp_stream) != hipSuccess ||
-                hipEventRecord(P->copied, c->cp_stream) != hipSuccess)
-                return LIVO_E_HIP;
-            P->inflight = true;
-        } else {
-            // page-locked caller arrays: one kernel reads them through their mapped
-            // device addresses (no DMA command per scan: a hipMemcpyAsync of one
-            // held the host 13-16 ms now and then inside a running farm); an
-            // array without a device mapping: DMA copies
-            FeSrc F{};
-            bool mapped = true;
-            int64_t o = 0;
-            for (int32_t b = 0; b < m; b++) {
-                F.off[b] = o;
-                F.n[b] = N[b0 + b];
-                F.src[b] = nullptr;
-                if (mapped && N[b0 + b] > 0) {
-                    void* dp = nullptr;
-                    if (hipHostGetDevicePointer(&dp, const_cast<float*>(xyz[b0 + b]), 0) != hipSuccess || !dp) {
-                        (void)hipGetLastError();
-                        mapped = false;
-                    }
-                    F.src[b] = (const float*)dp;
-                }
-                o += N[b0 + b];
-            }
-            if (mapped) {
-                const int r2 = launch_fe_copy_seg(F, m, max_n, d_src, c->cp_stream);
-                if (r2) return r2;
-            } else {
-                o = 0;
-                for (int32_t b = 0; b < m; b++) {
-                    if (N[b0 + b] > 0 &&
-                        hipMemcpyAsync(d_src + 3 * o, xyz[b0 + b], (size_t)N[b0 + b] * 3 * sizeof(float),
-                                       hipMemcpyHostToDevice, c->cp_stream) != hipSuccess)
-                        return LIVO_E_HIP;
-                    o += N[b0 + b];
-                }
-            }
-            t_d = trace ? now_us() : 0.0;  // (the copies' host time)
-        }
-        if (hipEventRecord(c->bsrc_copied[sl], c->cp_stream) != hipSuccess ||
-            hipStreamWaitEvent(c->up_stream, c->bsrc_copied[sl], 0) != hipSuccess)
-            return LIVO_E_HIP;
-        // the scans' buffers
-        ScanBuf sb[kFeSegMax];
-        FeSegs S{};
-        int64_t o = 0;
-        for (int32_t b = 0; b < m && !rc; b++) {
-            rc = alloc_scan_buf(c, sb[b], N[b0 + b]);
-            if (!rc && !sb[b].ready && hipEventCreateWithFlags(&sb[b].ready, hipEventDisableTiming) != hipSuccess) {
-                sb[b].ready = nullptr;
-                rc = LIVO_E_HIP;
-            }
-            S.off[b] = o;
-            S.n[b] = N[b0 + b];
-            S.pts4[b] = sb[b].pts;
-            S.iperm[b] = sb[b].d_iperm;
-            S.perm[b] = sb[b].d_perm;
-            S.nn[b] = sb[b].nn;
-            S.pstate[b] = sb[b].pstate;
-            o += N[b0 + b];
-        }
-        // bounds start at +max (mins) and ~(-max) (maxes, stored inverted) in the order-preserving encoding
-        if (!rc && (hipMemsetD32Async((hipDeviceptr_t)L.bounds, 0xFFFFFFFFu, 6 * kFeSegMax, c->up_stream) != hipSuccess))
-            rc = LIVO_E_HIP;
-        if (!rc) rc = launch_fe_build_seg(d_src, S, m, max_n, L.bounds, morton_scale(), L.keys, L.iota, c->up_stream);
-        int key_bits = 27;  // + the scan index's bits
-        while ((1 << (key_bits - 27)) < m) key_bits++;
-        if (!rc)
-            rc = sort_u32_on(c->up_stream, &c->aup_prim, &c->aup_prim_bytes, true, L.keys, L.skeys, L.iota, L.svals, tot,
-                             key_bits);
-        if (!rc) rc = launch_fe_gather_seg(d_src, S, m, max_n, L.svals, c->up_stream);
-        if (!rc && hipEventRecord(c->bsrc_free[sl], c->up_stream) != hipSuccess) rc = LIVO_E_HIP;
-        c->bsrc_used[sl] = true;
-        for (int32_t b = 0; b < m && !rc; b++)
-            if (hipEventRecord(sb[b].ready, c->up_stream) != hipSuccess) rc = LIVO_E_HIP;
-        if (rc) {
-            (void)hipStreamSynchronize(c->cp_stream);
-            (void)hipStreamSynchronize(c->up_stream);
-            for (int32_t b = 0; b < m; b++)
-                if (sb[b].used) release_scan_buf(c, sb[b]);
-            return rc;
-        }
-        if (trace)
-            std::fprintf(stderr, "[upload] %d scans %s: pinned check %.1f us, ring wait %.1f, pack / copies %.1f, build %.1f\n",
-                         (int)m, direct ? "direct" : "staged", t_b - t_a, t_c - t_b, t_d - t_c, now_us() - t_d);
-        for (int32_t b = 0; b < m; b++) {
-            if (N[b0 + b] == 0) {  // (an empty scan has nothing to build)
-                release_scan_buf(c, sb[b]);
-                rc = livo_scan_upload(c, xyz[b0 + b], 0, stride_bytes, scan_ids + b0 + b);
-                if (rc) {
-                    for (int32_t q = b + 1; q < m; q++) release_scan_buf(c, sb[q]);  // (built, not registered)
-                    return rc;
-                }
-                *registered = b0 + b + 1;
-                continue;
-            }
-            sb[b].pending = true;
-            scan_ids[b0 + b] = register_scan(c, sb[b]);
-            *registered = b0 + b + 1;
-        }
+        ScanBuf s;
+        RC_TRY(alloc_scan_buf(c, s, 0));
+        ids[b] = register_scan(c, s);
     }
     return LIVO_OK;
+}
+
+// A pass that fails gives up its unregistered scans (drop_pending) and the call
+// releases the scans it registered before, so a failed call leaves no scan
+// behind (scan_ids unspecified).
+int livo_scan_upload_batch_async(livo_ctx* c, const float* const* xyz, const int64_t* N, int32_t n,
+                                 int64_t stride_bytes, int32_t* scan_ids) {
+    if (!c || !xyz || !N || !scan_ids || n < 0) return LIVO_E_INVALID;
+    RC_TRY(upload_args(0, stride_bytes));
+    for (int32_t b = 0; b < n; b++) {
+        if (N[b] > 0 && !xyz[b]) return LIVO_E_INVALID;
+        RC_TRY(upload_args(N[b], stride_bytes));
+    }
+    if (set_device(c) || c->up.streams(true)) return LIVO_E_HIP;
+    int rc = LIVO_OK;
+    int32_t done = 0;
+    for (int32_t b0 = 0; b0 < n && !rc; b0 += kFeSegMax) {
+        UploadPass P;
+        ScanBuf sb[kFeSegMax];
+        UploadTrace T;
+        bool direct = false;
+        rc = upload_pass(N, n, b0, &P);
+        if (!rc && P.tot > 0) {  // (else: empty scans only)
+            UploadDev::Src& S = c->up.src[c->up.src_next];
+            c->up.src_next ^= 1;
+            rc = pass_source(c, xyz + b0, N + b0, stride_bytes, P, S, T, &direct);
+            if (!rc) rc = pass_build(c, N + b0, P, S, sb);
+        }
+        if (!rc) rc = pass_register(c, N + b0, P, sb, scan_ids + b0, &done);
+        if (rc) drop_pending(c, sb, P.m);
+        else if (P.tot > 0) T.print(P.m, direct);
+    }
+    if (rc)
+        for (int32_t b = 0; b < done; b++) (void)livo_scan_release(c, scan_ids[b]);
+    return rc;
 }
 
 int livo_scan_release(livo_ctx* c, int32_t id) {
@@ -5325,9 +5306,7 @@ int livo_sync(livo_ctx* c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (const BatchLane& B : c->lane)  // submitted batches run on their lanes' streams
         for (int k = 0; k < kMaxGroups && B.st[k]; k++) HIP_TRY(hipStreamSynchronize(B.st[k]));
-    if (c->cp_stream) HIP_TRY(hipStreamSynchronize(c->cp_stream));  // asynchronous uploads
-    if (c->up_stream) HIP_TRY(hipStreamSynchronize(c->up_stream));
-    return LIVO_OK;
+    return c->up.drain();  // asynchronous uploads
 }
 
 }  // extern "C"

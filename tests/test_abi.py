@@ -51,6 +51,22 @@ def test_carve_cursor_totals_and_alignment(tmp_path):
     assert out.stdout == "ok\n"
 
 
+def test_upload_plan_passes_and_scan_bytes(tmp_path):
+    """csrc/upload_plan.h, the host arithmetic of the scan uploads: tests/native/upload_plan_check.cpp on the
+    CPU under the address and undefined-behaviour sanitizers.  livo_scan_upload_batch_async's passes (18
+    ragged scans split 16 + 2; offsets, totals, largest scan and sort key bits recomputed; empty passes; the
+    32-bit position limit from both sides) and the bytes of a scan's nine device arrays, by which the spare
+    pool is budgeted, against the written-out formula."""
+    exe = tmp_path / "upload_plan_check"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "fast-livo-noted_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "native", "upload_plan_check.cpp"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout == "ok\n"
+
+
 def test_hip_code_object_is_gfx950(built):
     import livo_amd
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-S", livo_amd.LIB_PATH], capture_output=True,
