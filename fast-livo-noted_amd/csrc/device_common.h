@@ -122,11 +122,18 @@ __device__ __forceinline__ void world_point(const double* R, const double* pos, 
     wz = (float)(((R[6] * ix + R[7] * iy) + R[8] * iz) + pos[2]);
 }
 // The world point of cloud index i (the caller's point order), exactly as
-// k_to_world stores it.
+// k_to_world stores it.  A world cloud's three floats are returned as stored
+// (no identity transform: a -0.0f stays -0.0f).
 __device__ __forceinline__ void cloud_world_point(const CloudSrc& S, const WorldParams& W, int i, float& wx, float& wy,
                                                   float& wz) {
     const int64_t k = S.iperm ? (int64_t)S.iperm[i] : (int64_t)i;
     const float* p = S.src + S.stride * k;
+    if (S.world) {
+        wx = p[0];
+        wy = p[1];
+        wz = p[2];
+        return;
+    }
     world_point(W.rot, W.pos, W.R_LI, W.t_LI, p[0], p[1], p[2], wx, wy, wz);
 }
 

@@ -136,17 +136,11 @@ __device__ __forceinline__ unsigned f2o(float f) {
 // at kMinmaxBlocks): per-wave atomics from ~1.6k waves on 6 addresses
 // serialised across the XCDs and took 110-220 us per 100k-point scan.
 constexpr int kMinmaxBlocks = 64;
-__global__ __launch_bounds__(256) void k_fe_minmax(const float* __restrict__ pts, int64_t n, int stride,
-                                                   unsigned* minmax) {
+// The block's part: every thread's ordered mins and maxes reduced in its wave, then
+// in LDS, then one atomic per bound.  Every thread of a block of whole waves (4 at
+// most) calls it, once per kernel.
+__device__ __forceinline__ void block_minmax(unsigned (&mn)[3], unsigned (&mx)[3], unsigned* minmax) {
     __shared__ unsigned red[4][6];
-    unsigned mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const unsigned o = f2o(pts[stride * i + k]);
-            mn[k] = min(mn[k], o);
-            mx[k] = max(mx[k], o);
-        }
 #pragma unroll
     for (int k = 0; k < 3; k++)
 #pragma unroll
@@ -169,6 +163,18 @@ __global__ __launch_bounds__(256) void k_fe_minmax(const float* __restrict__ pts
         if (k < 3) atomicMin(minmax + k, v);
         else atomicMax(minmax + k, v);
     }
+}
+__global__ __launch_bounds__(256) void k_fe_minmax(const float* __restrict__ pts, int64_t n, int stride,
+                                                   unsigned* minmax) {
+    unsigned mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const unsigned o = f2o(pts[stride * i + k]);
+            mn[k] = min(mn[k], o);
+            mx[k] = max(mx[k], o);
+        }
+    block_minmax(mn, mx, minmax);
 }
 
 // PCL leaf index (voxel_grid.hpp): ijk = int(floor(p * inv) - float(min_b)), idx = ijk . divb_mul
@@ -351,16 +357,52 @@ __global__ void k_to_world(CloudSrc S, WorldParams W, float* __restrict__ out5) 
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= S.n) return;
     const float* p = S.src + S.stride * k;
+    const int64_t o = S.perm ? (int64_t)S.perm[k] : k;
+    float* q = out5 + 5 * o;
+    if (S.world) {  // a published world cloud: its rows as stored
+        const float r[5] = {p[0], p[1], p[2], p[3], p[4]};
+#pragma unroll
+        for (int c = 0; c < 5; c++) q[c] = r[c];
+        return;
+    }
     float wx, wy, wz;
     world_point(W.rot, W.pos, W.R_LI, W.t_LI, p[0], p[1], p[2], wx, wy, wz);
     const float intensity = S.stride >= 5 ? p[3] : 0.0f;  // (read before the stores: S's pointers carry no __restrict__)
-    const int64_t o = S.perm ? (int64_t)S.perm[k] : k;
-    float* q = out5 + 5 * o;
     q[0] = wx;
     q[1] = wy;
     q[2] = wz;
     q[3] = intensity;
     q[4] = 0.0f;
+}
+
+// livo_cloud_publish: k_to_world's rows of a body-frame cloud (the same world_point, the same
+// bytes) and, in the same pass, the bounds of the stored floats for the VoxelGrid that follows.
+// Grid-stride over the stored order, kPublishBlocks blocks at most: block_minmax's six atomics
+// per block stay few.  minmax == nullptr (no pg_down): the rows only.
+constexpr int kPublishBlocks = 256;
+__global__ __launch_bounds__(256) void k_cloud_publish(CloudSrc S, WorldParams W, float* __restrict__ out5,
+                                                       unsigned* minmax) {
+    unsigned mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < S.n; k += (int64_t)gridDim.x * blockDim.x) {
+        const float* p = S.src + S.stride * k;
+        float w[3];
+        world_point(W.rot, W.pos, W.R_LI, W.t_LI, p[0], p[1], p[2], w[0], w[1], w[2]);
+        const float intensity = S.stride >= 5 ? p[3] : 0.0f;
+        const int64_t o = S.perm ? (int64_t)S.perm[k] : k;
+        float* q = out5 + 5 * o;
+        q[0] = w[0];
+        q[1] = w[1];
+        q[2] = w[2];
+        q[3] = intensity;
+        q[4] = 0.0f;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const unsigned u = f2o(w[a]);
+            mn[a] = min(mn[a], u);
+            mx[a] = max(mx[a], u);
+        }
+    }
+    if (minmax) block_minmax(mn, mx, minmax);  // (uniform: every thread of the block takes it)
 }
 
 // laserCloudOri / corr_normvect (laser_mapping.cpp:547-561): the effective
@@ -474,6 +516,13 @@ int launch_fe_gather_seg(const float* pts, const FeSegs& S, int n_scans, int64_t
 }
 int launch_to_world(const CloudSrc& S, const WorldParams& W, float* out5, void* stream) {
     FE_LAUNCH(k_to_world, S.n, S, W, out5);
+}
+int launch_cloud_publish(const CloudSrc& S, const WorldParams& W, float* out5, unsigned* minmax, void* stream) {
+    if (S.n <= 0) return LIVO_OK;
+    if (S.world) return LIVO_E_INVALID;  // (the rows of a world cloud are launch_to_world's copy)
+    const unsigned blocks = (unsigned)std::min<int64_t>(kPublishBlocks, (S.n + 255) / 256);
+    hipLaunchKernelGGL(k_cloud_publish, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, W, out5, minmax);
+    return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream) {
     FE_LAUNCH(k_ori_flags, n, sel, perm, n, flags);

@@ -91,6 +91,19 @@ static int image_stage(DevImage& m, const uint8_t* host, size_t bytes, hipStream
     return hipMemcpyAsync(m.p, host, bytes, hipMemcpyHostToDevice, st) == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 
+// What a LiDAR frame hands to the camera frames behind it (livo_cloud_publish):
+// pcl_wait_pub and pg_down, 5 floats a point, in one allocation that grows and
+// never shrinks.
+struct WorldCloud {
+    void* buf = nullptr;
+    size_t bytes = 0;
+    const float* world = nullptr;  // n rows
+    const float* down = nullptr;   // n_down rows (world itself where the filter kept its input)
+    int64_t n = -1;                // -1: nothing published
+    int64_t n_down = -1;           // -1: pg_down not built
+    bool filtered = false;
+};
+
 static void free_scan_buf(ScanBuf& s) {
     scan_arrays(s, s.cap, [](auto*& p, size_t) { dev_free(p); });
     if (s.ready) (void)hipEventDestroy(s.ready);
@@ -434,6 +447,7 @@ struct livo_ctx {
     size_t fe_bytes = 0;
     const float* fe_raw = nullptr;     // the last preprocessed frame, de-skewed, full resolution (5 floats a point)
     int64_t fe_n = 0;
+    WorldCloud wcloud;                 // livo_cloud_publish: pcl_wait_pub and pg_down
     void* vio_buf = nullptr;           // VIO frame (image, points, partials, slot)
     size_t vio_bytes = 0;
     DevImage bgr_img;                  // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
@@ -2058,6 +2072,7 @@ int livo_ctx_destroy(livo_ctx* c) {
     ivox_free(c->iv);
     dyn_free(c->dyn);
     if (c->fe_buf) (void)hipFree(c->fe_buf);
+    if (c->wcloud.buf) (void)hipFree(c->wcloud.buf);
     if (c->prim_tmp) (void)hipFree(c->prim_tmp);
     if (c->vio_buf) (void)hipFree(c->vio_buf);
     dev_free(c->bgr_img.p);
@@ -4072,6 +4087,76 @@ int livo_scan_inherit_neighbors(livo_ctx* c, int32_t dst, int32_t src) {
     return LIVO_OK;
 }
 
+// ---- PCL VoxelGrid::applyFilter behind its bounds (livo_scan_preprocess, livo_cloud_publish) ----
+// The filter's arrays for nb points; F.raw (the input), F.down (nb x 5) and the bounds are the caller's.
+static void voxel_grid_layout(FrontParams& F, Carve& k, size_t nb) {
+    F.keys = k.take<uint32_t>(nb);
+    F.iota = k.take<uint32_t>(nb);
+    F.skeys = k.take<uint32_t>(nb);
+    F.svals = k.take<uint32_t>(nb);
+    F.flags = k.take<uint32_t>(nb);
+    F.vid = k.take<uint32_t>(nb);
+    F.starts = k.take<uint32_t>(nb + 1);
+}
+// The bounds' words before the first atomic (launch_fe_minmax, launch_cloud_publish).
+static int minmax_init(livo_ctx* c, unsigned* mm) {
+    static const unsigned init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
+    HIP_TRY(hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+    return LIVO_OK;
+}
+// The F.n > 0 points of F.raw with their bounds in mm (device, written on c->stream):
+// *n_vox centroids into F.down in ascending leaf order, or -1 where PCL returns its input.
+static int voxel_grid(livo_ctx* c, FrontParams& F, const unsigned* mm, float leaf_size, int64_t* n_vox) {
+    const int64_t n = F.n;
+    *n_vox = -1;
+    unsigned hm[6];
+    HIP_TRY(hipMemcpyAsync(hm, mm, sizeof(hm), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float mn[3], mx[3];
+    auto dec = [](unsigned o) {
+        const unsigned u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+    };
+    for (int k = 0; k < 3; k++) {
+        mn[k] = dec(hm[k]);
+        mx[k] = dec(hm[3 + k]);
+    }
+    const float inv = 1.0f / leaf_size;  // inverse_leaf_size_
+    const int64_t dx = static_cast<int64_t>((mx[0] - mn[0]) * inv) + 1;
+    const int64_t dy = static_cast<int64_t>((mx[1] - mn[1]) * inv) + 1;
+    const int64_t dz = static_cast<int64_t>((mx[2] - mn[2]) * inv) + 1;
+    if ((dx * dy * dz) > static_cast<int64_t>(0x7FFFFFFF)) return LIVO_OK;  // PCL returns the input
+    int max_b[3], div_b[3];
+    for (int k = 0; k < 3; k++) {
+        F.min_b[k] = static_cast<int>(std::floor(mn[k] * inv));
+        max_b[k] = static_cast<int>(std::floor(mx[k] * inv));
+        div_b[k] = max_b[k] - F.min_b[k] + 1;
+    }
+    F.divb_mul[0] = 1;
+    F.divb_mul[1] = div_b[0];
+    F.divb_mul[2] = div_b[0] * div_b[1];
+    F.inv_leaf = inv;
+    const int64_t cells = (int64_t)div_b[0] * div_b[1] * div_b[2];
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < cells) bits++;
+    int rc = launch_fe_leaf(F, c->stream);
+    if (!rc)
+        rc = sort_u32(c, F.keys, const_cast<uint32_t*>(F.skeys), F.iota, const_cast<uint32_t*>(F.svals), n, bits);
+    if (!rc) rc = launch_fe_runs(F, c->stream);
+    if (!rc) rc = scan_u32(c, F.flags, F.vid, n);
+    ScanCount vox;
+    if (!rc) rc = vox.read(F.vid, F.flags, n, c->stream);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rc = launch_fe_starts(F, c->stream);
+    if (!rc) rc = launch_fe_centroid(F, vox.sum(), c->stream);
+    if (rc) return rc;
+    *n_vox = vox.sum();
+    return LIVO_OK;
+}
+
 int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, const livo_imu_pose* poses,
                          int32_t n_poses, const double rot_end[9], const double pos_end[3], float leaf_size,
                          int32_t* scan_id, livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap,
@@ -4093,7 +4178,6 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
     FrontParams F{};
     double* d_poses;
     int32_t* seg;
-    uint32_t *skeys, *svals;
     unsigned* mm;  // the bounds (launch_fe_minmax)
     const size_t nb = (size_t)std::max<int64_t>(n, 1);
     auto layout = [&](Carve k) {
@@ -4101,13 +4185,7 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
         F.poses = d_poses = k.take<double>((size_t)std::max(n_poses, 1) * 22);
         F.seg = seg = k.take<int32_t>(nb);
         F.seg_rev = k.take<int32_t>(nb);
-        F.keys = k.take<uint32_t>(nb);
-        F.iota = k.take<uint32_t>(nb);
-        F.skeys = skeys = k.take<uint32_t>(nb);
-        F.svals = svals = k.take<uint32_t>(nb);
-        F.flags = k.take<uint32_t>(nb);
-        F.vid = k.take<uint32_t>(nb);
-        F.starts = k.take<uint32_t>(nb + 1);
+        voxel_grid_layout(F, k, nb);
         F.down = k.take<float>(nb * 5);
         mm = k.take<unsigned>(6);
         return k.total();
@@ -4153,54 +4231,11 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
     const float* kept = F.raw;
     int64_t n_kept = n;
     if (leaf_size > 0.f && n > 0) {
-        const unsigned init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-        HIP_TRY(hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-        rc = launch_fe_minmax(F.raw, n, 5, mm, c->stream);
-        if (rc) return rc;
-        unsigned hm[6];
-        HIP_TRY(hipMemcpyAsync(hm, mm, sizeof(hm), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        float mn[3], mx[3];
-        auto dec = [](unsigned o) {
-            const unsigned u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-            float f;
-            std::memcpy(&f, &u, 4);
-            return f;
-        };
-        for (int k = 0; k < 3; k++) {
-            mn[k] = dec(hm[k]);
-            mx[k] = dec(hm[3 + k]);
-        }
-        const float inv = 1.0f / leaf_size;  // inverse_leaf_size_
-        const int64_t dx = static_cast<int64_t>((mx[0] - mn[0]) * inv) + 1;
-        const int64_t dy = static_cast<int64_t>((mx[1] - mn[1]) * inv) + 1;
-        const int64_t dz = static_cast<int64_t>((mx[2] - mn[2]) * inv) + 1;
-        if ((dx * dy * dz) <= static_cast<int64_t>(0x7FFFFFFF)) {  // else PCL returns the input
-            int max_b[3], div_b[3];
-            for (int k = 0; k < 3; k++) {
-                F.min_b[k] = static_cast<int>(std::floor(mn[k] * inv));
-                max_b[k] = static_cast<int>(std::floor(mx[k] * inv));
-                div_b[k] = max_b[k] - F.min_b[k] + 1;
-            }
-            F.divb_mul[0] = 1;
-            F.divb_mul[1] = div_b[0];
-            F.divb_mul[2] = div_b[0] * div_b[1];
-            F.inv_leaf = inv;
-            const int64_t cells = (int64_t)div_b[0] * div_b[1] * div_b[2];
-            int bits = 1;
-            while (bits < 32 && ((int64_t)1 << bits) < cells) bits++;
-            rc = launch_fe_leaf(F, c->stream);
-            if (!rc) rc = sort_u32(c, F.keys, skeys, F.iota, svals, n, bits);
-            if (!rc) rc = launch_fe_runs(F, c->stream);
-            if (!rc) rc = scan_u32(c, F.flags, F.vid, n);
-            ScanCount vox;
-            if (!rc) rc = vox.read(F.vid, F.flags, n, c->stream);
-            if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            const int64_t n_vox = vox.sum();
-            rc = launch_fe_starts(F, c->stream);
-            if (!rc) rc = launch_fe_centroid(F, n_vox, c->stream);
-            if (rc) return rc;
+        RC_TRY(minmax_init(c, mm));
+        RC_TRY(launch_fe_minmax(F.raw, n, 5, mm, c->stream));
+        int64_t n_vox;
+        RC_TRY(voxel_grid(c, F, mm, leaf_size, &n_vox));
+        if (n_vox >= 0) {
             kept = F.down;
             n_kept = n_vox;
         }
@@ -4448,9 +4483,21 @@ int livo_map_last_add_stats(livo_ctx* c, livo_map_add_stats* out) {
 
 // The cloud of the frame stages: the last preprocessed frame at full resolution
 // (scan_id < 0; n = 0 while there is none) or a resident scan, with the
-// permutations between its stored order and the caller's point order.
+// permutations between its stored order and the caller's point order.  The two
+// LIVO_CLOUD_* ids: the published world cloud and pg_down, read as stored.
+static bool is_cloud_id(int32_t scan_id) { return scan_id == LIVO_CLOUD_WORLD || scan_id == LIVO_CLOUD_WORLD_DOWN; }
 static int frame_cloud(livo_ctx* c, int32_t scan_id, CloudSrc* S) {
     *S = CloudSrc{};
+    if (is_cloud_id(scan_id)) {
+        const WorldCloud& w = c->wcloud;
+        const bool down = scan_id == LIVO_CLOUD_WORLD_DOWN;
+        if (w.n < 0 || (down && w.n_down < 0)) return LIVO_E_NOSCAN;
+        S->src = down ? w.down : w.world;
+        S->n = down ? w.n_down : w.n;
+        S->stride = 5;
+        S->world = 1;
+        return LIVO_OK;
+    }
     if (scan_id < 0) {
         S->src = c->fe_raw;
         S->n = c->fe_raw ? c->fe_n : 0;
@@ -4493,6 +4540,90 @@ int livo_frame_to_world(livo_ctx* c, int32_t scan_id, const livo_state* state, l
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return LIVO_OK;
+}
+
+static void cloud_info(const WorldCloud& w, livo_cloud_info* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->n = w.n;
+    out->n_down = w.n_down;
+    out->down_filtered = w.filtered ? 1 : 0;
+    out->device_bytes = (int64_t)w.bytes;
+}
+
+// *pcl_wait_pub = *laserCloudWorld at the end of a LiDAR frame (laser_mapping.cpp:258-268) and the
+// pg_down every detect until the next one filters out of it (lidar_selection.cpp:341-344).
+int livo_cloud_publish(livo_ctx* c, int32_t src_scan_id, const livo_state* lio_state, float match_leaf,
+                       livo_cloud_info* info) {
+    if (!c || !lio_state || !std::isfinite(match_leaf) || is_cloud_id(src_scan_id)) return LIVO_E_INVALID;
+    CloudSrc S;
+    RC_TRY(frame_cloud(c, src_scan_id, &S));
+    const int64_t n = S.n;
+    if (n > (int64_t)0x7FFFFFFF - kRgbBlock) return LIVO_E_RANGE;  // (the stages' bound)
+    if (set_device(c)) return LIVO_E_HIP;
+    const bool build_down = match_leaf > 0.f;
+    const size_t nb = (size_t)std::max<int64_t>(n, 1);
+    // the filter's arrays: scratch, not fe_buf (feats_undistort there is the source of src_scan_id < 0)
+    FrontParams F{};
+    unsigned* mm = nullptr;
+    auto scratch = [&](Carve k) {
+        voxel_grid_layout(F, k, nb);
+        mm = k.take<unsigned>(6);
+        return k.total();
+    };
+    if (build_down && n > 0) {
+        RC_TRY(ensure_scratch(c, scratch(Carve{nullptr})));
+        scratch(Carve{(char*)c->scratch});
+    }
+    float *d_world, *d_down;
+    auto clouds = [&](Carve k) {
+        d_world = k.take<float>(nb * 5);
+        d_down = k.take<float>(build_down ? nb * 5 : 0);
+        return k.total();
+    };
+    WorldCloud& w = c->wcloud;
+    const size_t need = clouds(Carve{nullptr});
+    if (need > w.bytes) {  // the new buffer first: an allocation that fails leaves the published cloud
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) return LIVO_E_OOM;
+        if (w.buf) (void)hipFree(w.buf);  // (every call that read it has synchronised)
+        w.buf = p;
+        w.bytes = need;
+        w.n = w.n_down = -1;
+    }
+    clouds(Carve{(char*)w.buf});
+    // the previous cloud is gone from here on: no cloud until this one is complete
+    w.n = w.n_down = -1;
+    w.filtered = false;
+    if (mm) RC_TRY(minmax_init(c, mm));
+    RC_TRY(launch_cloud_publish(S, world_params(c, *lio_state), d_world, mm, c->stream));
+    int64_t n_down = build_down ? n : -1;
+    const float* down = build_down ? d_world : nullptr;
+    if (mm) {
+        F.raw = d_world;
+        F.n = n;
+        F.down = d_down;
+        int64_t n_vox;
+        RC_TRY(voxel_grid(c, F, mm, match_leaf, &n_vox));
+        if (n_vox >= 0) {
+            w.filtered = true;
+            n_down = n_vox;
+            down = d_down;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    w.world = d_world;
+    w.down = down;
+    w.n = n;
+    w.n_down = n_down;
+    if (info) cloud_info(w, info);
+    return LIVO_OK;
+}
+
+int livo_cloud_info_get(livo_ctx* c, livo_cloud_info* out) {
+    if (!c || !out) return LIVO_E_INVALID;
+    if (c->wcloud.n < 0) return LIVO_E_NOSCAN;
+    cloud_info(c->wcloud, out);
     return LIVO_OK;
 }
 
@@ -5153,7 +5284,10 @@ int livo_vio_detect(livo_ctx* c, int32_t scan_id, int32_t frame_id, livo_state* 
     VmapDev& m = c->vmap;
     MatchStage M;
     SelectStage S;
-    RC_TRY(match_prepare(c, scan_id, state, p, d->grid_size, d->ncc_en, d->ncc_thre, d->outlier_threshold, width,
+    // addFromSparseMap reads pg_down, addSparseMap the full cloud (lidar_selection.cpp:341-344, 140)
+    const int32_t match_id =
+        scan_id == LIVO_CLOUD_WORLD && c->wcloud.n >= 0 && c->wcloud.n_down >= 0 ? LIVO_CLOUD_WORLD_DOWN : scan_id;
+    RC_TRY(match_prepare(c, match_id, state, p, d->grid_size, d->ncc_en, d->ncc_thre, d->outlier_threshold, width,
                          height, true, &M));
     RC_TRY(select_prepare(c, scan_id, state, p, d->grid_size, width, height, true, &S));
     RC_TRY(frame_check(m, M.V.cam, width, height));

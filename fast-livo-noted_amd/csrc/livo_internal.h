@@ -621,16 +621,22 @@ int launch_fe_gather(const float* pts, int64_t n, int stride, const uint32_t* pe
 struct WorldParams {
     double rot[9], pos[3], R_LI[9], t_LI[3];
 };
-// The cloud of a frame stage: the last preprocessed frame or a resident scan.
+// The cloud of a frame stage: the last preprocessed frame, a resident scan or
+// a published world cloud (livo_cloud_publish).
 struct CloudSrc {
     const float* src;      // n points, stride floats each (x, y, z, ...), stored order
     const int32_t* perm;   // stored position -> cloud index (null: the same)
     const int32_t* iperm;  // cloud index -> stored position (null: the same)
     int64_t n;
     int32_t stride;
+    int32_t world;         // 1: src holds world points (5 floats, cloud order), read as stored
 };
-// RGBpointBodyToWorld of the cloud (x y z [intensity]) -> n x 5 floats, cloud order.
+// RGBpointBodyToWorld of the cloud (x y z [intensity]) -> n x 5 floats, cloud order
+// (a world cloud: its five columns copied).
 int launch_to_world(const CloudSrc& S, const WorldParams& W, float* out5, void* stream);
+// livo_cloud_publish: launch_to_world's rows of a body-frame cloud and, with minmax
+// (launch_fe_minmax's six words, initialised by the caller), the bounds of the stored floats.
+int launch_cloud_publish(const CloudSrc& S, const WorldParams& W, float* out5, unsigned* minmax, void* stream);
 // publish_frame_world_rgb (rgb_kernels.hip): the cloud of launch_to_world,
 // projected into the camera frame and coloured from the BGR image, the kept
 // points compacted in the cloud's order.

@@ -155,6 +155,19 @@ public:
         points_no_downsample = counts[1];
     }
 
+    // Run()'s tail (laser_mapping.cpp:258-268): *pcl_wait_pub = *laserCloudWorld, the frame
+    // (dense_map_en: the last set_scan_raw frame at full resolution, else the current
+    // feats_down_body) at the LIO-updated `state`, kept on the device for every camera frame
+    // until the next LiDAR frame ends: detectFromPublished() reads it at the state the IMU
+    // has propagated to the image's time.  match_leaf > 0 also builds the pg_down that each
+    // detect filters out of it (lidar_selection.cpp:7, 341-344); call it after map_incremental().
+    livo_cloud_info publish_cloud(bool dense_map_en = true, float match_leaf = 0.2f) {
+        if (!dense_map_en && scan_id_ < 0) throw Error("publish_cloud", LIVO_E_NOSCAN);
+        livo_cloud_info info{};
+        check(livo_cloud_publish(ctx_, dense_map_en ? -1 : scan_id_, &state, match_leaf, &info), "livo_cloud_publish");
+        return info;
+    }
+
     template <class S>
     void set_state(const S& s) { state = to_livo_state(s); }
     template <class S>
@@ -310,6 +323,24 @@ public:
         livo_vdetect_stats st{};
         check(livo_vio_detect(ctx_, dense_map_en ? -1 : scan_id_, frame_id, &state, &state_propagat, &vio, &d, img,
                               width, height, &st),
+              "livo_vio_detect");
+        return st;
+    }
+
+    // lidar_selector->detect(img, pcl_wait_pub) (laser_mapping.cpp:93) on the cloud of
+    // publish_cloud(): `state` places the camera only, addFromSparseMap reads pg_down where
+    // it was built and addSparseMap the full cloud.
+    livo_vdetect_stats detectFromPublished(const livo_vio_params& vio, const uint8_t* img, int32_t width,
+                                           int32_t height, int32_t frame_id, int32_t grid_size, bool ncc_en,
+                                           double ncc_thre, double outlier_threshold) {
+        livo_vdetect_params d{};
+        d.grid_size = grid_size;
+        d.ncc_en = ncc_en ? 1 : 0;
+        d.ncc_thre = ncc_thre;
+        d.outlier_threshold = outlier_threshold;
+        livo_vdetect_stats st{};
+        check(livo_vio_detect(ctx_, LIVO_CLOUD_WORLD, frame_id, &state, &state_propagat, &vio, &d, img, width, height,
+                              &st),
               "livo_vio_detect");
         return st;
     }

@@ -15,6 +15,7 @@ path:
     LidarSelector::addFromSparseMap      -> Context.vio_match
     LidarSelector::addObservation        -> Context.vio_observe
     LidarSelector::detect (one frame)    -> Context.vio_detect, Context.vmap_release_frames
+    pcl_wait_pub / pg_down (Run's tail)  -> Context.cloud_publish, CLOUD_WORLD, CLOUD_WORLD_DOWN
 
 There is no CPU fallback: loading fails loudly if the HIP library is missing,
 and every compute call raises LivoError when the GPU path fails.
@@ -41,6 +42,8 @@ ERRORS = {-1: "LIVO_E_INVALID", -2: "LIVO_E_HIP", -3: "LIVO_E_NOMAP", -4: "LIVO_
 MAX_INFLIGHT = 2  # LIVO_MAX_INFLIGHT
 BACKEND_IKDTREE = 0  # -DUSE_ikdtree build (CMakeLists.txt:15)
 BACKEND_IVOX = 1     # the reference's default build: faster_lio::IVox
+CLOUD_WORLD = 0x40000000       # LIVO_CLOUD_WORLD: the published world cloud as a frame stage's scan_id
+CLOUD_WORLD_DOWN = 0x40000001  # LIVO_CLOUD_WORLD_DOWN: its pg_down
 
 
 class LivoError(RuntimeError):
@@ -231,6 +234,11 @@ class VdetectStats(C.Structure):
                 ("n_matched", C.c_int64), ("n_new", C.c_int64), ("first_new_id", C.c_int32), ("pad_", C.c_int32)]
 
 
+class CloudInfo(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_down", C.c_int64), ("down_filtered", C.c_int32), ("pad_", C.c_int32),
+                ("device_bytes", C.c_int64)]
+
+
 def _stats_dict(st) -> dict:
     """A stats struct as a dict (arrays as lists)."""
     out = {}
@@ -323,6 +331,8 @@ SIGNATURES = {
     "livo_vmap_release_frames": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "livo_vio_detect": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(State), C.POINTER(State), C.POINTER(VioParams),
                                   C.POINTER(VdetectParams), _P, C.c_int32, C.c_int32, C.POINTER(VdetectStats)]),
+    "livo_cloud_publish": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.c_float, C.POINTER(CloudInfo)]),
+    "livo_cloud_info_get": (C.c_int, [_P, C.POINTER(CloudInfo)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -568,6 +578,21 @@ class Context:
         _check("livo_frame_to_world", self._L.livo_frame_to_world(self.h, sid, C.byref(st), _ptr(out), n.value,
                                                                   C.byref(n)))
         return out
+
+    def cloud_publish(self, state: dict, sid: int = -1, match_leaf: float = 0.2) -> dict:
+        """pcl_wait_pub at the end of a LiDAR frame (livo_cloud_publish): frame_to_world(state, sid) kept on
+        the device as CLOUD_WORLD for the camera frames that follow, and with match_leaf > 0 its VoxelGrid
+        (pg_down) as CLOUD_WORLD_DOWN.  Returns cloud_info()."""
+        st = state_to_c(state)
+        ci = CloudInfo()
+        _check("livo_cloud_publish", self._L.livo_cloud_publish(self.h, sid, C.byref(st), match_leaf, C.byref(ci)))
+        return {f: int(getattr(ci, f)) for f, _ in CloudInfo._fields_ if f != "pad_"}
+
+    def cloud_info(self) -> dict:
+        """The published cloud's n, n_down (-1: no pg_down), down_filtered and device_bytes."""
+        ci = CloudInfo()
+        _check("livo_cloud_info_get", self._L.livo_cloud_info_get(self.h, C.byref(ci)))
+        return {f: int(getattr(ci, f)) for f, _ in CloudInfo._fields_ if f != "pad_"}
 
     def colorize(self, state: dict, image_bgr, vio_params: VioParams, scan_id: int = -1):
         """publish_frame_world_rgb's coloured cloud (livo_cloud_colorize): the cloud of frame_to_world(state,

@@ -59,6 +59,7 @@ extern "C" {
 #endif
 
 /* 9: the resident visual map (livo_vmap_*) and livo_vio_match added (nothing else changed).
+ *    livo_cloud_publish, livo_cloud_info_get and the two LIVO_CLOUD_* ids added the same way.
  * 8: livo_vio_select added (nothing else changed).
  * 7: livo_cloud_colorize added (nothing else changed).
  * 5: livo_ivox_info grew add_passes (round 4).
@@ -843,6 +844,43 @@ typedef struct livo_vdetect_stats {
 int livo_vio_detect(livo_ctx* ctx, int32_t scan_id, int32_t frame_id, livo_state* state, const livo_state* prior,
                     const livo_vio_params* p, const livo_vdetect_params* d, const uint8_t* gray, int32_t width,
                     int32_t height, livo_vdetect_stats* stats);
+/* pcl_wait_pub and pg_down: what a LiDAR frame hands to the camera frames that follow it.
+ * Ids in the scan_id argument of the frame stages; no scan upload ever returns them (scan
+ * ids are small slot indices). */
+#define LIVO_CLOUD_WORLD      0x40000000  /* *pcl_wait_pub = *laserCloudWorld, laser_mapping.cpp:258-268 */
+#define LIVO_CLOUD_WORLD_DOWN 0x40000001  /* pg_down, lidar_selection.cpp:341-344 */
+typedef struct livo_cloud_info {
+    int64_t n;            /* points of the world cloud */
+    int64_t n_down;       /* points of pg_down; -1: not built (match_leaf <= 0) */
+    int32_t down_filtered;/* 0: PCL returned its input (dx*dy*dz > INT32_MAX) or not built */
+    int32_t pad_;
+    int64_t device_bytes;
+} livo_cloud_info;
+/* Stores the cloud of livo_frame_to_world(src_scan_id, lio_state) on the device: n x 5 floats
+ * in the caller's point order, bit for bit what that call returns (src_scan_id < 0: the last
+ * preprocessed frame at full resolution, else a resident scan).  The buffer belongs to the
+ * context and replaces the previous published cloud; it outlives the next
+ * livo_scan_preprocess, the release of the source scan and any map change, and is freed with
+ * the context.  match_leaf > 0 also builds pg_down: the PCL VoxelGrid of
+ * livo_scan_preprocess over the stored float world points at that leaf (centroids of all
+ * five columns, ascending leaf order; a leaf too small for 32-bit indices keeps the input,
+ * as PCL does).  The reference filters inside every detect; the filter is a function of the
+ * cloud alone, so one filter per LiDAR frame gives the same points.
+ * livo_frame_to_world, livo_cloud_colorize, livo_vio_select, livo_vio_match and
+ * livo_vio_detect take LIVO_CLOUD_WORLD and LIVO_CLOUD_WORLD_DOWN as scan_id: `state` then
+ * places the camera only and the points are read as stored (livo_frame_to_world ignores
+ * `state` but still requires it).  livo_vio_detect(LIVO_CLOUD_WORLD) runs its match on
+ * pg_down where it exists and its select on the full cloud, as the reference does: its
+ * chain is match(LIVO_CLOUD_WORLD_DOWN), select(LIVO_CLOUD_WORLD), then 3 to 6.  Both ids
+ * are LIVO_E_NOSCAN before the first publish, LIVO_CLOUD_WORLD_DOWN also after a publish
+ * with match_leaf <= 0, and both in every other entry point.
+ * LIVO_E_INVALID: ctx or lio_state NULL, a non-finite match_leaf, a cloud id as
+ * src_scan_id; LIVO_E_NOSCAN: an unknown scan; LIVO_E_RANGE: n > 2^31 - 1 - 256.  A refused
+ * call leaves the previous cloud as it was.  info may be NULL. */
+int livo_cloud_publish(livo_ctx* ctx, int32_t src_scan_id, const livo_state* lio_state, float match_leaf,
+                       livo_cloud_info* info);
+/* The published cloud's sizes; LIVO_E_NOSCAN before the first publish. */
+int livo_cloud_info_get(livo_ctx* ctx, livo_cloud_info* out);
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
