@@ -30,6 +30,7 @@ SOURCES = [
     ("livo_kernels.hip", True),
     ("ivox_kernels.hip", True),
     ("frontend_kernels.hip", True),
+    ("imu_kernels.hip", True),
     ("vio_kernels.hip", True),
     ("rgb_kernels.hip", True),
     ("vis_kernels.hip", True),

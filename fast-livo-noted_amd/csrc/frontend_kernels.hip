@@ -25,6 +25,7 @@
 
 #include "device_common.h"
 #include "livo_internal.h"
+#include "so3_device.h"
 
 namespace livo {
 
@@ -46,32 +47,6 @@ __global__ void k_fe_segment(const float* __restrict__ raw, int64_t n, const dou
             hi = mid;
     }
     seg_rev[n - 1 - i] = lo - 1;  // reversed: a prefix min-scan gives the suffix minimum
-}
-
-// Exp(ang_vel, dt) (so3_math.h:31-52)
-__device__ __forceinline__ void so3_exp_dt(const double* g, double dt, double* R) {
-    const double nrm = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    if (nrm > 0.0000001) {
-        const double r[3] = {g[0] / nrm, g[1] / nrm, g[2] / nrm};
-        const double K[9] = {0.0, -r[2], r[1], r[2], 0.0, -r[0], -r[1], r[0], 0.0};
-        const double ang = nrm * dt;
-        const double s = sin(ang), c1 = 1.0 - cos(ang);
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const double kk = ((c1 * K[i * 3 + 0]) * K[0 * 3 + j] + (c1 * K[i * 3 + 1]) * K[1 * 3 + j]) +
-                                  (c1 * K[i * 3 + 2]) * K[2 * 3 + j];
-                R[i * 3 + j] = (R[i * 3 + j] + s * K[i * 3 + j]) + kk;
-            }
-    }
-}
-
-__device__ __forceinline__ void m3v(const double* M, const double* v, double* o) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) o[i] = (M[i * 3 + 0] * v[0] + M[i * 3 + 1] * v[1]) + M[i * 3 + 2] * v[2];
 }
 
 // P_compensate = extR_Ri * (R_i * (R_LI * P_i + t_LI) + T_ei) - exrR_extT (IMU_Processing.cpp:356-370)

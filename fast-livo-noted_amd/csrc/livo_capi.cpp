@@ -384,6 +384,22 @@ struct UploadDev {
     }
 };
 
+// IMU forward propagation: a stream of its own (the calls touch neither the map nor
+// the scans, so they do not queue behind a batch in flight), one device and one pinned
+// staging area, and what livo_imu_propagate leaves for livo_scan_preprocess_imu.
+struct ImuDev {
+    hipStream_t st = nullptr;
+    void* buf = nullptr;   // states, carries, counts, jobs, samples, the batch's Pose6D rows
+    size_t bytes = 0;
+    void* pin = nullptr;   // the same layout up to the samples, page-locked
+    size_t pin_bytes = 0;
+    void* table = nullptr; // the resident table (rows x 22 doubles)
+    size_t table_bytes = 0;
+    int32_t rows = 0;      // 0: no table resident
+    bool sorted = true;    // its offset times are non-decreasing (the backward walk needs that)
+    double rot_end[9] = {}, pos_end[3] = {};
+};
+
 struct livo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -448,6 +464,7 @@ struct livo_ctx {
     const float* fe_raw = nullptr;     // the last preprocessed frame, de-skewed, full resolution (5 floats a point)
     int64_t fe_n = 0;
     WorldCloud wcloud;                 // livo_cloud_publish: pcl_wait_pub and pg_down
+    ImuDev imu;                        // livo_imu_propagate(_batch): stream, staging, the resident Pose6D table
     void* vio_buf = nullptr;           // VIO frame (image, points, partials, slot)
     size_t vio_bytes = 0;
     DevImage bgr_img;                  // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
@@ -555,6 +572,13 @@ static hipError_t event_wait(hipEvent_t ev) {
 
 static int set_device(livo_ctx* c) {
     return hipSetDevice(c->device) == hipSuccess ? LIVO_OK : LIVO_E_HIP;
+}
+
+// Devices the runtime sees (0 where it reports an error): the entry points added since the
+// context-free ones answer LIVO_E_HIP on it before they touch their context.
+static int hip_device_count() {
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 
 static int ensure_scratch(livo_ctx* c, size_t bytes) {
@@ -2073,6 +2097,11 @@ int livo_ctx_destroy(livo_ctx* c) {
     dyn_free(c->dyn);
     if (c->fe_buf) (void)hipFree(c->fe_buf);
     if (c->wcloud.buf) (void)hipFree(c->wcloud.buf);
+    if (c->imu.st) (void)hipStreamSynchronize(c->imu.st);
+    if (c->imu.buf) (void)hipFree(c->imu.buf);
+    if (c->imu.table) (void)hipFree(c->imu.table);
+    if (c->imu.pin) (void)hipHostFree(c->imu.pin);
+    if (c->imu.st) (void)hipStreamDestroy(c->imu.st);
     if (c->prim_tmp) (void)hipFree(c->prim_tmp);
     if (c->vio_buf) (void)hipFree(c->vio_buf);
     dev_free(c->bgr_img.p);
@@ -4157,16 +4186,20 @@ static int voxel_grid(livo_ctx* c, FrontParams& F, const unsigned* mm, float lea
     return LIVO_OK;
 }
 
-int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, const livo_imu_pose* poses,
-                         int32_t n_poses, const double rot_end[9], const double pos_end[3], float leaf_size,
-                         int32_t* scan_id, livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap,
-                         int64_t* n_down) {
-    if (!c || !scan_id || n < 0 || (n > 0 && !raw) || n_poses < 0 || (n_poses > 0 && !poses) ||
+// livo_scan_preprocess and livo_scan_preprocess_imu: the Pose6D table comes from the host
+// (poses, uploaded here) or lies on the device already (dev_poses, its order checked when
+// it was made: dev_sorted).
+static int scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, const livo_imu_pose* poses,
+                           const double* dev_poses, bool dev_sorted, int32_t n_poses, const double rot_end[9],
+                           const double pos_end[3], float leaf_size, int32_t* scan_id, livo_raw_point* undistorted,
+                           livo_raw_point* down, int64_t down_cap, int64_t* n_down) {
+    if (!c || !scan_id || n < 0 || (n > 0 && !raw) || n_poses < 0 || (n_poses > 0 && !poses && !dev_poses) ||
         !std::isfinite(leaf_size))
         return LIVO_E_INVALID;
     const bool deskew = n_poses >= 2 && n > 0;
     if (deskew && (!rot_end || !pos_end)) return LIVO_E_INVALID;
-    for (int32_t k = 1; k < n_poses; k++)
+    if (dev_poses && !dev_sorted) return LIVO_E_INVALID;
+    for (int32_t k = 1; k < n_poses && !dev_poses; k++)
         if (!(poses[k].offset_time >= poses[k - 1].offset_time)) return LIVO_E_INVALID;  // the walk needs sorted segments
     if (n > (int64_t)0x7FFFFFFF - kBlock) return LIVO_E_RANGE;
     if (set_device(c)) return LIVO_E_HIP;
@@ -4182,7 +4215,7 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
     const size_t nb = (size_t)std::max<int64_t>(n, 1);
     auto layout = [&](Carve k) {
         F.raw = k.take<float>(nb * 5);
-        F.poses = d_poses = k.take<double>((size_t)std::max(n_poses, 1) * 22);
+        F.poses = d_poses = k.take<double>((size_t)std::max(dev_poses ? 0 : n_poses, 1) * 22);
         F.seg = seg = k.take<int32_t>(nb);
         F.seg_rev = k.take<int32_t>(nb);
         voxel_grid_layout(F, k, nb);
@@ -4212,8 +4245,11 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
             F.pos_end[i] = pos_end[i];
         }
         static_assert(sizeof(livo_imu_pose) == 22 * sizeof(double), "Pose6D row");
-        HIP_TRY(hipMemcpyAsync(d_poses, poses, (size_t)n_poses * sizeof(livo_imu_pose), hipMemcpyHostToDevice,
-                               c->stream));
+        if (dev_poses)
+            F.poses = dev_poses;
+        else
+            HIP_TRY(hipMemcpyAsync(d_poses, poses, (size_t)n_poses * sizeof(livo_imu_pose), hipMemcpyHostToDevice,
+                                   c->stream));
         rc = launch_fe_segment(F, c->stream);
         if (!rc) {
             size_t tb = 0;
@@ -4248,6 +4284,217 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
     c->fe_raw = F.raw;  // feats_undistort stays resident until the next frame (livo_frame_to_world)
     c->fe_n = n;
     return scan_create_device(c, kept, 5, n_kept, scan_id);
+}
+
+int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, const livo_imu_pose* poses,
+                         int32_t n_poses, const double rot_end[9], const double pos_end[3], float leaf_size,
+                         int32_t* scan_id, livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap,
+                         int64_t* n_down) {
+    return scan_preprocess(c, raw, n, poses, nullptr, true, n_poses, rot_end, pos_end, leaf_size, scan_id,
+                           undistorted, down, down_cap, n_down);
+}
+
+int livo_scan_preprocess_imu(livo_ctx* c, const livo_raw_point* raw, int64_t n, float leaf_size, int32_t* scan_id,
+                             livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down) {
+    if (!c || !scan_id || n < 0 || (n > 0 && !raw) || !std::isfinite(leaf_size)) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (c->imu.rows <= 0) return LIVO_E_INVALID;  // no livo_imu_propagate yet
+    return scan_preprocess(c, raw, n, nullptr, (const double*)c->imu.table, c->imu.sorted, c->imu.rows,
+                           c->imu.rot_end, c->imu.pos_end, leaf_size, scan_id, undistorted, down, down_cap, n_down);
+}
+
+// ---- IMU initialisation and forward propagation (IMU_Processing.cpp:18-51, 92-197, 236-338) ----
+int livo_imu_params_default(livo_imu_params* p) {
+    if (!p) return LIVO_E_INVALID;
+    for (int k = 0; k < 3; k++) p->cov_acc[k] = p->cov_gyr[k] = p->cov_bias_gyr[k] = p->cov_bias_acc[k] = 0.1;
+    p->mean_acc[0] = p->mean_acc[1] = 0.0;
+    p->mean_acc[2] = -1.0;
+    return LIVO_OK;
+}
+
+int livo_imu_params_inited(livo_imu_params* p) {
+    if (!p) return LIVO_E_INVALID;
+    for (int k = 0; k < 3; k++) {
+        p->cov_acc[k] = p->cov_gyr[k] = 0.01;
+        p->cov_bias_gyr[k] = p->cov_bias_acc[k] = 0.0001;
+    }
+    return LIVO_OK;
+}
+
+static double norm3(const double* v) { return std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
+
+int livo_imu_init(livo_ctx*, const livo_imu_sample* imu, int32_t n, livo_imu_params* params, int32_t* init_iter_num,
+                  double mean_gyr[3], livo_state* state, int32_t* status) {
+    if (n < 0 || (n > 0 && !imu) || !params || !init_iter_num || !mean_gyr || !state || !status ||
+        *init_iter_num < 1)
+        return LIVO_E_INVALID;
+    *status = LIVO_IMU_INIT_COLLECTING;
+    if (n == 0) return LIVO_OK;  // Process2 returns before IMU_init on an empty meas.imu
+    // detectZeroVelocity: running mean and covariance over the samples
+    int N = *init_iter_num;
+    double* ma = params->mean_acc;
+    for (int32_t s = 0; s < n; s++) {
+        const double* cur_acc = imu[s].acc;
+        const double* cur_gyr = imu[s].gyr;
+        for (int k = 0; k < 3; k++) {
+            if (N == 1) {
+                ma[k] = cur_acc[k];
+                mean_gyr[k] = cur_gyr[k];
+            }
+            ma[k] += (cur_acc[k] - ma[k]) / N;
+            mean_gyr[k] += (cur_gyr[k] - mean_gyr[k]) / N;
+            const double da = cur_acc[k] - ma[k], dg = cur_gyr[k] - mean_gyr[k];
+            params->cov_acc[k] = params->cov_acc[k] * (N - 1.0) / N + da * da * (N - 1.0) / (N * N);
+            params->cov_gyr[k] = params->cov_gyr[k] * (N - 1.0) / N + dg * dg * (N - 1.0) / (N * N);
+        }
+        N++;
+    }
+    *init_iter_num = N;
+    const double na = norm3(ma);
+    const bool at_rest = std::fabs(na - 9.81) < 0.1 && std::fabs(norm3(mean_gyr)) < 0.1;
+    if (!at_rest) {  // Reset()
+        ma[0] = ma[1] = 0.0;
+        ma[2] = -1.0;
+        mean_gyr[0] = mean_gyr[1] = mean_gyr[2] = 0.0;
+        *init_iter_num = 1;
+        *status = LIVO_IMU_INIT_RESET;
+        return LIVO_OK;
+    }
+    if (N < 50) return LIVO_OK;
+    for (int k = 0; k < 3; k++) {
+        state->gravity[k] = -ma[k] / na * 9.81;
+        state->bias_g[k] = mean_gyr[k];
+    }
+    livo_imu_params_inited(params);
+    *status = LIVO_IMU_INIT_DONE;
+    return LIVO_OK;
+}
+
+// n jobs in one launch on the IMU stream.  table: job 0's rows go to the context's
+// resident table (livo_imu_propagate) instead of the staging area.
+static int imu_propagate(livo_ctx* c, int32_t n, const livo_imu_job* jobs, const livo_imu_params* params,
+                         livo_imu_carry* carries, livo_state* states, livo_imu_pose* poses, int32_t pose_cap,
+                         int32_t* n_poses, bool table) {
+    if (!c || n < 0 || (n > 0 && (!jobs || !carries || !states)) || !params || pose_cap < 0)
+        return LIVO_E_INVALID;
+    int64_t total = 0;
+    int32_t max_rows = 1;
+    for (int32_t j = 0; j < n; j++) {
+        if (jobs[j].n_imu < 0 || (jobs[j].n_imu > 0 && !jobs[j].imu)) return LIVO_E_INVALID;
+        int32_t rows = 1;  // IMUpose[0], then one row per sample not skipped at :251
+        for (int32_t s = 0; s < jobs[j].n_imu; s++)
+            if (!(jobs[j].imu[s].stamp < carries[j].last_lidar_end_time)) rows++;
+        if (poses && rows > pose_cap) return LIVO_E_RANGE;
+        max_rows = std::max(max_rows, rows);
+        total += jobs[j].n_imu;
+    }
+    if (total > (int64_t)0x7FFFFFFF) return LIVO_E_RANGE;
+    if (hip_device_count() <= 0 || set_device(c)) return LIVO_E_HIP;
+    if (n == 0) return LIVO_OK;
+    ImuDev& D = c->imu;
+    if (!lazy_stream(&D.st)) return LIVO_E_HIP;
+    const bool want_rows = poses != nullptr || table;
+    const int32_t dev_cap = want_rows ? max_rows : 0;
+    ImuBatch B{};
+    size_t io_bytes = 0, in_bytes = 0;  // states .. counts (copied back); .. samples (copied in)
+    double* d_rows = nullptr;
+    livo_state* h_states = nullptr;
+    livo_imu_carry* h_carries = nullptr;
+    int32_t* h_counts = nullptr;
+    ImuJobDev* h_jobs = nullptr;
+    livo_imu_sample* h_samples = nullptr;
+    auto layout = [&](Carve k, bool host) {
+        auto* s = k.take<livo_state>((size_t)n);
+        auto* cy = k.take<livo_imu_carry>((size_t)n);
+        auto* cnt = k.take<int32_t>((size_t)n);
+        io_bytes = k.total();
+        auto* jb = k.take<ImuJobDev>((size_t)n);
+        auto* sm = k.take<livo_imu_sample>((size_t)std::max<int64_t>(total, 1));
+        in_bytes = k.total();
+        if (host) {
+            h_states = s, h_carries = cy, h_counts = cnt, h_jobs = jb, h_samples = sm;
+        } else {
+            B.states = s, B.carries = cy, B.n_poses = cnt, B.jobs = jb, B.samples = sm;
+            if (!table) d_rows = k.take<double>((size_t)n * (size_t)dev_cap * 22);
+        }
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&D.buf, &D.bytes, layout(Carve{nullptr}, false)));
+    layout(Carve{(char*)D.buf}, false);
+    const size_t host_need = layout(Carve{nullptr}, true);
+    if (host_need > D.pin_bytes) {
+        if (D.pin) (void)hipHostFree(D.pin);
+        D.pin = nullptr;
+        D.pin_bytes = 0;
+        if (hipHostMalloc(&D.pin, host_need, hipHostMallocDefault) != hipSuccess) {
+            D.pin = nullptr;
+            return LIVO_E_OOM;
+        }
+        D.pin_bytes = host_need;
+    }
+    layout(Carve{(char*)D.pin}, true);
+    if (table) {
+        D.rows = 0;  // no table until this call has succeeded
+        RC_TRY(ensure_dev_bytes(&D.table, &D.table_bytes, (size_t)dev_cap * 22 * sizeof(double)));
+        d_rows = (double*)D.table;
+    }
+    int64_t at = 0;
+    for (int32_t j = 0; j < n; j++) {
+        h_states[j] = states[j];
+        h_carries[j] = carries[j];
+        h_jobs[j] = ImuJobDev{at, jobs[j].n_imu, 0, jobs[j].pcl_beg_time, jobs[j].pcl_end_time};
+        if (jobs[j].n_imu > 0) std::memcpy(h_samples + at, jobs[j].imu, (size_t)jobs[j].n_imu * sizeof(livo_imu_sample));
+        at += jobs[j].n_imu;
+    }
+    bool sorted = true;  // job 0's offset times, as the kernel writes them
+    if (table) {
+        double prev = 0.0;
+        for (int32_t s = 0; s < jobs[0].n_imu; s++) {
+            if (jobs[0].imu[s].stamp < carries[0].last_lidar_end_time) continue;
+            const double off = jobs[0].imu[s].stamp - jobs[0].pcl_beg_time;
+            if (!(off >= prev)) sorted = false;
+            prev = off;
+        }
+    }
+    B.poses = want_rows ? d_rows : nullptr;
+    B.pose_cap = dev_cap;
+    std::memcpy(B.cov_acc, params->cov_acc, sizeof(B.cov_acc));
+    std::memcpy(B.cov_gyr, params->cov_gyr, sizeof(B.cov_gyr));
+    std::memcpy(B.cov_bias_gyr, params->cov_bias_gyr, sizeof(B.cov_bias_gyr));
+    std::memcpy(B.cov_bias_acc, params->cov_bias_acc, sizeof(B.cov_bias_acc));
+    B.acc_norm = norm3(params->mean_acc);
+    HIP_TRY(hipMemcpyAsync(D.buf, D.pin, in_bytes, hipMemcpyHostToDevice, D.st));
+    RC_TRY(launch_imu_propagate(B, n, D.st));
+    HIP_TRY(hipMemcpyAsync(D.pin, D.buf, io_bytes, hipMemcpyDeviceToHost, D.st));
+    if (poses)
+        HIP_TRY(hipMemcpy2DAsync(poses, (size_t)pose_cap * sizeof(livo_imu_pose), d_rows,
+                                 (size_t)dev_cap * sizeof(livo_imu_pose), (size_t)dev_cap * sizeof(livo_imu_pose),
+                                 (size_t)n, hipMemcpyDeviceToHost, D.st));
+    HIP_TRY(stream_wait(D.st));
+    for (int32_t j = 0; j < n; j++) {
+        states[j] = h_states[j];
+        carries[j] = h_carries[j];
+        if (n_poses) n_poses[j] = h_counts[j];
+    }
+    if (table) {
+        std::memcpy(D.rot_end, states[0].rot, sizeof(D.rot_end));
+        std::memcpy(D.pos_end, states[0].pos, sizeof(D.pos_end));
+        D.sorted = sorted;
+        D.rows = h_counts[0];
+    }
+    return LIVO_OK;
+}
+
+int livo_imu_propagate_batch(livo_ctx* c, int32_t n, const livo_imu_job* jobs, const livo_imu_params* params,
+                             livo_imu_carry* carries, livo_state* states, livo_imu_pose* poses, int32_t pose_cap,
+                             int32_t* n_poses) {
+    return imu_propagate(c, n, jobs, params, carries, states, poses, pose_cap, n_poses, false);
+}
+
+int livo_imu_propagate(livo_ctx* c, const livo_imu_job* job, const livo_imu_params* params, livo_imu_carry* carry,
+                       livo_state* state, livo_imu_pose* poses, int32_t pose_cap, int32_t* n_poses) {
+    if (!job || !carry || !state) return LIVO_E_INVALID;
+    return imu_propagate(c, 1, job, params, carry, state, poses, pose_cap, n_poses, true);
 }
 
 int livo_vio_params_default(livo_vio_params* p) {

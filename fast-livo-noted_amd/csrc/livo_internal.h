@@ -593,6 +593,25 @@ int launch_fe_starts(const FrontParams& F, void* stream);
 int launch_fe_centroid(const FrontParams& F, int64_t n_vox, void* stream);
 int launch_fe_morton(const float* pts, int64_t n, int stride, const unsigned* minmax, float scale,
                      uint32_t* codes, uint32_t* iota, void* stream);
+// IMU forward propagation (imu_kernels.hip): n jobs, one wave each.
+struct ImuJobDev {
+    int64_t first;            // the job's first sample in ImuBatch::samples
+    int32_t n_imu;
+    int32_t pad_;
+    double pcl_beg, pcl_end;
+};
+struct ImuBatch {
+    const ImuJobDev* jobs;
+    const livo_imu_sample* samples;  // every job's samples, packed
+    livo_imu_carry* carries;         // in / out
+    livo_state* states;              // in / out
+    double* poses;                   // job j's Pose6D rows at poses + j * pose_cap * 22, or null
+    int32_t* n_poses;                // rows per job
+    int32_t pose_cap;
+    double cov_acc[3], cov_gyr[3], cov_bias_gyr[3], cov_bias_acc[3];
+    double acc_norm;                 // mean_acc.norm()
+};
+int launch_imu_propagate(const ImuBatch& B, int32_t n, void* stream);
 // A batch of at most kFeSegMax scans built in one pass (kernel argument table).
 constexpr int kFeSegMax = 16;  // (the scan index rides in the 32-bit sort key's bits 27..30)
 struct FeSegs {

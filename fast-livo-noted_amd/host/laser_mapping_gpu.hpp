@@ -92,6 +92,7 @@ public:
         check(livo_ctx_create(device, &p, &ctx_), "livo_ctx_create");
         check(livo_params_default(&params_), "livo_params_default");
         params_ = p;
+        check(livo_imu_params_default(&imu_params), "livo_imu_params_default");
     }
     ~LaserMappingGpu() {
         if (ctx_) {
@@ -141,6 +142,44 @@ public:
                                    nullptr, down, down_cap, &nd),
               "livo_scan_preprocess");
         adopt_scan(id, nd);
+    }
+
+    // p_imu->Process2(LidarMeasures, state, feats_undistort) behind IMU_init (laser_mapping.cpp:119,
+    // IMU_Processing.cpp:381-403): UndistortPcl's forward propagation of `state` over meas.imu
+    // (imu_params and imu_carry are ImuProcess's members), state_propagat = state
+    // (laser_mapping.cpp:122), and, with n > 0 points, the backward walk and downSizeFilterSurf
+    // through the table the propagation left on the device.  n == 0 is the camera frame
+    // (is_lidar_end == false, pcl_end_time = lidar_beg_time + img_offset_time): the propagated
+    // `state` is then what detectFromPublished() takes.  `down` as set_scan_raw's.
+    void Process2(const livo_imu_sample* imu, int32_t n_imu, double pcl_beg_time, double pcl_end_time,
+                  const livo_raw_point* raw, int64_t n, float filter_size_surf, livo_raw_point* down = nullptr,
+                  int64_t down_cap = 0) {
+        livo_imu_job job{};
+        job.imu = imu;
+        job.n_imu = n_imu;
+        job.pcl_beg_time = pcl_beg_time;
+        job.pcl_end_time = pcl_end_time;
+        check(livo_imu_propagate(ctx_, &job, &imu_params, &imu_carry, &state, nullptr, 0, nullptr),
+              "livo_imu_propagate");
+        state_propagat = state;
+        if (n <= 0) return;
+        int32_t id = -1;
+        int64_t nd = 0;
+        check(livo_scan_preprocess_imu(ctx_, raw, n, filter_size_surf, &id, nullptr, down, down_cap, &nd),
+              "livo_scan_preprocess_imu");
+        adopt_scan(id, nd);
+    }
+    // p_imu->IMU_init(meas, state, init_iter_num) (IMU_Processing.cpp:147-198) while imu_need_init:
+    // returns true once gravity and bias_g are set (imu_need_init_ = false).
+    bool IMU_init(const livo_imu_sample* imu, int32_t n_imu) {
+        int32_t status = LIVO_IMU_INIT_COLLECTING;
+        check(livo_imu_init(ctx_, imu, n_imu, &imu_params, &init_iter_num, mean_gyr, &state, &status), "livo_imu_init");
+        if (status == LIVO_IMU_INIT_RESET) {
+            imu_carry = livo_imu_carry{};  // Reset(): angvel_last, last_imu_
+        } else if (n_imu > 0) {
+            imu_carry.last_imu = imu[n_imu - 1];  // :149
+        }
+        return status == LIVO_IMU_INIT_DONE;
     }
 
     // map_incremental() (laser_mapping.cpp:329-389) at the updated state: the iVox branch
@@ -367,6 +406,12 @@ public:
     int64_t effct_feat_num = 0;
     int64_t feats_down_size = 0;
     int64_t points_added = 0, points_no_downsample = 0;  // last map_incremental
+    // ImuProcess's members (IMU_Processing.h): the noise terms and mean_acc, what UndistortPcl
+    // keeps between calls, and IMU_init's counters
+    livo_imu_params imu_params{};
+    livo_imu_carry imu_carry{};
+    int32_t init_iter_num = 1;
+    double mean_gyr[3] = {0.0, 0.0, 0.0};
 
 private:
     void adopt_scan(int32_t id, int64_t N) {

@@ -16,6 +16,8 @@ path:
     LidarSelector::addObservation        -> Context.vio_observe
     LidarSelector::detect (one frame)    -> Context.vio_detect, Context.vmap_release_frames
     pcl_wait_pub / pg_down (Run's tail)  -> Context.cloud_publish, CLOUD_WORLD, CLOUD_WORLD_DOWN
+    ImuProcess::IMU_init                 -> imu_init
+    ImuProcess::UndistortPcl (forward)   -> Context.imu_propagate(_batch), Context.scan_preprocess_imu
 
 There is no CPU fallback: loading fails loudly if the HIP library is missing,
 and every compute call raises LivoError when the GPU path fails.
@@ -265,6 +267,87 @@ class MapAddStats(C.Structure):
                 ("deferred", C.c_int64), ("map_points", C.c_int64)]
 
 
+class ImuSample(C.Structure):
+    _fields_ = [("stamp", C.c_double), ("acc", C.c_double * 3), ("gyr", C.c_double * 3)]
+
+
+class ImuParams(C.Structure):
+    _fields_ = [("cov_acc", C.c_double * 3), ("cov_gyr", C.c_double * 3), ("cov_bias_gyr", C.c_double * 3),
+                ("cov_bias_acc", C.c_double * 3), ("mean_acc", C.c_double * 3)]
+
+
+class ImuCarry(C.Structure):
+    _fields_ = [("last_imu", ImuSample), ("acc_s_last", C.c_double * 3), ("angvel_last", C.c_double * 3),
+                ("last_lidar_end_time", C.c_double)]
+
+
+class ImuJob(C.Structure):
+    _fields_ = [("imu", C.c_void_p), ("n_imu", C.c_int32), ("pcl_beg_time", C.c_double),
+                ("pcl_end_time", C.c_double)]
+
+
+IMU_INIT_COLLECTING, IMU_INIT_RESET, IMU_INIT_DONE = 0, 1, 2
+_IMU_PARAM_FIELDS = ("cov_acc", "cov_gyr", "cov_bias_gyr", "cov_bias_acc", "mean_acc")
+
+
+def imu_params_to_c(p: dict | None) -> ImuParams:
+    """None: the constructor's values (livo_imu_params_default); keys left out keep those."""
+    q = ImuParams()
+    _check("livo_imu_params_default", load().livo_imu_params_default(C.byref(q)))
+    for k, v in (p or {}).items():
+        getattr(q, k)[:] = np.asarray(v, np.float64).reshape(3).tolist()
+    return q
+
+
+def imu_params_from_c(q: ImuParams) -> dict:
+    return {k: np.array(getattr(q, k)[:]) for k in _IMU_PARAM_FIELDS}
+
+
+def imu_params_inited(p: dict | None = None) -> dict:
+    q = imu_params_to_c(p)
+    _check("livo_imu_params_inited", load().livo_imu_params_inited(C.byref(q)))
+    return imu_params_from_c(q)
+
+
+def imu_carry_to_c(c: dict) -> ImuCarry:
+    """carry: last_imu (7: stamp, acc, gyr), acc_s_last, angvel_last, last_lidar_end_time."""
+    q = ImuCarry()
+    li = np.asarray(c["last_imu"], np.float64).reshape(7)
+    q.last_imu.stamp = li[0]
+    q.last_imu.acc[:] = li[1:4].tolist()
+    q.last_imu.gyr[:] = li[4:7].tolist()
+    q.acc_s_last[:] = np.asarray(c["acc_s_last"], np.float64).reshape(3).tolist()
+    q.angvel_last[:] = np.asarray(c["angvel_last"], np.float64).reshape(3).tolist()
+    q.last_lidar_end_time = float(c["last_lidar_end_time"])
+    return q
+
+
+def imu_carry_from_c(q: ImuCarry) -> dict:
+    return {"last_imu": np.array([q.last_imu.stamp] + q.last_imu.acc[:] + q.last_imu.gyr[:]),
+            "acc_s_last": np.array(q.acc_s_last[:]), "angvel_last": np.array(q.angvel_last[:]),
+            "last_lidar_end_time": q.last_lidar_end_time}
+
+
+def new_imu_carry() -> dict:
+    """The constructor's carry: an empty last_imu_, zero rates, last_lidar_end_time_ 0."""
+    return {"last_imu": np.zeros(7), "acc_s_last": np.zeros(3), "angvel_last": np.zeros(3),
+            "last_lidar_end_time": 0.0}
+
+
+def imu_init(imu: np.ndarray, params: dict | None, init_iter_num: int, mean_gyr, state: dict):
+    """ImuProcess::IMU_init over meas.imu (n, 7: stamp, acc, gyr).  Host code: needs no GPU.
+    -> (status, params, init_iter_num, mean_gyr, state)."""
+    imu = np.ascontiguousarray(imu, np.float64).reshape(-1, 7)
+    q = imu_params_to_c(params)
+    it = C.c_int32(init_iter_num)
+    mg = np.ascontiguousarray(np.array(mean_gyr, np.float64).reshape(3))
+    s = state_to_c(state)
+    status = C.c_int32(-1)
+    _check("livo_imu_init", load().livo_imu_init(None, _ptr(imu), imu.shape[0], C.byref(q), C.byref(it), _ptr(mg),
+                                                 C.byref(s), C.byref(status)))
+    return status.value, imu_params_from_c(q), it.value, mg, state_from_c(s)
+
+
 SIGNATURES = {
     "livo_abi_version": (C.c_int, []),
     "livo_error_string": (C.c_char_p, [C.c_int]),
@@ -333,6 +416,15 @@ SIGNATURES = {
                                   C.POINTER(VdetectParams), _P, C.c_int32, C.c_int32, C.POINTER(VdetectStats)]),
     "livo_cloud_publish": (C.c_int, [_P, C.c_int32, C.POINTER(State), C.c_float, C.POINTER(CloudInfo)]),
     "livo_cloud_info_get": (C.c_int, [_P, C.POINTER(CloudInfo)]),
+    "livo_imu_params_default": (C.c_int, [C.POINTER(ImuParams)]),
+    "livo_imu_params_inited": (C.c_int, [C.POINTER(ImuParams)]),
+    "livo_imu_init": (C.c_int, [_P, _P, C.c_int32, C.POINTER(ImuParams), C.POINTER(C.c_int32), _P,
+                                C.POINTER(State), C.POINTER(C.c_int32)]),
+    "livo_imu_propagate_batch": (C.c_int, [_P, C.c_int32, _P, C.POINTER(ImuParams), _P, _P, _P, C.c_int32, _P]),
+    "livo_imu_propagate": (C.c_int, [_P, C.POINTER(ImuJob), C.POINTER(ImuParams), C.POINTER(ImuCarry),
+                                     C.POINTER(State), _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "livo_scan_preprocess_imu": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.POINTER(C.c_int32), _P, _P, C.c_int64,
+                                           C.POINTER(C.c_int64)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -847,6 +939,56 @@ class Context:
         _check("livo_scan_preprocess", self._L.livo_scan_preprocess(
             self.h, _ptr(raw), n, _ptr(poses), npo, _ptr(rot_end), _ptr(pos_end), leaf_size, C.byref(sid),
             _ptr(und), _ptr(down), n, C.byref(nd)))
+        self.scans[sid.value] = int(nd.value)
+        return sid.value, und, down[:nd.value].copy()
+
+    def imu_propagate(self, imu: np.ndarray, pcl_beg_time: float, pcl_end_time: float, params: dict | None,
+                      carry: dict, state: dict, want_poses: bool = True):
+        """UndistortPcl's forward propagation of one frame (livo_imu_propagate): imu (n, 7: stamp, acc, gyr)
+        is meas.imu.  -> (state, carry, poses (rows, 22) or None); the table and the end pose stay
+        resident for scan_preprocess_imu."""
+        imu = np.ascontiguousarray(imu, np.float64).reshape(-1, 7)
+        job = ImuJob(_ptr(imu).value if imu.shape[0] else None, imu.shape[0], pcl_beg_time, pcl_end_time)
+        q, cy, s = imu_params_to_c(params), imu_carry_to_c(carry), state_to_c(state)
+        cap = imu.shape[0] + 1
+        poses = np.zeros((cap, 22)) if want_poses else None
+        npo = C.c_int32()
+        _check("livo_imu_propagate", self._L.livo_imu_propagate(self.h, C.byref(job), C.byref(q), C.byref(cy),
+                                                                C.byref(s), _ptr(poses), cap, C.byref(npo)))
+        return state_from_c(s), imu_carry_from_c(cy), (poses[:npo.value].copy() if want_poses else None)
+
+    def imu_propagate_batch(self, jobs: list, params: dict | None, carries: list, states: list,
+                            want_poses: bool = True, pose_cap: int | None = None):
+        """n independent propagations in one launch (livo_imu_propagate_batch).  jobs: (imu (n_j, 7),
+        pcl_beg_time, pcl_end_time) each.  -> (states, carries, list of pose tables or None)."""
+        n = len(jobs)
+        imus = [np.ascontiguousarray(j[0], np.float64).reshape(-1, 7) for j in jobs]
+        cj = (ImuJob * max(n, 1))()
+        for k in range(n):
+            cj[k] = ImuJob(_ptr(imus[k]).value if imus[k].shape[0] else None, imus[k].shape[0], jobs[k][1],
+                           jobs[k][2])
+        cc = (ImuCarry * max(n, 1))(*[imu_carry_to_c(c) for c in carries])
+        cs = (State * max(n, 1))(*[state_to_c(s) for s in states])
+        cap = (max([m.shape[0] for m in imus] + [0]) + 1) if pose_cap is None else pose_cap
+        poses = np.zeros((max(n, 1), cap, 22)) if want_poses else None
+        cnt = np.zeros(max(n, 1), np.int32)
+        q = imu_params_to_c(params)
+        _check("livo_imu_propagate_batch", self._L.livo_imu_propagate_batch(
+            self.h, n, C.cast(cj, C.c_void_p), C.byref(q), C.cast(cc, C.c_void_p), C.cast(cs, C.c_void_p),
+            _ptr(poses), cap, _ptr(cnt)))
+        return ([state_from_c(cs[k]) for k in range(n)], [imu_carry_from_c(cc[k]) for k in range(n)],
+                [poses[k, :cnt[k]].copy() for k in range(n)] if want_poses else None)
+
+    def scan_preprocess_imu(self, raw: np.ndarray, leaf_size: float = 0.5):
+        """scan_preprocess with the resident table and end pose of the last imu_propagate."""
+        raw = np.ascontiguousarray(raw, np.float32).reshape(-1, 5)
+        n = raw.shape[0]
+        und = np.zeros_like(raw)
+        down = np.zeros_like(raw)
+        nd = C.c_int64()
+        sid = C.c_int32()
+        _check("livo_scan_preprocess_imu", self._L.livo_scan_preprocess_imu(
+            self.h, _ptr(raw), n, leaf_size, C.byref(sid), _ptr(und), _ptr(down), n, C.byref(nd)))
         self.scans[sid.value] = int(nd.value)
         return sid.value, und, down[:nd.value].copy()
 

@@ -60,6 +60,7 @@ extern "C" {
 
 /* 9: the resident visual map (livo_vmap_*) and livo_vio_match added (nothing else changed).
  *    livo_cloud_publish, livo_cloud_info_get and the two LIVO_CLOUD_* ids added the same way.
+ *    livo_imu_* (params, init, propagate, propagate_batch) and livo_scan_preprocess_imu too.
  * 8: livo_vio_select added (nothing else changed).
  * 7: livo_cloud_colorize added (nothing else changed).
  * 5: livo_ivox_info grew add_passes (round 4).
@@ -881,6 +882,73 @@ int livo_cloud_publish(livo_ctx* ctx, int32_t src_scan_id, const livo_state* lio
                        livo_cloud_info* info);
 /* The published cloud's sizes; LIVO_E_NOSCAN before the first publish. */
 int livo_cloud_info_get(livo_ctx* ctx, livo_cloud_info* out);
+
+/* ------------------------------------------------------------------------
+ * IMU forward propagation: ImuProcess::IMU_init / detectZeroVelocity
+ * (src/IMU_Processing.cpp:92-197) and the first half of UndistortPcl
+ * (:236-338), the step that produces the state every other entry point takes
+ * ("after propagation"), its 18 x 18 covariance and the Pose6D table.
+ * ------------------------------------------------------------------------ */
+typedef struct livo_imu_sample { double stamp; double acc[3]; double gyr[3]; } livo_imu_sample;   /* sensor_msgs::Imu, seconds */
+
+typedef struct livo_imu_params {       /* ImuProcess members the propagation reads */
+    double cov_acc[3], cov_gyr[3], cov_bias_gyr[3], cov_bias_acc[3];
+    double mean_acc[3];                 /* only G_m_s2 / |mean_acc| is used */
+} livo_imu_params;
+
+typedef struct livo_imu_carry {        /* what UndistortPcl keeps between calls */
+    livo_imu_sample last_imu;           /* last_imu_      */
+    double acc_s_last[3], angvel_last[3];
+    double last_lidar_end_time;         /* last_lidar_end_time_ */
+} livo_imu_carry;
+
+typedef struct livo_imu_job {
+    const livo_imu_sample* imu; int32_t n_imu;   /* meas.imu, without last_imu_ (the call pushes it in front) */
+    double pcl_beg_time, pcl_end_time;           /* as computed at :211 and :219-221 */
+} livo_imu_job;
+
+enum {
+    LIVO_IMU_INIT_COLLECTING = 0, /* init_iter_num < 50 (:159-163)                              */
+    LIVO_IMU_INIT_RESET = 1,      /* not at rest: Reset() (:38-51, :153-157)                     */
+    LIVO_IMU_INIT_DONE = 2        /* gravity, bias_g and the params' _inited values set (:184-196) */
+};
+
+/* The constructor's values (:18-34) and the values IMU_init leaves behind (:190-194: 0.01, 0.01,
+ * 1e-4, 1e-4; mean_acc is kept).  Host code. */
+int livo_imu_params_default(livo_imu_params* p);
+int livo_imu_params_inited(livo_imu_params* p);
+/* IMU_init with detectZeroVelocity over meas.imu (n samples): the running means and covariances
+ * in params->mean_acc / cov_acc / cov_gyr and mean_gyr, counted by *init_iter_num (1 at the
+ * start, as the constructor sets it).  *status: LIVO_IMU_INIT_*.  On RESET mean_acc, mean_gyr
+ * and *init_iter_num take Reset()'s values (the caller clears its carry, as Reset() does); on
+ * DONE state->gravity = -mean_acc / |mean_acc| * 9.81, state->bias_g = mean_gyr and the
+ * covariances take livo_imu_params_inited's values.  In every case the caller's carry takes
+ * last_imu = imu[n - 1] (:149) unless it was reset.  n == 0 changes nothing (Process2 :390).
+ * Plain host code, no device needed: ctx is not used and may be NULL. */
+int livo_imu_init(livo_ctx* ctx, const livo_imu_sample* imu, int32_t n, livo_imu_params* params,
+                  int32_t* init_iter_num, double mean_gyr[3], livo_state* state, int32_t* status);
+/* n independent forward propagations (:236-338) in one launch, one wave per job.  Job j reads
+ * jobs[j], carries[j], states[j]; it writes the propagated state (rot, pos, vel at
+ * pcl_end_time, the covariance F_x P F_x^T + cov_w per sample), the updated carry, and, with
+ * poses != NULL, its Pose6D table at poses + j * pose_cap: row 0 from the carry and the
+ * incoming state (:238), then one row per propagated sample; n_poses[j] = its rows (n_poses may
+ * be NULL).  Samples whose stamp lies before carry.last_lidar_end_time are skipped (:251).
+ * LIVO_E_RANGE, before anything runs, if poses != NULL and a job's table exceeds pose_cap
+ * (n_imu + 1 rows always suffice).  Touches neither the map nor the scans: allowed while
+ * batches are in flight. */
+int livo_imu_propagate_batch(livo_ctx* ctx, int32_t n, const livo_imu_job* jobs, const livo_imu_params* params,
+                             livo_imu_carry* carries, livo_state* states, livo_imu_pose* poses, int32_t pose_cap,
+                             int32_t* n_poses);
+/* The batch with n = 1; it also leaves the table and the frame-end pose resident in the
+ * context for livo_scan_preprocess_imu (replacing those of the previous call; a camera frame
+ * propagates with no points behind it).  poses and n_poses may be NULL. */
+int livo_imu_propagate(livo_ctx* ctx, const livo_imu_job* job, const livo_imu_params* params, livo_imu_carry* carry,
+                       livo_state* state, livo_imu_pose* poses, int32_t pose_cap, int32_t* n_poses);
+/* livo_scan_preprocess with the table and the end pose of the last livo_imu_propagate, read
+ * where they lie on the device.  LIVO_E_INVALID if no table is resident. */
+int livo_scan_preprocess_imu(livo_ctx* ctx, const livo_raw_point* raw, int64_t n, float leaf_size, int32_t* scan_id,
+                             livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down);
+
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
