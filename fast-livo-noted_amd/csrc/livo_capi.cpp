@@ -400,6 +400,18 @@ struct ImuDev {
     double rot_end[9] = {}, pos_end[3] = {};
 };
 
+// The sensor handlers' frame (livo_frame_ingest_*): one allocation holds the uploaded message,
+// the passes' scratch and the resident result, the time-ordered frame with its sorted keys.
+struct IngestDev {
+    void* buf = nullptr;
+    size_t bytes = 0;
+    const float* frame = nullptr;     // n_kept x 5 floats, ascending time (meas.lidar)
+    const uint32_t* skeys = nullptr;  // their order-preserving time keys
+    unsigned* ctr = nullptr;          // kIngCtr*
+    bool have = false;                // an ingest has succeeded
+    livo_ingest_info info{};
+};
+
 struct livo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -465,6 +477,7 @@ struct livo_ctx {
     int64_t fe_n = 0;
     WorldCloud wcloud;                 // livo_cloud_publish: pcl_wait_pub and pg_down
     ImuDev imu;                        // livo_imu_propagate(_batch): stream, staging, the resident Pose6D table
+    IngestDev ing;                     // livo_frame_ingest_*: the current frame and its cursor
     void* vio_buf = nullptr;           // VIO frame (image, points, partials, slot)
     size_t vio_bytes = 0;
     DevImage bgr_img;                  // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
@@ -2097,6 +2110,7 @@ int livo_ctx_destroy(livo_ctx* c) {
     dyn_free(c->dyn);
     if (c->fe_buf) (void)hipFree(c->fe_buf);
     if (c->wcloud.buf) (void)hipFree(c->wcloud.buf);
+    if (c->ing.buf) (void)hipFree(c->ing.buf);
     if (c->imu.st) (void)hipStreamSynchronize(c->imu.st);
     if (c->imu.buf) (void)hipFree(c->imu.buf);
     if (c->imu.table) (void)hipFree(c->imu.table);
@@ -4188,8 +4202,9 @@ static int voxel_grid(livo_ctx* c, FrontParams& F, const unsigned* mm, float lea
 
 // livo_scan_preprocess and livo_scan_preprocess_imu: the Pose6D table comes from the host
 // (poses, uploaded here) or lies on the device already (dev_poses, its order checked when
-// it was made: dev_sorted).
-static int scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, const livo_imu_pose* poses,
+// it was made: dev_sorted).  The points come from the host or, with raw_dev, from the device
+// (livo_frame_take: a range of the ingested frame).
+static int scan_preprocess(livo_ctx* c, const livo_raw_point* raw, bool raw_dev, int64_t n, const livo_imu_pose* poses,
                            const double* dev_poses, bool dev_sorted, int32_t n_poses, const double rot_end[9],
                            const double pos_end[3], float leaf_size, int32_t* scan_id, livo_raw_point* undistorted,
                            livo_raw_point* down, int64_t down_cap, int64_t* n_down) {
@@ -4229,7 +4244,9 @@ static int scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, co
     F.np = n_poses;
     std::memcpy(F.R_LI, c->params.R_LI, sizeof(F.R_LI));
     std::memcpy(F.t_LI, c->params.t_LI, sizeof(F.t_LI));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(F.raw, raw, (size_t)n * 20, hipMemcpyHostToDevice, c->stream));
+    if (n > 0)
+        HIP_TRY(hipMemcpyAsync(F.raw, raw, (size_t)n * 20, raw_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                               c->stream));
     int rc = LIVO_OK;
     if (deskew) {
         // extR_Ri = R_LI^T rot_end^T, exrR_extT = R_LI^T t_LI (IMU_Processing.cpp:337-338)
@@ -4290,7 +4307,7 @@ int livo_scan_preprocess(livo_ctx* c, const livo_raw_point* raw, int64_t n, cons
                          int32_t n_poses, const double rot_end[9], const double pos_end[3], float leaf_size,
                          int32_t* scan_id, livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap,
                          int64_t* n_down) {
-    return scan_preprocess(c, raw, n, poses, nullptr, true, n_poses, rot_end, pos_end, leaf_size, scan_id,
+    return scan_preprocess(c, raw, false, n, poses, nullptr, true, n_poses, rot_end, pos_end, leaf_size, scan_id,
                            undistorted, down, down_cap, n_down);
 }
 
@@ -4299,7 +4316,7 @@ int livo_scan_preprocess_imu(livo_ctx* c, const livo_raw_point* raw, int64_t n, 
     if (!c || !scan_id || n < 0 || (n > 0 && !raw) || !std::isfinite(leaf_size)) return LIVO_E_INVALID;
     if (hip_device_count() <= 0) return LIVO_E_HIP;
     if (c->imu.rows <= 0) return LIVO_E_INVALID;  // no livo_imu_propagate yet
-    return scan_preprocess(c, raw, n, nullptr, (const double*)c->imu.table, c->imu.sorted, c->imu.rows,
+    return scan_preprocess(c, raw, false, n, nullptr, (const double*)c->imu.table, c->imu.sorted, c->imu.rows,
                            c->imu.rot_end, c->imu.pos_end, leaf_size, scan_id, undistorted, down, down_cap, n_down);
 }
 
@@ -4495,6 +4512,175 @@ int livo_imu_propagate(livo_ctx* c, const livo_imu_job* job, const livo_imu_para
                        livo_state* state, livo_imu_pose* poses, int32_t pose_cap, int32_t* n_poses) {
     if (!job || !carry || !state) return LIVO_E_INVALID;
     return imu_propagate(c, 1, job, params, carry, state, poses, pose_cap, n_poses, true);
+}
+
+// ---- Sensor handlers: the driver's message to the time-ordered frame (preprocess.cpp:82-116,
+// laser_mapping.cpp:705, IMU_Processing.cpp:217-235) ----
+int livo_ingest_params_default(livo_ingest_params* p) {
+    if (!p) return LIVO_E_INVALID;
+    p->lidar_type = LIVO_LIDAR_AVIA;  // laser_mapping.cpp:989-993
+    p->n_scans = 16;
+    p->point_filter_num = 2;
+    p->reserved = 0;
+    p->blind = 0.01;
+    return LIVO_OK;
+}
+
+// The message of n records of rec bytes -> the context's frame.  L: the cloud's layout (null: Avia).
+static int frame_ingest(livo_ctx* c, const livo_ingest_params* p, const void* data, int64_t n, int64_t rec,
+                        const livo_cloud_layout* L, livo_ingest_info* info) {
+    if (n > (int64_t)0x7FFFFFFF - kBlock) return LIVO_E_RANGE;
+    IngestParams P{};
+    P.n = n;
+    P.lidar_type = p->lidar_type;
+    P.n_scans = p->n_scans;
+    P.filter_num = p->point_filter_num;
+    P.blind = p->blind;
+    if (L) P.L = *L;
+    if (n > 0 && p->lidar_type == LIVO_LIDAR_VELO16) {
+        float t;  // pl_orig.points[plsize - 1].time (:479)
+        std::memcpy(&t, (const char*)data + (n - 1) * rec + L->off_time, 4);
+        if (!(t > 0.f)) return LIVO_E_INVALID;  // given_offset_time == false: the times from yaw, not built
+    }
+    if (n > 0 && p->lidar_type == LIVO_LIDAR_XT32) std::memcpy(&P.time_head, (const char*)data + L->off_time, 8);
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
+    if (set_device(c)) return LIVO_E_HIP;
+    IngestDev& D = c->ing;
+    D.have = false;  // no frame until this call has succeeded
+    const size_t nb = (size_t)std::max<int64_t>(n, 1);
+    unsigned char* msg;
+    uint32_t *pos, *skeys, *svals;
+    float* frame;
+    auto layout = [&](Carve k) {
+        msg = k.take<unsigned char>(nb * (size_t)rec + 4);  // (k_ingest_cloud reads whole words)
+        P.dec = k.take<float>(nb * 5);
+        P.flags = k.take<uint32_t>(nb);
+        pos = k.take<uint32_t>(nb);
+        P.pts = k.take<float>(nb * 5);
+        P.keys = k.take<uint32_t>(nb);
+        P.iota = k.take<uint32_t>(nb);
+        skeys = k.take<uint32_t>(nb);
+        svals = k.take<uint32_t>(nb);
+        frame = k.take<float>(nb * 5);
+        P.ctr = k.take<unsigned>(kIngCtrN);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&D.buf, &D.bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)D.buf});
+    P.msg = msg;
+    P.pos = pos;
+    livo_ingest_info I{};
+    I.n_in = n;
+    if (n > 0) {
+        HIP_TRY(hipMemsetAsync(P.ctr, 0, kIngCtrN * sizeof(unsigned), c->stream));
+        HIP_TRY(hipMemcpyAsync(msg, data, (size_t)n * (size_t)rec, hipMemcpyHostToDevice, c->stream));
+        RC_TRY(launch_ingest_decode(P, c->stream));
+        RC_TRY(scan_u32(c, P.flags, pos, n));
+        RC_TRY(launch_ingest_emit(P, c->stream));
+        unsigned h[3];
+        HIP_TRY(hipMemcpyAsync(h, P.ctr, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(stream_wait(c->stream));
+        const int64_t total = h[kIngCtrTotal];
+        I.n_kept = p->lidar_type == LIVO_LIDAR_AVIA ? total / p->point_filter_num : total;
+        I.n_rejected = n - (int64_t)h[kIngCtrPass];
+        I.n_decimated = (int64_t)h[kIngCtrPass] - I.n_kept;
+        if (I.n_kept > 0) {
+            const unsigned o = h[kIngCtrMaxKey], u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+            std::memcpy(&I.end_curvature, &u, 4);
+            // the stable sort by time and its permutation applied: queued, the calls that read the frame follow
+            RC_TRY(sort_u32(c, P.keys, skeys, P.iota, svals, I.n_kept, 32));
+            RC_TRY(launch_ingest_gather(P.pts, svals, I.n_kept, frame, c->stream));
+        }
+    }
+    D.frame = frame;
+    D.skeys = skeys;
+    D.ctr = P.ctr;
+    D.info = I;
+    D.have = true;
+    if (info) *info = I;
+    return LIVO_OK;
+}
+
+static bool ingest_params_ok(const livo_ingest_params* p) {
+    return p && p->point_filter_num >= 1 && p->n_scans >= 0;
+}
+
+int livo_frame_ingest_livox(livo_ctx* c, const livo_ingest_params* p, const livo_livox_point* pts, int64_t n,
+                            livo_ingest_info* info) {
+    if (!c || !ingest_params_ok(p) || p->lidar_type != LIVO_LIDAR_AVIA || n < 0 || (n > 0 && !pts))
+        return LIVO_E_INVALID;
+    return frame_ingest(c, p, pts, n, sizeof(livo_livox_point), nullptr, info);
+}
+
+int livo_frame_ingest_cloud(livo_ctx* c, const livo_ingest_params* p, const void* data, int64_t n,
+                            const livo_cloud_layout* L, livo_ingest_info* info) {
+    if (!c || !ingest_params_ok(p) || !L || n < 0 || (n > 0 && !data)) return LIVO_E_INVALID;
+    if (p->lidar_type != LIVO_LIDAR_VELO16 && p->lidar_type != LIVO_LIDAR_OUST64 && p->lidar_type != LIVO_LIDAR_XT32)
+        return LIVO_E_INVALID;
+    if (L->point_step < 1 || L->point_step > kIngestMaxStep) return LIVO_E_INVALID;
+    const int32_t offs[5] = {L->off_x, L->off_y, L->off_z, L->off_intensity, L->off_time};
+    for (int k = 0; k < 5; k++) {
+        const int32_t width = (k == 4 && p->lidar_type == LIVO_LIDAR_XT32) ? 8 : 4;
+        if (offs[k] < 0 || offs[k] > L->point_step - width) return LIVO_E_INVALID;
+    }
+    return frame_ingest(c, p, data, n, L->point_step, L, info);
+}
+
+int livo_frame_info(livo_ctx* c, livo_ingest_info* info) {
+    if (!c || !info) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (!c->ing.have) return LIVO_E_INVALID;
+    *info = c->ing.info;
+    return LIVO_OK;
+}
+
+int livo_frame_dump(livo_ctx* c, livo_raw_point* out, int64_t cap, int64_t* n) {
+    if (!c || !n) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (!c->ing.have) return LIVO_E_INVALID;
+    const int64_t m = c->ing.info.n_kept;
+    *n = m;
+    if (!out || m == 0) return LIVO_OK;
+    if (cap < m) return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    HIP_TRY(hipMemcpyAsync(out, c->ing.frame, (size_t)m * 20, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(stream_wait(c->stream));
+    return LIVO_OK;
+}
+
+int livo_frame_take(livo_ctx* c, double offset_limit_ms, int is_lidar_end, float leaf_size, int32_t* scan_id,
+                    livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down,
+                    int64_t* n_taken) {
+    if (!c || !n_taken || (scan_id && !std::isfinite(leaf_size))) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
+    IngestDev& D = c->ing;
+    if (!D.have) return LIVO_E_INVALID;
+    if (scan_id && c->imu.rows <= 0) return LIVO_E_INVALID;  // no livo_imu_propagate yet
+    if (set_device(c)) return LIVO_E_HIP;
+    const int64_t from = D.info.cursor;
+    unsigned cnt = 0;
+    if (from < D.info.n_kept) {
+        RC_TRY(launch_ingest_take_count(D.skeys, from, D.info.n_kept, offset_limit_ms, D.ctr + kIngCtrTake, c->stream));
+        HIP_TRY(hipMemcpyAsync(&cnt, D.ctr + kIngCtrTake, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(stream_wait(c->stream));
+    }
+    if (scan_id) {
+        if (cnt == 0) {  // an empty feats_undistort: no scan
+            c->fe_raw = nullptr;
+            c->fe_n = 0;
+            *scan_id = -1;
+            if (n_down) *n_down = 0;
+        } else {
+            RC_TRY(scan_preprocess(c, reinterpret_cast<const livo_raw_point*>(D.frame + 5 * from), true, (int64_t)cnt,
+                                   nullptr, (const double*)c->imu.table, c->imu.sorted, c->imu.rows, c->imu.rot_end,
+                                   c->imu.pos_end, leaf_size, scan_id, undistorted, down, down_cap, n_down));
+        }
+    }
+    D.info.cursor = is_lidar_end ? 0 : from + (int64_t)cnt;  // (:229, :232-235)
+    *n_taken = (int64_t)cnt;
+    return LIVO_OK;
 }
 
 int livo_vio_params_default(livo_vio_params* p) {

@@ -612,6 +612,32 @@ struct ImuBatch {
     double acc_norm;                 // mean_acc.norm()
 };
 int launch_imu_propagate(const ImuBatch& B, int32_t n, void* stream);
+// Sensor handlers (ingest_kernels.hip): the driver's message to the time-ordered frame.
+constexpr int kIngestBlock = 256;     // message points per block of the decode and emit passes
+constexpr int kIngestMaxStep = 240;   // largest point_step: a block's records fit 60 KiB of LDS
+enum { kIngCtrPass = 0, kIngCtrTotal = 1, kIngCtrMaxKey = 2, kIngCtrTake = 3, kIngCtrN = 4 };
+struct IngestParams {
+    const unsigned char* msg;   // the message's records as uploaded (20 B, or L.point_step B each)
+    int64_t n;
+    int32_t lidar_type, n_scans, filter_num;
+    double blind;
+    livo_cloud_layout L;        // livo_frame_ingest_cloud only
+    double time_head;           // XT32: points[0].timestamp
+    float* dec;                 // n x 5: every message point as its handler would emit it
+    uint32_t* flags;            // n: AVIA the handler's survivors; else survivors with i % filter_num == 0
+    const uint32_t* pos;        // n: exclusive scan of flags
+    float* pts;                 // the kept points, message order
+    uint32_t* keys;             // ... their order-preserving time keys
+    uint32_t* iota;
+    unsigned* ctr;              // kIngCtr*
+};
+int launch_ingest_decode(const IngestParams& P, void* stream);
+int launch_ingest_emit(const IngestParams& P, void* stream);
+// frame[k] = pts[perm[k]], 5 floats each
+int launch_ingest_gather(const float* pts, const uint32_t* perm, int64_t n, float* frame, void* stream);
+// *count = points of the sorted keys [from, n) in front of the first whose time exceeds limit_ms
+int launch_ingest_take_count(const uint32_t* skeys, int64_t from, int64_t n, double limit_ms, unsigned* count,
+                             void* stream);
 // A batch of at most kFeSegMax scans built in one pass (kernel argument table).
 constexpr int kFeSegMax = 16;  // (the scan index rides in the 32-bit sort key's bits 27..30)
 struct FeSegs {

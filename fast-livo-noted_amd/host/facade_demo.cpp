@@ -10,7 +10,15 @@
 // With "ivox": the map goes in through ivox_->AddPoints (the reference's
 // default backend) and a final "incr <added> <no_downsample>" line reports
 // map_incremental() at the updated state.
+// With "ingest": a synthetic Avia message made from the scan (split by one image 30 ms into it)
+// goes through livox_pcl_cbk -> Process2 (camera frame) -> Process2 (LiDAR frame) -> iterate ->
+// map_incremental on the iVox backend, the frame never leaving the device; "ingest_host" runs the
+// same message through a host restatement of avia_handler, the time sort and the slice and the
+// Process2 that takes a host array.  Both print "take <camera> <lidar>", the "iekf" line and
+// "incr"; tests/test_facade_ingest.py compares them.
 // Exit status: 0 ok, 2 usage/IO, 3 livo::Error (code printed on stderr).
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -56,13 +64,104 @@ std::vector<char> slurp(const char* path) {
     return b;
 }
 
+void print_iekf(const livo_iter_stats& it, const States& s1) {
+    std::printf("iekf %d %d", it.iterations, it.converged);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) std::printf(" %.17g", s1.rot_end(i, j));
+    for (int i = 0; i < 3; i++) std::printf(" %.17g", s1.pos_end(i));
+    for (int i = 0; i < 18; i++)
+        for (int j = 0; j < 18; j++) std::printf(" %.17g", s1.cov(i, j));
+    std::printf("\n");
+}
+
+// avia_handler with feature_enabled == false (preprocess.cpp:315-349), as a caller restates it
+std::vector<livo_raw_point> avia_handler_host(const std::vector<livo_livox_point>& msg, const livo_ingest_params& q) {
+    std::vector<livo_raw_point> out;
+    unsigned effect_ind = 0;
+    for (size_t i = 1; i < msg.size(); i++) {
+        const livo_livox_point &a = msg[i], &b = msg[i - 1];
+        const double range = a.x * a.x + a.y * a.y;
+        if (std::abs(a.x - b.x) < 1e-8 || std::abs(a.y - b.y) < 1e-8 || std::abs(a.z - b.z) < 1e-8 || range < q.blind ||
+            range > 900 || a.line > q.n_scans || (a.tag & 0x30) != 0x10)
+            continue;
+        effect_ind++;
+        if (effect_ind % q.point_filter_num == 0)
+            out.push_back({a.x, a.y, a.z, std::sqrt(a.x * a.x + a.y * a.y + a.z * a.z), a.offset_time / float(1000000)});
+    }
+    return out;
+}
+
+// The ingest modes (see the head of the file).  scan: body-frame xyz triples.
+void run_ingest(livo::LaserMappingGpu& lm, const float* scan, int64_t n, bool on_device) {
+    const double stamp = 1000.0, img_offset_time = 0.03;
+    std::vector<livo_livox_point> msg((size_t)n + 1);
+    for (int64_t i = 0; i <= n; i++) {
+        livo_livox_point& p = msg[(size_t)i];
+        const float* s = scan + 3 * (i > 0 ? i - 1 : 0);
+        p.x = s[0], p.y = s[1], p.z = s[2];
+        // a twentieth of the points at time 0 (a camera frame inside the scan consumes them), the
+        // rest spread over 100 ms out of order
+        p.offset_time = i % 20 == 0 ? 0u : (uint32_t)((i * 7919) % n) * (uint32_t)(100000000 / n);
+        p.reflectivity = 100, p.tag = 0x10, p.line = (uint8_t)(i % 6), p.pad = 0;
+    }
+    // an IMU at rest at the state: 5 ms samples from the stamp to 105 ms
+    std::vector<livo_imu_sample> imu(22);
+    double f[3];
+    for (int k = 0; k < 3; k++)
+        f[k] = -(lm.state.rot[0 + k] * lm.state.gravity[0] + lm.state.rot[3 + k] * lm.state.gravity[1] +
+                 lm.state.rot[6 + k] * lm.state.gravity[2]) + lm.state.bias_a[k];
+    for (int s = 0; s < 22; s++) {
+        imu[(size_t)s].stamp = stamp + 0.005 * s;
+        for (int k = 0; k < 3; k++) {
+            imu[(size_t)s].acc[k] = f[k];
+            imu[(size_t)s].gyr[k] = lm.state.bias_g[k] + 0.01 * (k - 1);
+            lm.imu_params.mean_acc[k] = f[k];
+        }
+    }
+    lm.imu_carry = livo_imu_carry{};
+    lm.imu_carry.last_imu = imu[0];
+    lm.imu_carry.last_lidar_end_time = stamp;
+    const int n_cam = 7;  // samples 1..6 lie before the image at 30 ms, sample 7 closes its interval
+    const float fs = 0.2f;
+    int64_t taken[2] = {0, 0};
+    if (on_device) {
+        lm.livox_pcl_cbk(msg.data(), (int64_t)msg.size(), stamp);
+        taken[0] = lm.Process2(imu.data() + 1, n_cam, false, img_offset_time, fs);
+        taken[1] = lm.Process2(imu.data() + 1 + n_cam, 21 - n_cam, true, 0.0, fs);
+    } else {
+        std::vector<livo_raw_point> pts = avia_handler_host(msg, lm.ingest_params);
+        std::stable_sort(pts.begin(), pts.end(),
+                         [](const livo_raw_point& a, const livo_raw_point& b) { return a.curvature < b.curvature; });
+        const double end_time = stamp + pts.back().curvature / double(1000);
+        size_t cursor = 0;
+        while (cursor < pts.size() && pts[cursor].curvature <= 0.0) cursor++;  // the camera frame's slice
+        taken[0] = (int64_t)cursor;
+        lm.Process2(imu.data() + 1, n_cam, stamp, stamp + img_offset_time, nullptr, 0, fs);
+        const double limit = (end_time - stamp) * double(1000);
+        size_t last = cursor;
+        while (last < pts.size() && pts[last].curvature <= limit) last++;
+        taken[1] = (int64_t)(last - cursor);
+        lm.Process2(imu.data() + 1 + n_cam, 21 - n_cam, stamp + img_offset_time, end_time, pts.data() + cursor,
+                    taken[1], fs);
+    }
+    std::printf("take %lld %lld\n", (long long)taken[0], (long long)taken[1]);
+    const livo_iter_stats it = lm.iterate();
+    States s1;
+    lm.get_state(s1);
+    print_iekf(it, s1);
+    lm.map_incremental(0.5);
+    std::printf("incr %lld %lld\n", (long long)lm.points_added, (long long)lm.points_no_downsample);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc != 5 && !(argc == 6 && std::string(argv[5]) == "ivox")) {
-        std::fprintf(stderr, "usage: %s map.f32 scan.f32 state.f64 max_iter [ivox]\n", argv[0]);
+    const std::string mode = argc == 6 ? argv[5] : "";
+    if (argc != 5 && !(argc == 6 && (mode == "ivox" || mode == "ingest" || mode == "ingest_host"))) {
+        std::fprintf(stderr, "usage: %s map.f32 scan.f32 state.f64 max_iter [ivox|ingest|ingest_host]\n", argv[0]);
         return 2;
     }
+    const bool ingest = mode == "ingest" || mode == "ingest_host";
     const bool ivox = argc == 6;
     const std::vector<char> map = slurp(argv[1]), scan = slurp(argv[2]), st = slurp(argv[3]);
     if (map.empty() || scan.empty() || st.size() != 348 * sizeof(double)) {
@@ -95,6 +194,13 @@ int main(int argc, char** argv) {
         } else {
             lm.build_map(reinterpret_cast<const float*>(map.data()), (int64_t)(map.size() / 12));
         }
+        if (ingest) {
+            lm.set_state(s0);
+            livo_ingest_params& q = lm.ingest_params;
+            q.point_filter_num = 1;
+            run_ingest(lm, reinterpret_cast<const float*>(scan.data()), (int64_t)(scan.size() / 12), mode == "ingest");
+            return 0;
+        }
         lm.set_scan(reinterpret_cast<const float*>(scan.data()), (int64_t)(scan.size() / 12));
         lm.set_state(s0);
         lm.set_state_propagat(s0);
@@ -111,13 +217,7 @@ int main(int argc, char** argv) {
         const livo_iter_stats it = lm.iterate();
         States s1;
         lm.get_state(s1);
-        std::printf("iekf %d %d", it.iterations, it.converged);
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) std::printf(" %.17g", s1.rot_end(i, j));
-        for (int i = 0; i < 3; i++) std::printf(" %.17g", s1.pos_end(i));
-        for (int i = 0; i < 18; i++)
-            for (int j = 0; j < 18; j++) std::printf(" %.17g", s1.cov(i, j));
-        std::printf("\n");
+        print_iekf(it, s1);
         if (ivox) {
             lm.map_incremental(0.5);  // filter_size_map default (laser_mapping.cpp:983)
             std::printf("incr %lld %lld\n", (long long)lm.points_added, (long long)lm.points_no_downsample);

@@ -93,6 +93,7 @@ public:
         check(livo_params_default(&params_), "livo_params_default");
         params_ = p;
         check(livo_imu_params_default(&imu_params), "livo_imu_params_default");
+        check(livo_ingest_params_default(&ingest_params), "livo_ingest_params_default");
     }
     ~LaserMappingGpu() {
         if (ctx_) {
@@ -169,6 +170,54 @@ public:
               "livo_scan_preprocess_imu");
         adopt_scan(id, nd);
     }
+    // livox_pcl_cbk / standard_pcl_cbk (laser_mapping.cpp) with sync_packages' step 1 (:691-708):
+    // p_pre->process(msg, ptr) and the time sort run on the device (ingest_params are Preprocess's
+    // members), the frame stays there as meas.lidar with lidar_scan_index_now = 0, and
+    // lidar_beg_time = the message's stamp, lidar_end_time = lidar_beg_time + points.back().curvature
+    // / 1000 (:707).  `pts` / `data` are the driver's buffers as they are.
+    livo_ingest_info livox_pcl_cbk(const livo_livox_point* pts, int64_t n, double stamp) {
+        livo_ingest_info info{};
+        check(livo_frame_ingest_livox(ctx_, &ingest_params, pts, n, &info), "livo_frame_ingest_livox");
+        frame_pushed(info, stamp);
+        return info;
+    }
+    livo_ingest_info standard_pcl_cbk(const void* data, int64_t n, const livo_cloud_layout& layout, double stamp) {
+        livo_ingest_info info{};
+        check(livo_frame_ingest_cloud(ctx_, &ingest_params, data, n, &layout, &info), "livo_frame_ingest_cloud");
+        frame_pushed(info, stamp);
+        return info;
+    }
+
+    // Process2 on the frame the callback left on the device: UndistortPcl's times (:211, :219-224)
+    // from lidar_beg_time, last_update_time and the frame's end, the forward propagation, and the
+    // slice from lidar_scan_index_now, which never comes to the host.  is_lidar_end: the LiDAR
+    // frame's end (the slice is de-skewed, filtered and becomes the current scan; `down` as
+    // set_scan_raw's); else a camera frame at lidar_beg_time + img_offset_time, whose slice only
+    // moves the cursor (Run() never reads its feats_undistort).  Returns the points taken.
+    int64_t Process2(const livo_imu_sample* imu, int32_t n_imu, bool is_lidar_end, double img_offset_time,
+                     float filter_size_surf, livo_raw_point* down = nullptr, int64_t down_cap = 0) {
+        const double pcl_beg_time = lidar_beg_time > last_update_time ? lidar_beg_time : last_update_time;
+        const double pcl_end_time = is_lidar_end ? lidar_beg_time + frame_end_curvature / double(1000)
+                                                 : lidar_beg_time + img_offset_time;
+        const double pcl_offset_time = is_lidar_end ? (pcl_end_time - lidar_beg_time) * double(1000) : 0.0;
+        livo_imu_job job{};
+        job.imu = imu;
+        job.n_imu = n_imu;
+        job.pcl_beg_time = pcl_beg_time;
+        job.pcl_end_time = pcl_end_time;
+        check(livo_imu_propagate(ctx_, &job, &imu_params, &imu_carry, &state, nullptr, 0, nullptr),
+              "livo_imu_propagate");
+        state_propagat = state;
+        last_update_time = pcl_end_time;  // (:231)
+        int32_t id = -1;
+        int64_t nd = 0, taken = 0;
+        check(livo_frame_take(ctx_, pcl_offset_time, is_lidar_end ? 1 : 0, filter_size_surf,
+                              is_lidar_end ? &id : nullptr, nullptr, down, down_cap, &nd, &taken),
+              "livo_frame_take");
+        if (id >= 0) adopt_scan(id, nd);
+        return taken;
+    }
+
     // p_imu->IMU_init(meas, state, init_iter_num) (IMU_Processing.cpp:147-198) while imu_need_init:
     // returns true once gravity and bias_g are set (imu_need_init_ = false).
     bool IMU_init(const livo_imu_sample* imu, int32_t n_imu) {
@@ -412,8 +461,18 @@ public:
     livo_imu_carry imu_carry{};
     int32_t init_iter_num = 1;
     double mean_gyr[3] = {0.0, 0.0, 0.0};
+    // Preprocess's members (lidar_type, N_SCANS, point_filter_num, blind) and LidarMeasureGroup's
+    // times: the current frame's stamp, its end (sync_packages :707) and last_update_time
+    livo_ingest_params ingest_params{};
+    double lidar_beg_time = 0.0, lidar_end_time = 0.0, last_update_time = 0.0;
+    float frame_end_curvature = 0.f;  // meas.lidar->points.back().curvature (ms)
 
 private:
+    void frame_pushed(const livo_ingest_info& info, double stamp) {
+        frame_end_curvature = info.end_curvature;
+        lidar_beg_time = stamp;
+        lidar_end_time = lidar_beg_time + info.end_curvature / double(1000);
+    }
     void adopt_scan(int32_t id, int64_t N) {
         if (scan_id_ >= 0) {
             if (ivox_) check(livo_scan_inherit_neighbors(ctx_, id, scan_id_), "livo_scan_inherit_neighbors");

@@ -287,6 +287,40 @@ class ImuJob(C.Structure):
 
 
 IMU_INIT_COLLECTING, IMU_INIT_RESET, IMU_INIT_DONE = 0, 1, 2
+LIDAR_AVIA, LIDAR_VELO16, LIDAR_OUST64, LIDAR_XT32 = 1, 2, 3, 4  # LIVO_LIDAR_* (preprocess.h:14)
+
+
+class LivoxPoint(C.Structure):
+    _fields_ = [("offset_time", C.c_uint32), ("x", C.c_float), ("y", C.c_float), ("z", C.c_float),
+                ("reflectivity", C.c_uint8), ("tag", C.c_uint8), ("line", C.c_uint8), ("pad", C.c_uint8)]
+
+
+LIVOX_POINT_DTYPE = np.dtype([("offset_time", np.uint32), ("x", np.float32), ("y", np.float32), ("z", np.float32),
+                              ("reflectivity", np.uint8), ("tag", np.uint8), ("line", np.uint8), ("pad", np.uint8)])
+
+
+class CloudLayout(C.Structure):
+    _fields_ = [("point_step", C.c_int32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("off_z", C.c_int32),
+                ("off_intensity", C.c_int32), ("off_time", C.c_int32)]
+
+
+class IngestParams(C.Structure):
+    _fields_ = [("lidar_type", C.c_int32), ("n_scans", C.c_int32), ("point_filter_num", C.c_int32),
+                ("reserved", C.c_int32), ("blind", C.c_double)]
+
+
+class IngestInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_kept", C.c_int64), ("cursor", C.c_int64), ("n_rejected", C.c_int64),
+                ("n_decimated", C.c_int64), ("end_curvature", C.c_float)]
+
+
+def ingest_params(**kw) -> IngestParams:
+    """livo_ingest_params_default (AVIA, 16, 2, 0.01) with the given members replaced."""
+    p = IngestParams()
+    _check("livo_ingest_params_default", load().livo_ingest_params_default(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
 _IMU_PARAM_FIELDS = ("cov_acc", "cov_gyr", "cov_bias_gyr", "cov_bias_acc", "mean_acc")
 
 
@@ -425,6 +459,14 @@ SIGNATURES = {
                                      C.POINTER(State), _P, C.c_int32, C.POINTER(C.c_int32)]),
     "livo_scan_preprocess_imu": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.POINTER(C.c_int32), _P, _P, C.c_int64,
                                            C.POINTER(C.c_int64)]),
+    "livo_ingest_params_default": (C.c_int, [C.POINTER(IngestParams)]),
+    "livo_frame_ingest_livox": (C.c_int, [_P, C.POINTER(IngestParams), _P, C.c_int64, C.POINTER(IngestInfo)]),
+    "livo_frame_ingest_cloud": (C.c_int, [_P, C.POINTER(IngestParams), _P, C.c_int64, C.POINTER(CloudLayout),
+                                          C.POINTER(IngestInfo)]),
+    "livo_frame_info": (C.c_int, [_P, C.POINTER(IngestInfo)]),
+    "livo_frame_dump": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "livo_frame_take": (C.c_int, [_P, C.c_double, C.c_int, C.c_float, C.POINTER(C.c_int32), _P, _P, C.c_int64,
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -991,6 +1033,60 @@ class Context:
             self.h, _ptr(raw), n, leaf_size, C.byref(sid), _ptr(und), _ptr(down), n, C.byref(nd)))
         self.scans[sid.value] = int(nd.value)
         return sid.value, und, down[:nd.value].copy()
+
+    def frame_ingest_livox(self, pts: np.ndarray, params: IngestParams | None = None) -> dict:
+        """A livox CustomMsg's points (LIVOX_POINT_DTYPE, or raw bytes of 20 a point) through avia_handler and
+        the time sort on the device (livo_frame_ingest_livox); the frame stays resident.  -> the info dict."""
+        pts = np.ascontiguousarray(pts)
+        n = pts.nbytes // 20
+        info = IngestInfo()
+        _check("livo_frame_ingest_livox", self._L.livo_frame_ingest_livox(
+            self.h, C.byref(params or ingest_params()), _ptr(pts) if n else None, n, C.byref(info)))
+        return _stats_dict(info)
+
+    def frame_ingest_cloud(self, data: np.ndarray, layout: CloudLayout, params: IngestParams) -> dict:
+        """A PointCloud2's data (bytes, point_step a point) through the handler of params.lidar_type
+        (livo_frame_ingest_cloud).  -> the info dict."""
+        data = np.ascontiguousarray(data)
+        n = data.nbytes // layout.point_step
+        info = IngestInfo()
+        _check("livo_frame_ingest_cloud", self._L.livo_frame_ingest_cloud(
+            self.h, C.byref(params), _ptr(data) if n else None, n, C.byref(layout), C.byref(info)))
+        return _stats_dict(info)
+
+    def frame_info(self) -> dict:
+        info = IngestInfo()
+        _check("livo_frame_info", self._L.livo_frame_info(self.h, C.byref(info)))
+        return _stats_dict(info)
+
+    def frame_dump(self) -> np.ndarray:
+        """The resident, time-ordered frame (n_kept, 5: x, y, z, intensity, curvature ms)."""
+        n = C.c_int64()
+        _check("livo_frame_dump", self._L.livo_frame_dump(self.h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 5), np.float32)
+        if n.value:
+            _check("livo_frame_dump", self._L.livo_frame_dump(self.h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def frame_take(self, offset_limit_ms: float, is_lidar_end: bool, leaf_size: float = 0.5, make_scan: bool = True):
+        """UndistortPcl's slice of the resident frame from its cursor, then scan_preprocess_imu's body on it
+        (livo_frame_take).  -> (n_taken, scan id or -1, de-skewed points, downsampled cloud); with
+        make_scan=False (a camera frame) only the cursor moves: (n_taken, None, None, None)."""
+        nt = C.c_int64()
+        if not make_scan:
+            _check("livo_frame_take", self._L.livo_frame_take(self.h, offset_limit_ms, int(is_lidar_end), leaf_size,
+                                                              None, None, None, 0, None, C.byref(nt)))
+            return nt.value, None, None, None
+        cap = max(self.frame_info()["n_kept"], 1)
+        und = np.zeros((cap, 5), np.float32)
+        down = np.zeros((cap, 5), np.float32)
+        nd, sid = C.c_int64(), C.c_int32()
+        _check("livo_frame_take", self._L.livo_frame_take(self.h, offset_limit_ms, int(is_lidar_end), leaf_size,
+                                                          C.byref(sid), _ptr(und), _ptr(down), cap, C.byref(nd),
+                                                          C.byref(nt)))
+        if sid.value >= 0:
+            self.scans[sid.value] = int(nd.value)
+        return nt.value, sid.value, und[:nt.value].copy(), down[:nd.value].copy()
 
     # ------------------------------------------------------------ VIO ----
     def vio_update(self, frame: dict, state: dict, prior: dict | None = None, max_iter: int = 4,

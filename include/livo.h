@@ -61,6 +61,7 @@ extern "C" {
 /* 9: the resident visual map (livo_vmap_*) and livo_vio_match added (nothing else changed).
  *    livo_cloud_publish, livo_cloud_info_get and the two LIVO_CLOUD_* ids added the same way.
  *    livo_imu_* (params, init, propagate, propagate_batch) and livo_scan_preprocess_imu too.
+ *    livo_ingest_params_default, livo_frame_ingest_livox / _cloud, livo_frame_info / _dump / _take too.
  * 8: livo_vio_select added (nothing else changed).
  * 7: livo_cloud_colorize added (nothing else changed).
  * 5: livo_ivox_info grew add_passes (round 4).
@@ -948,6 +949,86 @@ int livo_imu_propagate(livo_ctx* ctx, const livo_imu_job* job, const livo_imu_pa
  * where they lie on the device.  LIVO_E_INVALID if no table is resident. */
 int livo_scan_preprocess_imu(livo_ctx* ctx, const livo_raw_point* raw, int64_t n, float leaf_size, int32_t* scan_id,
                              livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down);
+
+/* ------------------------------------------------------------------------
+ * Sensor handlers: the driver's message to the time-ordered frame on the device.
+ *   Preprocess::process, feature_enabled == false     src/preprocess.cpp:82-116
+ *     avia_handler :315-349, oust64_handler :424-453, velodyne_handler with point
+ *     times :578-637, xt32_handler :650-680
+ *   sort(meas.lidar->points, time_list)                src/laser_mapping.cpp:705
+ *   UndistortPcl's slice from lidar_scan_index_now     src/IMU_Processing.cpp:217-235
+ * Not built: feature extraction (give_feature), extract_normal (#define NORMAL) and the
+ * Velodyne branch that derives point times from yaw (given_offset_time == false).
+ * ------------------------------------------------------------------------ */
+typedef struct livo_livox_point {      /* livox_ros_driver::CustomPoint as it lies in memory, 20 B */
+    uint32_t offset_time;               /* ns from the message's timebase */
+    float x, y, z;
+    uint8_t reflectivity, tag, line, pad;
+} livo_livox_point;
+
+typedef struct livo_cloud_layout {     /* sensor_msgs::PointCloud2: point_step and the byte offsets its `fields` give */
+    int32_t point_step, off_x, off_y, off_z, off_intensity, off_time;
+} livo_cloud_layout;                   /* x, y, z, intensity: float32.  time: uint32 ns (OUST64 `t`),
+                                          float32 s (VELO16 `time`), float64 s (XT32 `timestamp`) */
+
+enum { LIVO_LIDAR_AVIA = 1, LIVO_LIDAR_VELO16 = 2, LIVO_LIDAR_OUST64 = 3, LIVO_LIDAR_XT32 = 4 };  /* preprocess.h:14 */
+
+typedef struct livo_ingest_params {    /* Preprocess members, laser_mapping.cpp:989-993 */
+    int32_t lidar_type;                /* LIVO_LIDAR_* */
+    int32_t n_scans, point_filter_num, reserved;
+    double  blind;
+} livo_ingest_params;
+
+typedef struct livo_ingest_info {
+    int64_t n_in, n_kept, cursor;      /* cursor = lidar_scan_index_now */
+    int64_t n_rejected, n_decimated;   /* failed the handler's predicate (AVIA: point 0 too, which its loop never
+                                          visits) / passed it but not the 1-in-point_filter_num */
+    float   end_curvature;             /* points.back().curvature after the sort (ms); 0 when n_kept == 0 */
+} livo_ingest_info;
+
+/* AVIA, 16, 2, 0.01: the nh.param defaults. */
+int livo_ingest_params_default(livo_ingest_params* p);
+/* The message's n points are uploaded as they are, in one copy (page-locked memory, livo_host_register,
+ * is read by the copy engine directly; the buffer is free again on return), the handler of
+ * p->lidar_type and the time sort run on the device, and the result, 5 floats a point, stays in the
+ * context as the current frame (meas.lidar) with cursor = 0, replacing the previous one.  The handlers
+ * are the reference's as written: AVIA never emits point 0, compares x*x + y*y with `blind`
+ * unsquared and counts its 1-in-point_filter_num over the survivors; OUST64 keeps r^2 == blind^2 and
+ * VELO16 drops it; XT32 compares r^2 with `blind` unsquared.  The sort is stable on the float's
+ * order-preserving 32-bit key: ties keep message order (one of the outcomes std::sort may produce),
+ * -0.0 lies before +0.0, NaNs with the sign bit set lie first and the others last (the reference's
+ * order of NaN times is undefined, and livo_frame_take's count assumes there are none).
+ * livo_frame_ingest_livox takes LIVO_LIDAR_AVIA only, livo_frame_ingest_cloud the other three, with
+ * every offset of `layout` (all five are checked, each field whole inside point_step <= 240).
+ * LIVO_E_INVALID: a NULL argument, point_filter_num < 1, n_scans < 0, n < 0, a lidar_type that is
+ * unknown or does not match the call, a layout that does not fit, and a VELO16 message with n > 0
+ * whose last point has time <= 0: the reference then derives the times from yaw, ring by ring
+ * (given_offset_time == false), which is not built here.  LIVO_E_RANGE: n > 2^31 - 1 - 256.
+ * LIVO_E_HIP: no device.  LIVO_E_BUSY while a batch is in flight.  info may be NULL. */
+int livo_frame_ingest_livox(livo_ctx* ctx, const livo_ingest_params* p, const livo_livox_point* pts, int64_t n,
+                            livo_ingest_info* info);
+int livo_frame_ingest_cloud(livo_ctx* ctx, const livo_ingest_params* p, const void* data, int64_t n,
+                            const livo_cloud_layout* layout, livo_ingest_info* info);
+/* The current frame's counts and cursor; LIVO_E_INVALID before any ingest. */
+int livo_frame_info(livo_ctx* ctx, livo_ingest_info* info);
+/* The resident, sorted frame (= meas.lidar): *n = its points; out == NULL queries, else cap >= *n
+ * (LIVO_E_RANGE otherwise).  LIVO_E_INVALID before any ingest. */
+int livo_frame_dump(livo_ctx* ctx, livo_raw_point* out, int64_t cap, int64_t* n);
+/* UndistortPcl's slice and livo_scan_preprocess_imu's body: starting at the cursor, the points with
+ * (double)curvature <= offset_limit_ms are taken (*n_taken; the cursor advances by it, and returns
+ * to 0 afterwards with is_lidar_end), de-skewed where they lie against the table and end pose of the
+ * last livo_imu_propagate, filtered at leaf_size and made a resident scan (*scan_id; undistorted,
+ * down, down_cap, n_down as livo_scan_preprocess_imu's).  The caller computes the limit as the
+ * reference does: (pcl_end_time - lidar_beg_time) * 1000.0 on a LiDAR frame, with pcl_end_time =
+ * lidar_beg_time + end_curvature / 1000.0, and 0.0 on a camera frame (:219-224).  scan_id == NULL
+ * moves the cursor only (a camera frame, whose feats_undistort Run() never reads).  *n_taken == 0
+ * makes no scan: *scan_id = -1, and the frame of livo_frame_to_world(-1) is empty.  Otherwise
+ * livo_frame_to_world(-1) and livo_cloud_publish(-1) see the taken range.  LIVO_E_INVALID: ctx or
+ * n_taken NULL, a non-finite leaf_size, no ingest yet, a scan_id before any livo_imu_propagate.
+ * LIVO_E_BUSY while a batch is in flight.  A refused or failed take leaves the cursor where it was. */
+int livo_frame_take(livo_ctx* ctx, double offset_limit_ms, int is_lidar_end, float leaf_size, int32_t* scan_id,
+                    livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down,
+                    int64_t* n_taken);
 
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
