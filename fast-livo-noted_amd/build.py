@@ -31,6 +31,7 @@ SOURCES = [
     ("ivox_kernels.hip", True),
     ("frontend_kernels.hip", True),
     ("imu_kernels.hip", True),
+    ("lio_kernels.hip", True),
     ("ingest_kernels.hip", True),
     ("vio_kernels.hip", True),
     ("rgb_kernels.hip", True),

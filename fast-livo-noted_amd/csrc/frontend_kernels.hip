@@ -50,6 +50,8 @@ __global__ void k_fe_segment(const float* __restrict__ raw, int64_t n, const dou
 }
 
 // P_compensate = extR_Ri * (R_i * (R_LI * P_i + t_LI) + T_ei) - exrR_extT (IMU_Processing.cpp:356-370)
+// kDev (livo_lio_frame): the frame-end pose is read from F.end_dev.
+template <bool kDev>
 __device__ void fe_compensate(float* p, const double* __restrict__ head, const FrontParams& F) {
     const double dt = (double)p[4] / double(1000) - head[0];
     double Re[9], Ri[9];
@@ -60,10 +62,32 @@ __device__ void fe_compensate(float* p, const double* __restrict__ head, const F
 #pragma unroll
         for (int j = 0; j < 3; j++)
             Ri[i * 3 + j] = (Rh[i * 3 + 0] * Re[0 * 3 + j] + Rh[i * 3 + 1] * Re[1 * 3 + j]) + Rh[i * 3 + 2] * Re[2 * 3 + j];
+    // the frame-end pose: the host's extR_Ri / pos_end, or (livo_lio_frame) the same expressions
+    // over the propagated state where k_imu_propagate left it
+    double eR[9], pe[3];
+    if (kDev) {
+        const double* rot_end = F.end_dev;
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                double acc = F.R_LI[0 * 3 + i] * rot_end[j * 3 + 0];
+#pragma unroll
+                for (int l = 1; l < 3; l++) acc = acc + F.R_LI[l * 3 + i] * rot_end[j * 3 + l];
+                eR[i * 3 + j] = acc;
+            }
+#pragma unroll
+        for (int k = 0; k < 3; k++) pe[k] = F.end_dev[9 + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; k++) eR[k] = F.extR_Ri[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) pe[k] = F.pos_end[k];
+    }
     double T[3];
 #pragma unroll
     for (int k = 0; k < 3; k++)
-        T[k] = ((head[10 + k] + head[7 + k] * dt) + ((0.5 * head[1 + k]) * dt) * dt) - F.pos_end[k];
+        T[k] = ((head[10 + k] + head[7 + k] * dt) + ((0.5 * head[1 + k]) * dt) * dt) - pe[k];
     const double Pi[3] = {(double)p[0], (double)p[1], (double)p[2]};
     double a[3], b[3], c[3];
     m3v(F.R_LI, Pi, a);
@@ -72,7 +96,7 @@ __device__ void fe_compensate(float* p, const double* __restrict__ head, const F
     m3v(Ri, a, b);
 #pragma unroll
     for (int k = 0; k < 3; k++) b[k] = b[k] + T[k];
-    m3v(F.extR_Ri, b, c);
+    m3v(eR, b, c);
     p[0] = (float)(c[0] - F.exrR_extT[0]);
     p[1] = (float)(c[1] - F.exrR_extT[1]);
     p[2] = (float)(c[2] - F.exrR_extT[2]);
@@ -80,6 +104,7 @@ __device__ void fe_compensate(float* p, const double* __restrict__ head, const F
 
 // seg_rev holds the prefix minimum of the reversed segments: point i's
 // segment is seg_rev[n-1-i] (-1: untouched).
+template <bool kDev>
 __global__ void k_fe_undistort(FrontParams F) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= F.n) return;
@@ -91,9 +116,9 @@ __global__ void k_fe_undistort(FrontParams F) {
     if (i == 0) {
         // the walk's inner loop breaks at begin() without stepping, so every
         // earlier segment moves the first point again
-        for (int hh = h; hh >= 0; hh--) fe_compensate(p, F.poses + (int64_t)hh * kPoseD, F);
+        for (int hh = h; hh >= 0; hh--) fe_compensate<kDev>(p, F.poses + (int64_t)hh * kPoseD, F);
     } else {
-        fe_compensate(p, F.poses + (int64_t)h * kPoseD, F);
+        fe_compensate<kDev>(p, F.poses + (int64_t)h * kPoseD, F);
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) F.raw[5 * i + k] = p[k];
@@ -355,13 +380,16 @@ __global__ void k_to_world(CloudSrc S, WorldParams W, float* __restrict__ out5) 
 // Grid-stride over the stored order, kPublishBlocks blocks at most: block_minmax's six atomics
 // per block stay few.  minmax == nullptr (no pg_down): the rows only.
 constexpr int kPublishBlocks = 256;
-__global__ __launch_bounds__(256) void k_cloud_publish(CloudSrc S, WorldParams W, float* __restrict__ out5,
-                                                       unsigned* minmax) {
+// kDev (livo_lio_frame): rot / pos from the device state at `pose` (rot[9], pos[3]), the same expressions.
+template <bool kDev>
+__global__ __launch_bounds__(256) void k_cloud_publish(CloudSrc S, WorldParams W, const double* __restrict__ pose,
+                                                       float* __restrict__ out5, unsigned* minmax) {
     unsigned mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < S.n; k += (int64_t)gridDim.x * blockDim.x) {
         const float* p = S.src + S.stride * k;
         float w[3];
-        world_point(W.rot, W.pos, W.R_LI, W.t_LI, p[0], p[1], p[2], w[0], w[1], w[2]);
+        if (kDev) world_point(pose, pose + 9, W.R_LI, W.t_LI, p[0], p[1], p[2], w[0], w[1], w[2]);
+        else world_point(W.rot, W.pos, W.R_LI, W.t_LI, p[0], p[1], p[2], w[0], w[1], w[2]);
         const float intensity = S.stride >= 5 ? p[3] : 0.0f;
         const int64_t o = S.perm ? (int64_t)S.perm[k] : k;
         float* q = out5 + 5 * o;
@@ -414,7 +442,10 @@ static inline dim3 fe_blocks(int64_t n) { return dim3((unsigned)((n + 255) / 256
 int launch_fe_segment(const FrontParams& F, void* stream) {
     FE_LAUNCH(k_fe_segment, F.n, F.raw, F.n, F.poses, F.np, F.seg);
 }
-int launch_fe_undistort(const FrontParams& F, void* stream) { FE_LAUNCH(k_fe_undistort, F.n, F); }
+int launch_fe_undistort(const FrontParams& F, void* stream) {
+    if (F.end_dev) FE_LAUNCH(k_fe_undistort<true>, F.n, F);
+    FE_LAUNCH(k_fe_undistort<false>, F.n, F);
+}
 int launch_fe_minmax(const float* pts, int64_t n, int stride, unsigned* minmax, void* stream) {
     if (n <= 0) return LIVO_OK;
     const unsigned blocks = (unsigned)std::min<int64_t>(kMinmaxBlocks, (n + 255) / 256);
@@ -492,11 +523,17 @@ int launch_fe_gather_seg(const float* pts, const FeSegs& S, int n_scans, int64_t
 int launch_to_world(const CloudSrc& S, const WorldParams& W, float* out5, void* stream) {
     FE_LAUNCH(k_to_world, S.n, S, W, out5);
 }
-int launch_cloud_publish(const CloudSrc& S, const WorldParams& W, float* out5, unsigned* minmax, void* stream) {
+int launch_cloud_publish(const CloudSrc& S, const WorldParams& W, float* out5, unsigned* minmax, void* stream,
+                         const double* dev_pose) {
     if (S.n <= 0) return LIVO_OK;
     if (S.world) return LIVO_E_INVALID;  // (the rows of a world cloud are launch_to_world's copy)
     const unsigned blocks = (unsigned)std::min<int64_t>(kPublishBlocks, (S.n + 255) / 256);
-    hipLaunchKernelGGL(k_cloud_publish, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, W, out5, minmax);
+    if (dev_pose)
+        hipLaunchKernelGGL(k_cloud_publish<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, W, dev_pose, out5,
+                           minmax);
+    else
+        hipLaunchKernelGGL(k_cloud_publish<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, W, dev_pose, out5,
+                           minmax);
     return hipGetLastError() == hipSuccess ? LIVO_OK : LIVO_E_HIP;
 }
 int launch_ori_flags(const uint8_t* sel, const int32_t* perm, int64_t n, uint32_t* flags, void* stream) {

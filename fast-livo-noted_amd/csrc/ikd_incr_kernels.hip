@@ -146,7 +146,9 @@ __global__ void k_add_prep(DynAddParams P) {
         if (P.wpts) {  // map_incremental: the stored point g is caller point perm[g], to the world frame
             const float4 b = reinterpret_cast<const float4*>(P.wpts)[g];
             float wx, wy, wz;
-            world_point(P.wrot, P.wpos, P.R_LI, P.t_LI, b.x, b.y, b.z, wx, wy, wz);
+            // (two calls, no pointer select: the arguments stay in the kernel-argument segment)
+            if (P.wdev) world_point(P.wdev, P.wdev + 9, P.R_LI, P.t_LI, b.x, b.y, b.z, wx, wy, wz);
+            else world_point(P.wrot, P.wpos, P.R_LI, P.t_LI, b.x, b.y, b.z, wx, wy, wz);
             i = P.wperm[g];
             p = make_float4(wx, wy, wz, 0.f);
             reinterpret_cast<float4*>(const_cast<float*>(P.W))[i] = p;

@@ -1122,7 +1122,8 @@ __global__ void k_map_incr(MapIncrParams P) {
     if (j >= P.n) return;
     const float4 b = reinterpret_cast<const float4*>(P.pts)[j];
     float pw[3];
-    world_point(P.slot->state.rot, P.slot->state.pos, P.R_LI, P.t_LI, b.x, b.y, b.z, pw[0], pw[1], pw[2]);
+    const double* pose = P.pose ? P.pose : P.slot->state.rot;  // (rot[9], pos[3]: contiguous in livo_state)
+    world_point(pose, pose + 9, P.R_LI, P.t_LI, b.x, b.y, b.z, pw[0], pw[1], pw[2]);
     float4 nb[kNN];
     int cnt, rflag;
     rec_load(P.nn + j, reinterpret_cast<const float4*>(P.keypts), nb, cnt, rflag);

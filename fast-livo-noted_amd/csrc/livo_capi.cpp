@@ -280,6 +280,9 @@ struct BatchPlan {
     bool iv = false;     // iVox search (its own overflow replay lists)
     bool lazy = false;   // fused: searches after the first skip unread records (KnnParams::rec_lazy)
     int prof = 0;       // profiling level of this batch (0: no event is recorded)
+    // livo_lio_frame: the one scan's state lies on the device; its slot is staged there
+    // (k_lio_stage_slot) instead of init_slot + the upload
+    const livo_state* dev_state = nullptr;
     Staging* stage = nullptr;
     size_t stride = 0;   // bytes from one slot to the next
     int ngroups = 0;
@@ -1806,7 +1809,8 @@ static int dyn_rebuild_merge(livo_ctx* c) {
 struct DynWorldIn {
     const float* pts;
     const int32_t* perm;
-    const livo_state* state;
+    const livo_state* state;      // host, or
+    const livo_state* dev_state;  // ... non-null: on the device (livo_lio_frame)
 };
 static int dyn_add(livo_ctx* c, int64_t n, float ds, bool downsample, livo_map_add_stats* out,
                    const DynWorldIn* world = nullptr) {
@@ -1879,8 +1883,14 @@ static int dyn_add(livo_ctx* c, int64_t n, float ds, bool downsample, livo_map_a
             P.dirty = d.dirty; P.dirty_cap = kDynDirtyCap; P.ctr = d.ctr;
             if (world) {
                 P.wpts = world->pts; P.wperm = world->perm;
-                std::memcpy(P.wrot, world->state->rot, sizeof(P.wrot));
-                std::memcpy(P.wpos, world->state->pos, sizeof(P.wpos));
+                static_assert(offsetof(livo_state, rot) == 0 && offsetof(livo_state, pos) == 9 * sizeof(double),
+                              "rot[9], pos[3] lead the state");
+                if (world->dev_state) {
+                    P.wdev = reinterpret_cast<const double*>(world->dev_state);
+                } else {
+                    std::memcpy(P.wrot, world->state->rot, sizeof(P.wrot));
+                    std::memcpy(P.wpos, world->state->pos, sizeof(P.wpos));
+                }
                 std::memcpy(P.R_LI, c->params.R_LI, sizeof(P.R_LI));
                 std::memcpy(P.t_LI, c->params.t_LI, sizeof(P.t_LI));
             }
@@ -1981,8 +1991,8 @@ static int dyn_add(livo_ctx* c, int64_t n, float ds, bool downsample, livo_map_a
 // map_incremental with USE_ikdtree (laser_mapping.cpp:343-345, 383-384): every
 // point to the world frame at the state, then Add_Points(feats_down_world, true)
 // with downsample_size = filter_size_map_min (set_downsample_param, :138).
-static int map_incremental_ikd(livo_ctx* c, int32_t id, const livo_state* state, double fs, uint8_t* cat,
-                               int64_t counts[2]) {
+static int map_incremental_ikd(livo_ctx* c, int32_t id, const livo_state* state, const livo_state* dev_state, double fs,
+                               uint8_t* cat, int64_t counts[2]) {
     if (!c->has_map) return LIVO_E_NOMAP;
     ScanBuf* s = get_scan(c, id);
     if (!s) return LIVO_E_NOSCAN;
@@ -1994,7 +2004,7 @@ static int map_incremental_ikd(livo_ctx* c, int32_t id, const livo_state* state,
     if (!rc) rc = dyn_add_scratch(c, std::max<int64_t>(N, 1));
     if (rc) return rc;
     // (feats_down_world: k_add_prep takes the points to the world frame, the state in its arguments)
-    const DynWorldIn world{s->pts, s->d_perm, state};
+    const DynWorldIn world{s->pts, s->d_perm, state, dev_state};
     livo_map_add_stats st{};
     rc = dyn_add(c, N, (float)fs, true, &st, &world);
     if (rc) return rc;
@@ -3439,6 +3449,8 @@ static void batch_fill(livo_ctx* c, const BatchPlan& P, const int32_t* ids, cons
     for (int32_t b = 0; b < P.n; b++) {
         if (P.model == kModelIkfom) {
             init_slot_ik(hslot(P, b), ik_states[b], max_iter);
+        } else if (P.dev_state) {
+            std::memset(&hslot(P, b), 0, kSlotLmBytes);  // (the device writes its slot; this copy is the read-back's)
         } else {
             init_slot(hslot(P, b), states[b], priors ? priors[b] : states[b], max_iter, kSlotLmBytes);
         }
@@ -3478,7 +3490,10 @@ static int stage_group(livo_ctx* c, int L, const BatchPlan& P, int gi, const int
     } else if (P.kcopy) {
         RC_TRY(launch_copy_ranges(P.stage->h_dev, P.stage->d, s0, sb, j0, jb, st));
     } else {
-        HIP_TRY(hipMemcpyAsync(P.stage->d + s0, P.stage->h + s0, sb, hipMemcpyHostToDevice, st));
+        if (P.dev_state)
+            RC_TRY(launch_lio_stage_slot(P.dev_state, dslot(P, G.first), c->params.max_iterations, st));
+        else
+            HIP_TRY(hipMemcpyAsync(P.stage->d + s0, P.stage->h + s0, sb, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(P.stage->d + j0, P.stage->h + j0, jb, hipMemcpyHostToDevice, st));
     }
     if (!P.fused) HIP_TRY(hipMemsetAsync(lane_rcount(c, L) + gi, 0, sizeof(unsigned), st));
@@ -3618,9 +3633,12 @@ static void batch_records_invalid(livo_ctx* c, int32_t n, const int32_t* ids) {
         if (ScanBuf* s = get_scan_q(c, ids[b])) s->searched = s->nn_lazy = false;
 }
 
+// dev_state (livo_lio_frame; one scan, synchronous, LaserMapping): the scan's state and prior on the device.
 static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int model, const livo_state* states,
-                         const livo_state* priors, const livo_ikfom_state* ik_states, bool sync) {
-    if (!c || n < 0 || (n > 0 && (!ids || (model == kModelIkfom ? !ik_states : !states)))) return LIVO_E_INVALID;
+                         const livo_state* priors, const livo_ikfom_state* ik_states, bool sync,
+                         const livo_state* dev_state = nullptr) {
+    if (!c || n < 0 || (n > 0 && (!ids || (model == kModelIkfom ? !ik_states : !states && !dev_state)))) return LIVO_E_INVALID;
+    if (dev_state && (n != 1 || !sync || model != kModelLaserMapping)) return LIVO_E_INVALID;
     BatchLane& B = c->lane[L];
     if (B.busy) return LIVO_E_BUSY;
     B.n = 0;
@@ -3630,6 +3648,7 @@ static int batch_enqueue(livo_ctx* c, int L, int32_t n, const int32_t* ids, int 
     RC_TRY(lane_streams(c, L));
     RC_TRY(B.stage[model].ensure(stage_bytes(model, n)));
     const int64_t total_n = batch_plan(c, L, n, ids, model, sync);
+    B.plan.dev_state = dev_state;
     const BatchPlan& P = B.plan;
     batch_fill(c, P, ids, states, priors, ik_states);
     RC_TRY(ensure_replay(c, total_n));
@@ -3786,9 +3805,9 @@ static void lane_abort(BatchLane& B) {
 
 static int batch_update(livo_ctx* c, int32_t n, const int32_t* ids, int model, livo_state* states,
                         const livo_state* priors, livo_iter_stats* stats, livo_ikfom_state* ik_states,
-                        livo_ikfom_stats* ik_stats) {
+                        livo_ikfom_stats* ik_stats, const livo_state* dev_state = nullptr) {
     if (c && any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
-    const int rc = batch_enqueue(c, 0, n, ids, model, states, priors, ik_states, true);
+    const int rc = batch_enqueue(c, 0, n, ids, model, states, priors, ik_states, true, dev_state);
     if (rc) {
         if (c) lane_abort(c->lane[0]);
         return rc;
@@ -4044,11 +4063,12 @@ int livo_ivox_dump(livo_ctx* c, float* xyz, int32_t* ids, int32_t* keys, int64_t
     return k == v.npts ? LIVO_OK : LIVO_E_HIP;
 }
 
-int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, double fs, int ekf_inited, uint8_t* cat,
-                         int64_t counts[2]) {
-    if (!c || !state || !(fs > 0.0)) return LIVO_E_INVALID;
+// state: on the host, or dev_state: on the device (livo_lio_frame: the loop's slot or the propagated state).
+static int map_incremental(livo_ctx* c, int32_t id, const livo_state* state, const livo_state* dev_state, double fs,
+                           int ekf_inited, uint8_t* cat, int64_t counts[2]) {
+    if (!c || (!state && !dev_state) || !(fs > 0.0)) return LIVO_E_INVALID;
     if (any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
-    if (c->backend != LIVO_BACKEND_IVOX) return map_incremental_ikd(c, id, state, fs, cat, counts);
+    if (c->backend != LIVO_BACKEND_IVOX) return map_incremental_ikd(c, id, state, dev_state, fs, cat, counts);
     if (!c->iv.ready) return LIVO_E_NOMAP;
     ScanBuf* s = get_scan(c, id);
     if (!s) return LIVO_E_NOSCAN;
@@ -4065,8 +4085,10 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
     const MapIncr W = map_incr_layout(cv, (size_t)N);
     rc = ensure_nn_coords(c, s, c->stream);  // (first: rebuilding skipped records takes the staging slot)
     if (rc) return rc;
-    init_slot(c->h_slots[0], *state, *state, c->params.max_iterations);
-    HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
+    if (!dev_state) {
+        init_slot(c->h_slots[0], *state, *state, c->params.max_iterations);
+        HIP_TRY(hipMemcpyAsync(c->d_slots, c->h_slots, sizeof(IekfSlot), hipMemcpyHostToDevice, c->stream));
+    }
     HIP_TRY(hipMemsetAsync(W.flags, 0, (size_t)N * 8, c->stream));
     MapIncrParams mp{};
     mp.pts = s->pts;
@@ -4074,6 +4096,7 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
     mp.keypts = c->gpts;
     mp.perm = s->d_perm;
     mp.slot = c->d_slots;
+    mp.pose = reinterpret_cast<const double*>(dev_state);  // (rot[9], pos[3] lead the state)
     std::memcpy(mp.R_LI, c->params.R_LI, sizeof(mp.R_LI));
     std::memcpy(mp.t_LI, c->params.t_LI, sizeof(mp.t_LI));
     mp.ordered = W.ordered;
@@ -4108,6 +4131,12 @@ int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, doubl
         counts[1] = total - n_add;
     }
     return LIVO_OK;
+}
+
+int livo_map_incremental(livo_ctx* c, int32_t id, const livo_state* state, double fs, int ekf_inited, uint8_t* cat,
+                         int64_t counts[2]) {
+    if (!state) return LIVO_E_INVALID;
+    return map_incremental(c, id, state, nullptr, fs, ekf_inited, cat, counts);
 }
 
 int livo_scan_inherit_neighbors(livo_ctx* c, int32_t dst, int32_t src) {
@@ -4207,12 +4236,12 @@ static int voxel_grid(livo_ctx* c, FrontParams& F, const unsigned* mm, float lea
 static int scan_preprocess(livo_ctx* c, const livo_raw_point* raw, bool raw_dev, int64_t n, const livo_imu_pose* poses,
                            const double* dev_poses, bool dev_sorted, int32_t n_poses, const double rot_end[9],
                            const double pos_end[3], float leaf_size, int32_t* scan_id, livo_raw_point* undistorted,
-                           livo_raw_point* down, int64_t down_cap, int64_t* n_down) {
+                           livo_raw_point* down, int64_t down_cap, int64_t* n_down, const livo_state* end_dev = nullptr) {
     if (!c || !scan_id || n < 0 || (n > 0 && !raw) || n_poses < 0 || (n_poses > 0 && !poses && !dev_poses) ||
         !std::isfinite(leaf_size))
         return LIVO_E_INVALID;
     const bool deskew = n_poses >= 2 && n > 0;
-    if (deskew && (!rot_end || !pos_end)) return LIVO_E_INVALID;
+    if (deskew && !end_dev && (!rot_end || !pos_end)) return LIVO_E_INVALID;
     if (dev_poses && !dev_sorted) return LIVO_E_INVALID;
     for (int32_t k = 1; k < n_poses && !dev_poses; k++)
         if (!(poses[k].offset_time >= poses[k - 1].offset_time)) return LIVO_E_INVALID;  // the walk needs sorted segments
@@ -4250,16 +4279,18 @@ static int scan_preprocess(livo_ctx* c, const livo_raw_point* raw, bool raw_dev,
     int rc = LIVO_OK;
     if (deskew) {
         // extR_Ri = R_LI^T rot_end^T, exrR_extT = R_LI^T t_LI (IMU_Processing.cpp:337-338)
+        // (end_dev: the frame-end pose is on the device, fe_compensate forms extR_Ri and pos_end there)
         const double* RL = c->params.R_LI;
+        F.end_dev = reinterpret_cast<const double*>(end_dev);
         for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) {
+            for (int j = 0; j < 3 && !end_dev; j++) {
                 double acc = RL[0 * 3 + i] * rot_end[j * 3 + 0];
                 for (int l = 1; l < 3; l++) acc = acc + RL[l * 3 + i] * rot_end[j * 3 + l];
                 F.extR_Ri[i * 3 + j] = acc;
             }
             F.exrR_extT[i] = (RL[0 * 3 + i] * c->params.t_LI[0] + RL[1 * 3 + i] * c->params.t_LI[1]) +
                              RL[2 * 3 + i] * c->params.t_LI[2];
-            F.pos_end[i] = pos_end[i];
+            if (!end_dev) F.pos_end[i] = pos_end[i];
         }
         static_assert(sizeof(livo_imu_pose) == 22 * sizeof(double), "Pose6D row");
         if (dev_poses)
@@ -4391,7 +4422,7 @@ int livo_imu_init(livo_ctx*, const livo_imu_sample* imu, int32_t n, livo_imu_par
 // resident table (livo_imu_propagate) instead of the staging area.
 static int imu_propagate(livo_ctx* c, int32_t n, const livo_imu_job* jobs, const livo_imu_params* params,
                          livo_imu_carry* carries, livo_state* states, livo_imu_pose* poses, int32_t pose_cap,
-                         int32_t* n_poses, bool table) {
+                         int32_t* n_poses, bool table, const livo_state** dev_state = nullptr) {
     if (!c || n < 0 || (n > 0 && (!jobs || !carries || !states)) || !params || pose_cap < 0)
         return LIVO_E_INVALID;
     int64_t total = 0;
@@ -4482,20 +4513,27 @@ static int imu_propagate(livo_ctx* c, int32_t n, const livo_imu_job* jobs, const
     B.acc_norm = norm3(params->mean_acc);
     HIP_TRY(hipMemcpyAsync(D.buf, D.pin, in_bytes, hipMemcpyHostToDevice, D.st));
     RC_TRY(launch_imu_propagate(B, n, D.st));
-    HIP_TRY(hipMemcpyAsync(D.pin, D.buf, io_bytes, hipMemcpyDeviceToHost, D.st));
+    // dev_state (livo_lio_frame, one job): the propagated state stays on the device, where the later
+    // stages read it; the carry and the row count come back
+    const size_t io_from = dev_state ? (size_t)((char*)B.carries - (char*)D.buf) : 0;
+    HIP_TRY(hipMemcpyAsync((char*)D.pin + io_from, (char*)D.buf + io_from, io_bytes - io_from, hipMemcpyDeviceToHost,
+                           D.st));
     if (poses)
         HIP_TRY(hipMemcpy2DAsync(poses, (size_t)pose_cap * sizeof(livo_imu_pose), d_rows,
                                  (size_t)dev_cap * sizeof(livo_imu_pose), (size_t)dev_cap * sizeof(livo_imu_pose),
                                  (size_t)n, hipMemcpyDeviceToHost, D.st));
     HIP_TRY(stream_wait(D.st));
     for (int32_t j = 0; j < n; j++) {
-        states[j] = h_states[j];
+        if (!dev_state) states[j] = h_states[j];
         carries[j] = h_carries[j];
         if (n_poses) n_poses[j] = h_counts[j];
     }
+    if (dev_state) *dev_state = B.states;
     if (table) {
-        std::memcpy(D.rot_end, states[0].rot, sizeof(D.rot_end));
-        std::memcpy(D.pos_end, states[0].pos, sizeof(D.pos_end));
+        if (!dev_state) {  // (livo_lio_frame sets them from the one state copy at its end)
+            std::memcpy(D.rot_end, states[0].rot, sizeof(D.rot_end));
+            std::memcpy(D.pos_end, states[0].pos, sizeof(D.pos_end));
+        }
         D.sorted = sorted;
         D.rows = h_counts[0];
     }
@@ -4649,9 +4687,10 @@ int livo_frame_dump(livo_ctx* c, livo_raw_point* out, int64_t cap, int64_t* n) {
     return LIVO_OK;
 }
 
-int livo_frame_take(livo_ctx* c, double offset_limit_ms, int is_lidar_end, float leaf_size, int32_t* scan_id,
-                    livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down,
-                    int64_t* n_taken) {
+// end_dev (livo_lio_frame): the frame-end pose of the de-skew on the device instead of c->imu.rot_end / pos_end.
+static int frame_take(livo_ctx* c, double offset_limit_ms, int is_lidar_end, float leaf_size, int32_t* scan_id,
+                      livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down,
+                      int64_t* n_taken, const livo_state* end_dev) {
     if (!c || !n_taken || (scan_id && !std::isfinite(leaf_size))) return LIVO_E_INVALID;
     if (hip_device_count() <= 0) return LIVO_E_HIP;
     if (any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
@@ -4675,12 +4714,19 @@ int livo_frame_take(livo_ctx* c, double offset_limit_ms, int is_lidar_end, float
         } else {
             RC_TRY(scan_preprocess(c, reinterpret_cast<const livo_raw_point*>(D.frame + 5 * from), true, (int64_t)cnt,
                                    nullptr, (const double*)c->imu.table, c->imu.sorted, c->imu.rows, c->imu.rot_end,
-                                   c->imu.pos_end, leaf_size, scan_id, undistorted, down, down_cap, n_down));
+                                   c->imu.pos_end, leaf_size, scan_id, undistorted, down, down_cap, n_down, end_dev));
         }
     }
     D.info.cursor = is_lidar_end ? 0 : from + (int64_t)cnt;  // (:229, :232-235)
     *n_taken = (int64_t)cnt;
     return LIVO_OK;
+}
+
+int livo_frame_take(livo_ctx* c, double offset_limit_ms, int is_lidar_end, float leaf_size, int32_t* scan_id,
+                    livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down,
+                    int64_t* n_taken) {
+    return frame_take(c, offset_limit_ms, is_lidar_end, leaf_size, scan_id, undistorted, down, down_cap, n_down, n_taken,
+                      nullptr);
 }
 
 int livo_vio_params_default(livo_vio_params* p) {
@@ -4986,9 +5032,10 @@ static void cloud_info(const WorldCloud& w, livo_cloud_info* out) {
 
 // *pcl_wait_pub = *laserCloudWorld at the end of a LiDAR frame (laser_mapping.cpp:258-268) and the
 // pg_down every detect until the next one filters out of it (lidar_selection.cpp:341-344).
-int livo_cloud_publish(livo_ctx* c, int32_t src_scan_id, const livo_state* lio_state, float match_leaf,
-                       livo_cloud_info* info) {
-    if (!c || !lio_state || !std::isfinite(match_leaf) || is_cloud_id(src_scan_id)) return LIVO_E_INVALID;
+// lio_state: on the host, or dev_state: on the device (livo_lio_frame).
+static int cloud_publish(livo_ctx* c, int32_t src_scan_id, const livo_state* lio_state, const livo_state* dev_state,
+                         float match_leaf, livo_cloud_info* info) {
+    if (!c || (!lio_state && !dev_state) || !std::isfinite(match_leaf) || is_cloud_id(src_scan_id)) return LIVO_E_INVALID;
     CloudSrc S;
     RC_TRY(frame_cloud(c, src_scan_id, &S));
     const int64_t n = S.n;
@@ -5029,7 +5076,11 @@ int livo_cloud_publish(livo_ctx* c, int32_t src_scan_id, const livo_state* lio_s
     w.n = w.n_down = -1;
     w.filtered = false;
     if (mm) RC_TRY(minmax_init(c, mm));
-    RC_TRY(launch_cloud_publish(S, world_params(c, *lio_state), d_world, mm, c->stream));
+    {
+        static const livo_state none{};  // (rot / pos unread with dev_state)
+        RC_TRY(launch_cloud_publish(S, world_params(c, dev_state ? none : *lio_state), d_world, mm, c->stream,
+                                    reinterpret_cast<const double*>(dev_state)));
+    }
     int64_t n_down = build_down ? n : -1;
     const float* down = build_down ? d_world : nullptr;
     if (mm) {
@@ -5051,6 +5102,12 @@ int livo_cloud_publish(livo_ctx* c, int32_t src_scan_id, const livo_state* lio_s
     w.n_down = n_down;
     if (info) cloud_info(w, info);
     return LIVO_OK;
+}
+
+int livo_cloud_publish(livo_ctx* c, int32_t src_scan_id, const livo_state* lio_state, float match_leaf,
+                       livo_cloud_info* info) {
+    if (!lio_state) return LIVO_E_INVALID;
+    return cloud_publish(c, src_scan_id, lio_state, nullptr, match_leaf, info);
 }
 
 int livo_cloud_info_get(livo_ctx* c, livo_cloud_info* out) {
@@ -5865,6 +5922,104 @@ int livo_vmap_release_frames(livo_ctx* c, int32_t* released, int64_t cap, int64_
     }
     std::sort(m.free_slots.begin(), m.free_slots.end(), std::greater<int32_t>());
     return LIVO_OK;
+}
+
+// ---- One LiDAR frame in one call (laser_mapping.cpp:37-284, the LIO half of Run()) ----
+// The stages are the entry points' own internals with the state on the device: dst is the propagated
+// state where k_imu_propagate left it (the IMU staging), then the loop's slot.  Host syncs that remain:
+// the propagation's (carry, row count), the take count, the VoxelGrid bounds and voxel count (twice:
+// downSizeFilterSurf, pg_down), the scan build, the loop's end (its slot comes back: the one copy of
+// the state), map_incremental's counts, the publish.
+int livo_lio_frame(livo_ctx* c, const livo_imu_job* job, const livo_imu_params* imu, livo_imu_carry* carry,
+                   double offset_limit_ms, const livo_lio_params* p, livo_state* state, livo_state* state_propagat,
+                   livo_lio_stats* stats) {
+    if (!c || !job || !imu || !carry || !p || !state || !state_propagat) return LIVO_E_INVALID;
+    if (job->n_imu < 0 || (job->n_imu > 0 && !job->imu)) return LIVO_E_INVALID;
+    if (!std::isfinite(p->filter_size_surf) || !std::isfinite(p->match_leaf) || !(p->filter_size_map_min > 0.0))
+        return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (any_inflight(c)) return LIVO_E_BUSY;  // submitted batches are collected first
+    if (!c->ing.have) return LIVO_E_INVALID;
+    const bool ivox = c->backend == LIVO_BACKEND_IVOX;
+    if (ivox ? !c->iv.ready : (!p->first_scan && !c->has_map)) return LIVO_E_NOMAP;
+    if (p->prev_scan_id >= 0 && !get_scan_q(c, p->prev_scan_id)) return LIVO_E_NOSCAN;
+    livo_lio_stats S;
+    std::memset(&S, 0, sizeof(S));
+    S.stage = LIVO_LIO_EMPTY;
+    S.scan_id = -1;
+    // 1. the forward propagation; the state stays in the IMU staging
+    const livo_state* dst = nullptr;
+    RC_TRY(imu_propagate(c, 1, job, imu, carry, state, nullptr, 0, nullptr, true, &dst));
+    // The one copy of a frame that runs no loop: the propagated state, for both outputs.
+    auto finish = [&](int rc) -> int {
+        if (rc) {
+            c->imu.rows = 0;  // (the table's end pose never reached the host: no table)
+            return rc;
+        }
+        std::memcpy(c->imu.rot_end, state_propagat->rot, sizeof(c->imu.rot_end));
+        std::memcpy(c->imu.pos_end, state_propagat->pos, sizeof(c->imu.pos_end));
+        if (stats) *stats = S;
+        return LIVO_OK;
+    };
+    auto fetch_propagated = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(state, dst, sizeof(livo_state), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(stream_wait(c->stream));
+        *state_propagat = *state;
+        return LIVO_OK;
+    };
+    // 2. the slice, the de-skew against the device's end pose, downSizeFilterSurf
+    std::vector<livo_raw_point> down;
+    int32_t id = -1;
+    {
+        const int64_t left = c->ing.info.n_kept - c->ing.info.cursor;
+        if (p->first_scan) down.resize((size_t)std::max<int64_t>(left, 1));
+        const int rc = frame_take(c, offset_limit_ms, 1, p->filter_size_surf, &id, nullptr,
+                                  p->first_scan ? down.data() : nullptr, (int64_t)down.size(), &S.n_down, &S.n_taken, dst);
+        if (rc) return finish(rc);
+    }
+    S.scan_id = id;
+    if (S.n_taken == 0) return finish(fetch_propagated());
+    // 3. the first scan builds / fills the map (through the host: once per session)
+    if (p->first_scan) {
+        S.stage = LIVO_LIO_FIRST_SCAN;
+        int rc = fetch_propagated();  // (also the wait for `down`)
+        if (!rc && S.n_down > 5) {
+            const float* xyz = reinterpret_cast<const float*>(down.data());
+            rc = ivox ? livo_ivox_add_points(c, xyz, S.n_down, sizeof(livo_raw_point))
+                      : livo_map_build(c, xyz, S.n_down, sizeof(livo_raw_point));
+            if (!rc) S.map_built = 1;
+        }
+        return finish(rc);
+    }
+    // 4. the facade's adopt_scan
+    if (p->prev_scan_id >= 0) {
+        int rc = ivox ? livo_scan_inherit_neighbors(c, id, p->prev_scan_id) : LIVO_OK;
+        if (!rc) rc = livo_scan_release(c, p->prev_scan_id);
+        if (rc) return finish(rc);
+    }
+    // 5. the IEKF loop: its slot staged from dst on the device, its end the one copy of the state
+    if (p->ekf_inited) {
+        const int rc = batch_update(c, 1, &id, kModelLaserMapping, state, nullptr, &S.iter, nullptr, nullptr, dst);
+        if (rc) return finish(rc);
+        const BatchPlan& P = c->lane[0].plan;
+        if (hslot(P, 0).ctrl.n_evals > 0) {
+            *state_propagat = hslot(P, 0).prior;
+            dst = &dslot(P, 0)->state;
+        } else {
+            // no evaluation ran (an empty scan: not reachable with n_taken > 0), so nothing wrote the slot
+            // back: the chain returns its input, the propagated state
+            const int rc2 = fetch_propagated();
+            if (rc2) return finish(rc2);
+            std::memset(&S.iter, 0, sizeof(S.iter));
+        }
+    }
+    // 6. map_incremental and 7. the publish at the state on the device
+    int rc = map_incremental(c, id, nullptr, dst, p->filter_size_map_min, p->ekf_inited, nullptr, S.map_counts);
+    if (!rc) rc = cloud_publish(c, p->dense_map_en ? -1 : id, nullptr, dst, p->match_leaf, &S.cloud);
+    if (!rc && !p->ekf_inited) rc = fetch_propagated();
+    if (rc) return finish(rc);
+    S.stage = LIVO_LIO_UPDATED;
+    return finish(LIVO_OK);
 }
 
 int livo_sync(livo_ctx* c) {

@@ -555,6 +555,7 @@ struct MapIncrParams {
     double fs;                // filter_size_map_min
     int32_t n;
     int32_t ekf_inited;
+    const double* pose;       // non-null: rot[9], pos[3] on the device, read instead of slot->state (livo_lio_frame)
 };
 int launch_map_incr(const MapIncrParams& p, void* stream);
 int launch_compact(const float* ordered, const uint32_t* flags, const uint32_t* pos, int64_t n, float* dense,
@@ -583,6 +584,9 @@ struct FrontParams {
     uint32_t* vid;            // scan of flags
     uint32_t* starts;         // n_vox + 1 run starts
     float* down;              // n_vox x 5 centroids
+    // livo_lio_frame: the frame-end pose on the device (rot[9], pos[3], the head of the propagated
+    // livo_state); non-null: k_fe_undistort forms extR_Ri and pos_end from it (the host's expressions)
+    const double* end_dev;
 };
 int launch_fe_segment(const FrontParams& F, void* stream);
 int launch_fe_undistort(const FrontParams& F, void* stream);
@@ -612,6 +616,10 @@ struct ImuBatch {
     double acc_norm;                 // mean_acc.norm()
 };
 int launch_imu_propagate(const ImuBatch& B, int32_t n, void* stream);
+// livo_lio_frame (lio_kernels.hip): the LaserMapping slot of init_slot + cov_factor, written on the
+// device from the propagated state (device memory); slot: device, its first kSlotLmBytes.
+struct IekfSlot;
+int launch_lio_stage_slot(const livo_state* src, IekfSlot* slot, int max_iter, void* stream);
 // Sensor handlers (ingest_kernels.hip): the driver's message to the time-ordered frame.
 constexpr int kIngestBlock = 256;     // message points per block of the decode and emit passes
 constexpr int kIngestMaxStep = 240;   // largest point_step: a block's records fit 60 KiB of LDS
@@ -681,7 +689,9 @@ struct CloudSrc {
 int launch_to_world(const CloudSrc& S, const WorldParams& W, float* out5, void* stream);
 // livo_cloud_publish: launch_to_world's rows of a body-frame cloud and, with minmax
 // (launch_fe_minmax's six words, initialised by the caller), the bounds of the stored floats.
-int launch_cloud_publish(const CloudSrc& S, const WorldParams& W, float* out5, unsigned* minmax, void* stream);
+// dev_pose (livo_lio_frame): rot[9], pos[3] on the device, read instead of W.rot / W.pos.
+int launch_cloud_publish(const CloudSrc& S, const WorldParams& W, float* out5, unsigned* minmax, void* stream,
+                         const double* dev_pose = nullptr);
 // publish_frame_world_rgb (rgb_kernels.hip): the cloud of launch_to_world,
 // projected into the camera frame and coloured from the BGR image, the kept
 // points compacted in the cloud's order.
@@ -927,6 +937,7 @@ struct DynAddParams {
     const float* wpts;          // scan body points, stored order (4 floats each)
     const int32_t* wperm;       // stored position -> caller index
     double wrot[9], wpos[3], R_LI[9], t_LI[3];
+    const double* wdev;         // non-null: rot[9], pos[3] on the device instead of wrot / wpos (livo_lio_frame)
 };
 int launch_add_prep(const DynAddParams& p, void* stream);
 int launch_add_group(const DynAddParams& p, void* stream);

@@ -16,6 +16,11 @@
 // same message through a host restatement of avia_handler, the time sort and the slice and the
 // Process2 that takes a host array.  Both print "take <camera> <lidar>", the "iekf" line and
 // "incr"; tests/test_facade_ingest.py compares them.
+// With "lio": three consecutive synthetic Avia frames (the scan nudged a centimetre a frame) go through
+// livox_pcl_cbk -> RunLidarFrame, one livo_lio_frame call a frame; "lio_chain" runs the same frames
+// through Process2 -> iterate -> map_incremental -> publish_cloud.  Both print, per frame, "frame <k>
+// <taken> <down> <iterations> <added> <no_downsample> <cloud n> <cloud n_down>", then "state <k>" and
+// "prop <k>" with the bytes of state and state_propagat as hex; tests/test_facade_lio.py compares them.
 // Exit status: 0 ok, 2 usage/IO, 3 livo::Error (code printed on stderr).
 #include <algorithm>
 #include <cmath>
@@ -153,12 +158,74 @@ void run_ingest(livo::LaserMappingGpu& lm, const float* scan, int64_t n, bool on
     std::printf("incr %lld %lld\n", (long long)lm.points_added, (long long)lm.points_no_downsample);
 }
 
+void print_hex(const char* what, int k, const livo_state& s) {
+    std::printf("%s %d ", what, k);
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(&s);
+    for (size_t i = 0; i < sizeof(livo_state); i++) std::printf("%02x", b[i]);
+    std::printf("\n");
+}
+
+// The lio modes (see the head of the file).  scan: body-frame xyz triples.
+void run_lio(livo::LaserMappingGpu& lm, const float* scan, int64_t n, bool one_call) {
+    const int frames = 3;
+    const float fs = 0.2f, match_leaf = 0.2f;
+    const double fs_map = 0.5;
+    double f[3];
+    for (int k = 0; k < 3; k++) {
+        f[k] = -(lm.state.rot[0 + k] * lm.state.gravity[0] + lm.state.rot[3 + k] * lm.state.gravity[1] +
+                 lm.state.rot[6 + k] * lm.state.gravity[2]) + lm.state.bias_a[k];
+        lm.imu_params.mean_acc[k] = f[k];
+    }
+    for (int fr = 0; fr < frames; fr++) {
+        const double stamp = 1000.0 + 0.11 * fr;
+        std::vector<livo_livox_point> msg((size_t)n + 1);
+        for (int64_t i = 0; i <= n; i++) {
+            livo_livox_point& p = msg[(size_t)i];
+            const float* s = scan + 3 * (i > 0 ? i - 1 : 0);
+            p.x = s[0] + 0.01f * fr, p.y = s[1] + 0.01f * fr, p.z = s[2];
+            p.offset_time = (uint32_t)(((i + 13 * fr) * 7919) % n) * (uint32_t)(100000000 / n) + 1000u;
+            p.reflectivity = 100, p.tag = 0x10, p.line = (uint8_t)(i % 6), p.pad = 0;
+        }
+        std::vector<livo_imu_sample> imu(22);  // at rest at the state, 5 ms apart from the stamp
+        for (int s = 0; s < 22; s++) {
+            imu[(size_t)s].stamp = stamp + 0.005 * s;
+            for (int k = 0; k < 3; k++) {
+                imu[(size_t)s].acc[k] = f[k];
+                imu[(size_t)s].gyr[k] = lm.state.bias_g[k] + 0.01 * (k - 1) + 0.001 * fr;
+            }
+        }
+        if (fr == 0) {
+            lm.imu_carry = livo_imu_carry{};
+            lm.imu_carry.last_imu = imu[0];
+            lm.imu_carry.last_lidar_end_time = stamp;
+        }
+        lm.livox_pcl_cbk(msg.data(), (int64_t)msg.size(), stamp);
+        long long taken, down, iters, cn, cd;
+        if (one_call) {
+            const livo_lio_stats st = lm.RunLidarFrame(imu.data() + 1, 21, fs, fs_map, true, true, match_leaf);
+            taken = st.n_taken, down = st.n_down, iters = st.iter.iterations, cn = st.cloud.n, cd = st.cloud.n_down;
+        } else {
+            taken = lm.Process2(imu.data() + 1, 21, true, 0.0, fs);
+            down = lm.feats_down_size;
+            iters = lm.iterate().iterations;
+            lm.map_incremental(fs_map, true);
+            const livo_cloud_info ci = lm.publish_cloud(true, match_leaf);
+            cn = ci.n, cd = ci.n_down;
+        }
+        std::printf("frame %d %lld %lld %lld %lld %lld %lld %lld\n", fr, taken, down, iters, (long long)lm.points_added,
+                    (long long)lm.points_no_downsample, cn, cd);
+        print_hex("state", fr, lm.state);
+        print_hex("prop", fr, lm.state_propagat);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     const std::string mode = argc == 6 ? argv[5] : "";
-    if (argc != 5 && !(argc == 6 && (mode == "ivox" || mode == "ingest" || mode == "ingest_host"))) {
-        std::fprintf(stderr, "usage: %s map.f32 scan.f32 state.f64 max_iter [ivox|ingest|ingest_host]\n", argv[0]);
+    if (argc != 5 && !(argc == 6 && (mode == "ivox" || mode == "ingest" || mode == "ingest_host" || mode == "lio" || mode == "lio_chain"))) {
+        std::fprintf(stderr, "usage: %s map.f32 scan.f32 state.f64 max_iter [ivox|ingest|ingest_host|lio|lio_chain]\n",
+                     argv[0]);
         return 2;
     }
     const bool ingest = mode == "ingest" || mode == "ingest_host";
@@ -199,6 +266,12 @@ int main(int argc, char** argv) {
             livo_ingest_params& q = lm.ingest_params;
             q.point_filter_num = 1;
             run_ingest(lm, reinterpret_cast<const float*>(scan.data()), (int64_t)(scan.size() / 12), mode == "ingest");
+            return 0;
+        }
+        if (mode == "lio" || mode == "lio_chain") {
+            lm.set_state(s0);
+            lm.ingest_params.point_filter_num = 1;
+            run_lio(lm, reinterpret_cast<const float*>(scan.data()), (int64_t)(scan.size() / 12), mode == "lio");
             return 0;
         }
         lm.set_scan(reinterpret_cast<const float*>(scan.data()), (int64_t)(scan.size() / 12));

@@ -218,6 +218,53 @@ public:
         return taken;
     }
 
+    // The LIO half of Run() on a LiDAR frame (laser_mapping.cpp:37-284) as one call on the frame the
+    // callback left on the device: Process2(..., is_lidar_end = true, ...), the first scan's map
+    // (flg_first_scan: cleared once a scan has built / filled it), iterate() behind flg_EKF_inited,
+    // map_incremental() and publish_cloud(), with `state` on the device in between: it comes to the
+    // host once, at the end, with state_propagat.  Returns the call's statistics; the members
+    // the separate methods set (state, state_propagat, imu_carry, last_update_time, the current scan,
+    // flg_EKF_converged, effct_feat_num, points_added, points_no_downsample) are set as they set them.
+    livo_lio_stats RunLidarFrame(const livo_imu_sample* imu, int32_t n_imu, float filter_size_surf,
+                                 double filter_size_map_min, bool flg_EKF_inited = true, bool dense_map_en = true,
+                                 float match_leaf = 0.2f) {
+        const double pcl_beg_time = lidar_beg_time > last_update_time ? lidar_beg_time : last_update_time;
+        const double pcl_end_time = lidar_beg_time + frame_end_curvature / double(1000);
+        const double pcl_offset_time = (pcl_end_time - lidar_beg_time) * double(1000);
+        livo_imu_job job{};
+        job.imu = imu;
+        job.n_imu = n_imu;
+        job.pcl_beg_time = pcl_beg_time;
+        job.pcl_end_time = pcl_end_time;
+        livo_lio_params p{};
+        p.filter_size_surf = filter_size_surf;
+        p.match_leaf = match_leaf;
+        p.filter_size_map_min = filter_size_map_min;
+        p.ekf_inited = flg_EKF_inited ? 1 : 0;
+        p.first_scan = flg_first_scan ? 1 : 0;
+        p.dense_map_en = dense_map_en ? 1 : 0;
+        p.prev_scan_id = scan_id_;
+        livo_lio_stats st{};
+        check(livo_lio_frame(ctx_, &job, &imu_params, &imu_carry, pcl_offset_time, &p, &state, &state_propagat, &st),
+              "livo_lio_frame");
+        last_update_time = pcl_end_time;  // (:231)
+        if (st.stage == LIVO_LIO_FIRST_SCAN) {
+            adopt_scan(st.scan_id, st.n_down);  // (the call leaves the previous scan to its owner here)
+            if (st.map_built) flg_first_scan = false;
+        } else if (st.stage == LIVO_LIO_UPDATED) {
+            scan_id_ = st.scan_id;  // (the previous one was inherited from and released inside the call)
+            feats_down_size = st.n_down;
+            nearest_search_en = true;
+            if (flg_EKF_inited) {
+                flg_EKF_converged = st.iter.converged != 0;
+                if (st.iter.iterations > 0) effct_feat_num = st.iter.effct_feat_num[st.iter.iterations - 1];
+            }
+            points_added = st.map_counts[0];
+            points_no_downsample = st.map_counts[1];
+        }
+        return st;
+    }
+
     // p_imu->IMU_init(meas, state, init_iter_num) (IMU_Processing.cpp:147-198) while imu_need_init:
     // returns true once gravity and bias_g are set (imu_need_init_ = false).
     bool IMU_init(const livo_imu_sample* imu, int32_t n_imu) {
@@ -452,6 +499,7 @@ public:
     livo_state state_propagat{};
     bool nearest_search_en = true;
     bool flg_EKF_converged = false;
+    bool flg_first_scan = false;  // RunLidarFrame: the next frame builds / fills the map (set it for a session without one)
     int64_t effct_feat_num = 0;
     int64_t feats_down_size = 0;
     int64_t points_added = 0, points_no_downsample = 0;  // last map_incremental

@@ -241,6 +241,21 @@ class CloudInfo(C.Structure):
                 ("device_bytes", C.c_int64)]
 
 
+class LioParams(C.Structure):
+    _fields_ = [("filter_size_surf", C.c_float), ("match_leaf", C.c_float), ("filter_size_map_min", C.c_double),
+                ("ekf_inited", C.c_int32), ("first_scan", C.c_int32), ("dense_map_en", C.c_int32),
+                ("prev_scan_id", C.c_int32)]
+
+
+LIO_EMPTY, LIO_FIRST_SCAN, LIO_UPDATED = 0, 1, 2  # LIVO_LIO_*
+
+
+class LioStats(C.Structure):
+    _fields_ = [("stage", C.c_int32), ("scan_id", C.c_int32), ("n_taken", C.c_int64), ("n_down", C.c_int64),
+                ("map_built", C.c_int32), ("pad_", C.c_int32), ("iter", IterStats), ("map_counts", C.c_int64 * 2),
+                ("cloud", CloudInfo)]
+
+
 def _stats_dict(st) -> dict:
     """A stats struct as a dict (arrays as lists)."""
     out = {}
@@ -467,6 +482,8 @@ SIGNATURES = {
     "livo_frame_dump": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "livo_frame_take": (C.c_int, [_P, C.c_double, C.c_int, C.c_float, C.POINTER(C.c_int32), _P, _P, C.c_int64,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "livo_lio_frame": (C.c_int, [_P, C.POINTER(ImuJob), C.POINTER(ImuParams), C.POINTER(ImuCarry), C.c_double,
+                                 C.POINTER(LioParams), C.POINTER(State), C.POINTER(State), C.POINTER(LioStats)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -1087,6 +1104,34 @@ class Context:
         if sid.value >= 0:
             self.scans[sid.value] = int(nd.value)
         return nt.value, sid.value, und[:nt.value].copy(), down[:nd.value].copy()
+
+    def lio_frame(self, imu: np.ndarray, pcl_beg_time: float, pcl_end_time: float, params: dict | None, carry: dict,
+                  state: dict, offset_limit_ms: float, filter_size_surf: float = 0.5, filter_size_map_min: float = 0.5,
+                  match_leaf: float = 0.2, ekf_inited: bool = True, first_scan: bool = False,
+                  dense_map_en: bool = True, prev_scan_id: int = -1):
+        """One LiDAR frame of the ingested message in one call (livo_lio_frame): imu_propagate, frame_take,
+        the first scan's map or adopt + iekf_update + map_incremental + cloud_publish, the state on the device
+        in between.  -> (state, state_propagat, carry, stats); stats: stage (LIO_*), scan_id, n_taken, n_down,
+        map_built, iter (the raw IterStats bytes as `iter_raw`, and iekf_update's dict as `iter`), map_counts,
+        cloud (cloud_info's dict)."""
+        imu = np.ascontiguousarray(imu, np.float64).reshape(-1, 7)
+        job = ImuJob(_ptr(imu).value if imu.shape[0] else None, imu.shape[0], pcl_beg_time, pcl_end_time)
+        q, cy, s, sp = imu_params_to_c(params), imu_carry_to_c(carry), state_to_c(state), State()
+        lp = LioParams(filter_size_surf, match_leaf, filter_size_map_min, int(bool(ekf_inited)), int(bool(first_scan)),
+                       int(bool(dense_map_en)), int(prev_scan_id))
+        ls = LioStats()
+        _check("livo_lio_frame", self._L.livo_lio_frame(self.h, C.byref(job), C.byref(q), C.byref(cy), offset_limit_ms,
+                                                        C.byref(lp), C.byref(s), C.byref(sp), C.byref(ls)))
+        if ls.scan_id >= 0:
+            self.scans[ls.scan_id] = int(ls.n_down)
+        if ls.stage == LIO_UPDATED and prev_scan_id >= 0:
+            self.scans.pop(prev_scan_id, None)
+        stats = {"stage": ls.stage, "scan_id": ls.scan_id, "n_taken": ls.n_taken, "n_down": ls.n_down,
+                 "map_built": ls.map_built, "iter": stats_from_c(ls.iter),
+                 "iter_raw": np.frombuffer(bytes(ls.iter), np.uint8).copy(),
+                 "map_counts": [int(ls.map_counts[0]), int(ls.map_counts[1])],
+                 "cloud": {f: int(getattr(ls.cloud, f)) for f, _ in CloudInfo._fields_ if f != "pad_"}}
+        return state_from_c(s), state_from_c(sp), imu_carry_from_c(cy), stats
 
     # ------------------------------------------------------------ VIO ----
     def vio_update(self, frame: dict, state: dict, prior: dict | None = None, max_iter: int = 4,

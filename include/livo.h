@@ -1030,6 +1030,62 @@ int livo_frame_take(livo_ctx* ctx, double offset_limit_ms, int is_lidar_end, flo
                     livo_raw_point* undistorted, livo_raw_point* down, int64_t down_cap, int64_t* n_down,
                     int64_t* n_taken);
 
+/* ---- One LiDAR frame in one call: the LIO half of LaserMapping::Run() (laser_mapping.cpp:37-284) ---- */
+typedef struct livo_lio_params {
+    float   filter_size_surf;     /* livo_frame_take's leaf_size */
+    float   match_leaf;           /* livo_cloud_publish's; <= 0: no pg_down */
+    double  filter_size_map_min;  /* livo_map_incremental's fs */
+    int32_t ekf_inited;           /* flg_EKF_inited (laser_mapping.cpp:79): 0 skips the IEKF loop */
+    int32_t first_scan;           /* ikdtree.Root_Node == nullptr / flg_first_scan (:133-152) */
+    int32_t dense_map_en;         /* publish the full-resolution frame (-1) or the new scan */
+    int32_t prev_scan_id;         /* the facade's current scan, -1: none */
+} livo_lio_params;
+
+enum { LIVO_LIO_EMPTY = 0, LIVO_LIO_FIRST_SCAN = 1, LIVO_LIO_UPDATED = 2 };
+
+typedef struct livo_lio_stats {
+    int32_t stage;                /* LIVO_LIO_* */
+    int32_t scan_id;              /* the new resident scan, -1 if none */
+    int64_t n_taken, n_down;
+    int32_t map_built;            /* FIRST_SCAN: 1 if n_down > 5 and the map was built / filled */
+    int32_t pad_;
+    livo_iter_stats iter;         /* zeroed when the loop did not run */
+    int64_t map_counts[2];        /* livo_map_incremental's */
+    livo_cloud_info cloud;        /* livo_cloud_publish's (zeroed unless stage == LIVO_LIO_UPDATED) */
+} livo_lio_stats;
+
+/* Everything between "the driver's message is resident" (livo_frame_ingest_*) and "the map and
+ * pcl_wait_pub are updated", with the state on the device from the propagation to the publish.  The
+ * call equals this chain, byte for byte, in *state, *state_propagat, *carry, *stats, livo_map_dump /
+ * livo_ivox_dump, livo_frame_to_world(LIVO_CLOUD_WORLD / LIVO_CLOUD_WORLD_DOWN), livo_cloud_info_get
+ * and the resident Pose6D table:
+ *   1. livo_imu_propagate(job, imu, carry, state), then *state_propagat = *state (:58-59);
+ *   2. livo_frame_take(offset_limit_ms, is_lidar_end = 1, filter_size_surf, &scan_id); n_taken == 0:
+ *      LIVO_LIO_EMPTY, nothing further runs and prev_scan_id stays resident;
+ *   3. first_scan (:133-152): with n_down > 5, livo_map_build (ikd-Tree backend) or
+ *      livo_ivox_add_points (iVox) of the down-sampled points; LIVO_LIO_FIRST_SCAN either way, no loop,
+ *      no map_incremental, no publish, prev_scan_id untouched;
+ *   4. prev_scan_id >= 0: livo_scan_inherit_neighbors(scan_id, prev_scan_id) on the iVox backend, then
+ *      livo_scan_release(prev_scan_id);
+ *   5. ekf_inited: livo_iekf_update(scan_id, state, state_propagat, &iter);
+ *   6. livo_map_incremental(scan_id, state, filter_size_map_min, ekf_inited, NULL, map_counts);
+ *   7. livo_cloud_publish(dense_map_en ? -1 : scan_id, state, match_leaf, &cloud): LIVO_LIO_UPDATED.
+ * The propagated state is not copied to the host between the stages: the de-skew reads its end pose,
+ * the IEKF slot (state, prior, the covariance factors) is staged from it by a kernel, and stages 6 and 7
+ * read the pose from the loop's slot (ekf_inited == 0: from the propagated state).  The host receives
+ * the state once, at the end, with the carry, iter and the counts that size launches.
+ * The refusals listed here happen before any launch and change nothing (the cursor, *carry, *state,
+ * the map and the published cloud stay); an error a stage reports later (LIVO_E_OOM, LIVO_E_HIP,
+ * LIVO_E_RANGE) leaves what the stages before it did.  LIVO_E_INVALID: a NULL argument (stats may be NULL), no ingest yet, what the
+ * seven calls refuse in their own arguments (n_imu < 0, samples missing, a non-finite
+ * filter_size_surf or match_leaf, filter_size_map_min not > 0); LIVO_E_NOMAP: first_scan == 0 on a
+ * backend that holds no map (iVox: not initialised, whatever first_scan is); LIVO_E_NOSCAN: an
+ * unknown prev_scan_id; LIVO_E_BUSY: a submitted batch is in flight; LIVO_E_HIP: no device.  Two
+ * calls on the same input give the same bytes. */
+int livo_lio_frame(livo_ctx* ctx, const livo_imu_job* job, const livo_imu_params* imu, livo_imu_carry* carry,
+                   double offset_limit_ms, const livo_lio_params* p, livo_state* state, livo_state* state_propagat,
+                   livo_lio_stats* stats);
+
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
  * out[0] by a sort of every id, out[1] by merging the added ids into the grid;
