@@ -38,6 +38,7 @@ SOURCES = [
     ("vis_kernels.hip", True),
     ("vmap_kernels.hip", True),
     ("ikd_incr_kernels.hip", True),
+    ("std_kernels.hip", True),
     ("prims.hip", True),
     ("livo_capi.cpp", False),
     ("map_build.cpp", False),

@@ -415,6 +415,41 @@ struct IngestDev {
     livo_ingest_info info{};
 };
 
+// The loop search (livo_std_*): the database in one allocation sized by livo_std_reset, the
+// staged key frame and the search's match arrays in two that grow.
+struct StdDev {
+    bool ready = false, staged = false, searched = false, cells_known = false;
+    livo_std_params prm{};
+    int64_t max_descs = 0, max_frames = 0, max_planes = 0;
+    int64_t n_descs = 0, n_planes = 0, cells = 0;
+    int32_t n_frames = 0;
+    std::vector<uint32_t> plane_off;   // the host's copy of the frames' plane ranges
+    void* buf = nullptr;               // records, both index copies, planes, the per-frame and per-candidate arrays
+    size_t bytes = 0;
+    StdHot* hot = nullptr;
+    StdVerts* verts = nullptr;
+    unsigned long long* skey[2] = {};  // the sorted (cell key, sequence) index; a commit merges cur -> 1 - cur
+    uint32_t* sseq[2] = {};
+    int cur = 0;
+    livo_std_plane* planes = nullptr;
+    uint32_t* d_plane_off = nullptr;
+    StdParams P{};                     // the search's arrays (those carved from buf; the others per call)
+    void* stage = nullptr;             // the staged frame, its new index entries and per-source counts
+    size_t stage_bytes = 0;
+    livo_std_desc* src = nullptr;
+    livo_std_plane* src_planes = nullptr;
+    unsigned long long *nkey = nullptr, *snkey = nullptr;
+    uint32_t *nseq = nullptr, *snseq = nullptr;
+    int64_t n_src = 0, n_src_planes = 0;
+    uint32_t id_min = 0, id_max = 0;   // of the staged frame_ids
+    void* mbuf = nullptr;              // matches, their keys and order, the success lists
+    size_t mbytes = 0;
+    int64_t n_matches = 0;
+    int32_t n_cand = 0;
+    std::vector<livo_std_candidate> cands;  // the last search's records
+    std::vector<uint32_t> coff;
+};
+
 struct livo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -481,6 +516,7 @@ struct livo_ctx {
     WorldCloud wcloud;                 // livo_cloud_publish: pcl_wait_pub and pg_down
     ImuDev imu;                        // livo_imu_propagate(_batch): stream, staging, the resident Pose6D table
     IngestDev ing;                     // livo_frame_ingest_*: the current frame and its cursor
+    StdDev stdb;                       // livo_std_*: the loop search's database, staged frame and last search
     void* vio_buf = nullptr;           // VIO frame (image, points, partials, slot)
     size_t vio_bytes = 0;
     DevImage bgr_img;                  // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
@@ -2121,6 +2157,9 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->fe_buf) (void)hipFree(c->fe_buf);
     if (c->wcloud.buf) (void)hipFree(c->wcloud.buf);
     if (c->ing.buf) (void)hipFree(c->ing.buf);
+    if (c->stdb.buf) (void)hipFree(c->stdb.buf);
+    if (c->stdb.stage) (void)hipFree(c->stdb.stage);
+    if (c->stdb.mbuf) (void)hipFree(c->stdb.mbuf);
     if (c->imu.st) (void)hipStreamSynchronize(c->imu.st);
     if (c->imu.buf) (void)hipFree(c->imu.buf);
     if (c->imu.table) (void)hipFree(c->imu.table);
@@ -6020,6 +6059,348 @@ int livo_lio_frame(livo_ctx* c, const livo_imu_job* job, const livo_imu_params* 
     if (rc) return finish(rc);
     S.stage = LIVO_LIO_UPDATED;
     return finish(LIVO_OK);
+}
+
+// ---- Loop search: the resident STD database and SearchLoop (include/STD/STDesc.cpp:299-374, :960-1280) ----
+int livo_std_params_default(livo_std_params* p) {
+    if (!p) return LIVO_E_INVALID;
+    p->skip_near_num = 50;  // read_parameters, STDesc.cpp:83-93
+    p->candidate_num = 50;
+    p->rough_dis_threshold = 0.01;
+    p->vertex_diff_threshold = 0.5;
+    p->icp_threshold = 0.5;
+    p->normal_threshold = 0.2;
+    p->dis_threshold = 0.5;
+    return LIVO_OK;
+}
+
+static bool std_params_ok(const livo_std_params* p) {
+    if (!p || p->skip_near_num < 0 || p->candidate_num < 0 || p->candidate_num > LIVO_STD_MAX_CANDIDATES) return false;
+    const double t[5] = {p->rough_dis_threshold, p->vertex_diff_threshold, p->icp_threshold, p->normal_threshold,
+                         p->dis_threshold};
+    for (double v : t)
+        if (!std::isfinite(v) || v < 0.0) return false;
+    return true;
+}
+
+constexpr int64_t kStdMaxCount = (int64_t)0x7FFFFFFF - 1024;
+
+int livo_std_reset(livo_ctx* c, const livo_std_params* p, int64_t max_descs, int64_t max_frames, int64_t max_planes) {
+    if (!c || !std_params_ok(p) || max_descs < 1 || max_frames < 1 || max_planes < 1) return LIVO_E_INVALID;
+    if (max_frames > LIVO_STD_MAX_FRAMES || max_descs > kStdMaxCount || max_planes > kStdMaxCount) return LIVO_E_RANGE;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (set_device(c)) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    HIP_TRY(stream_wait(c->stream));  // a commit may still be writing the arrays this replaces
+    D.ready = D.staged = D.searched = false;
+    StdParams& P = D.P;
+    P = StdParams{};
+    const size_t nd = (size_t)max_descs, nf = (size_t)max_frames;
+    auto layout = [&](Carve k) {
+        D.hot = k.take<StdHot>(nd);
+        D.verts = k.take<StdVerts>(nd);
+        for (int b = 0; b < 2; b++) {
+            D.skey[b] = k.take<unsigned long long>(nd);
+            D.sseq[b] = k.take<uint32_t>(nd);
+        }
+        D.planes = k.take<livo_std_plane>((size_t)max_planes);
+        D.d_plane_off = k.take<uint32_t>(nf + 1);
+        P.votes = k.take<uint32_t>(nf);
+        P.cand_of_frame = k.take<int32_t>(nf);
+        P.coff = k.take<uint32_t>(LIVO_STD_MAX_CANDIDATES + 1);
+        P.cands = k.take<livo_std_candidate>(LIVO_STD_MAX_CANDIDATES);
+        P.vote_list = k.take<uint32_t>((size_t)LIVO_STD_MAX_CANDIDATES * kStdSamples);
+        P.sample_rt = k.take<double>((size_t)LIVO_STD_MAX_CANDIDATES * kStdSamples * 12);
+        P.n_succ = k.take<uint32_t>(LIVO_STD_MAX_CANDIDATES);
+        P.ctr = k.take<unsigned>(kStdCtrN);
+        P.result = k.take<livo_std_result>(1);
+        return k.total();
+    };
+    RC_TRY(ensure_dev_bytes(&D.buf, &D.bytes, layout(Carve{nullptr})));
+    layout(Carve{(char*)D.buf});
+    HIP_TRY(hipMemsetAsync(D.d_plane_off, 0, 4, c->stream));
+    D.prm = *p;
+    D.max_descs = max_descs;
+    D.max_frames = max_frames;
+    D.max_planes = max_planes;
+    D.n_descs = D.n_planes = D.cells = 0;
+    D.n_frames = 0;
+    D.cur = 0;
+    D.cells_known = true;
+    D.plane_off.assign(1, 0u);
+    D.n_cand = 0;
+    D.n_matches = 0;
+    D.ready = true;
+    return LIVO_OK;
+}
+
+int livo_std_stage(livo_ctx* c, const livo_std_desc* descs, int64_t n, const livo_std_plane* planes, int64_t m) {
+    if (!c || n < 0 || m < 0 || (n > 0 && !descs) || (m > 0 && !planes)) return LIVO_E_INVALID;
+    if (n > kStdMaxCount || m > kStdMaxCount) return LIVO_E_RANGE;
+    uint32_t id_min = 0xFFFFFFFFu, id_max = 0u;
+    for (int64_t i = 0; i < n; i++) {
+        const double* v = descs[i].side_length;  // the six vectors lie one behind the other
+        for (int k = 0; k < 18; k++)
+            if (!std::isfinite(v[k])) return LIVO_E_INVALID;
+        for (int k = 0; k < 3; k++)
+            if (std::fabs(v[k]) >= (double)(kStdCellBias - 2)) return LIVO_E_RANGE;
+        id_min = std::min(id_min, descs[i].frame_id);
+        id_max = std::max(id_max, descs[i].frame_id);
+    }
+    for (int64_t i = 0; i < m; i++)
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(planes[i].xyz[k]) || !std::isfinite(planes[i].normal[k])) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready) return LIVO_E_INVALID;
+    if (set_device(c)) return LIVO_E_HIP;
+    D.staged = D.searched = false;
+    const size_t nn = (size_t)std::max<int64_t>(n, 1), mm = (size_t)std::max<int64_t>(m, 1);
+    auto layout = [&](Carve k) {
+        D.src = k.take<livo_std_desc>(nn);
+        D.src_planes = k.take<livo_std_plane>(mm);
+        D.nkey = k.take<unsigned long long>(nn);
+        D.snkey = k.take<unsigned long long>(nn);
+        D.nseq = k.take<uint32_t>(nn);
+        D.snseq = k.take<uint32_t>(nn);
+        D.P.cnt = k.take<uint32_t>(nn);
+        D.P.off = k.take<uint32_t>(nn);
+        return k.total();
+    };
+    const size_t need = layout(Carve{nullptr});
+    if (need > D.stage_bytes) HIP_TRY(stream_wait(c->stream));  // (a commit may still read the frame it replaces)
+    RC_TRY(ensure_dev_bytes(&D.stage, &D.stage_bytes, need));
+    layout(Carve{(char*)D.stage});
+    if (n > 0) HIP_TRY(hipMemcpyAsync(D.src, descs, (size_t)n * sizeof(livo_std_desc), hipMemcpyHostToDevice, c->stream));
+    if (m > 0)
+        HIP_TRY(hipMemcpyAsync(D.src_planes, planes, (size_t)m * sizeof(livo_std_plane), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(stream_wait(c->stream));  // host pointers are read before return
+    D.n_src = n;
+    D.n_src_planes = m;
+    D.id_min = id_min;
+    D.id_max = id_max;
+    D.staged = true;
+    return LIVO_OK;
+}
+
+// The search's parameter block over the database as it stands.
+static StdParams std_search_params(StdDev& D) {
+    StdParams P = D.P;
+    P.prm = D.prm;
+    P.hot = D.hot;
+    P.verts = D.verts;
+    P.skey = D.skey[D.cur];
+    P.sseq = D.sseq[D.cur];
+    P.n_db = D.n_descs;
+    P.n_frames = D.n_frames;
+    P.planes = D.planes;
+    P.plane_off = D.d_plane_off;
+    P.src = D.src;
+    P.n_src = (int32_t)D.n_src;
+    P.src_planes = D.src_planes;
+    P.n_src_planes = (int32_t)D.n_src_planes;
+    return P;
+}
+
+int livo_std_search(livo_ctx* c, livo_std_result* out, livo_std_pair* pairs, int64_t cap, int64_t* n_pairs) {
+    if (!c || !out || cap < 0) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready || !D.staged) return LIVO_E_INVALID;
+    if (set_device(c)) return LIVO_E_HIP;
+    D.searched = false;
+    D.n_cand = 0;
+    D.n_matches = 0;
+    livo_std_result R{};
+    R.frame = R.candidate = -1;
+    R.rot[0] = R.rot[4] = R.rot[8] = 1.0;
+    if (n_pairs) *n_pairs = 0;
+    if (D.n_src > 0 && D.n_frames > 0) {  // (:304: no descriptors, no search; an empty database holds no match)
+        StdParams P = std_search_params(D);
+        const size_t nf = (size_t)D.n_frames;
+        HIP_TRY(hipMemsetAsync(P.votes, 0, nf * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(P.cand_of_frame, 0xFF, nf * 4, c->stream));
+        RC_TRY(launch_std_match(P, false, c->stream));
+        RC_TRY(scan_u32(c, P.cnt, P.off, D.n_src));
+        RC_TRY(launch_std_rank(P, c->stream));
+        unsigned h[2];
+        HIP_TRY(hipMemcpyAsync(h, P.ctr, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(stream_wait(c->stream));  // wait 1: the match total sizes the arrays and launches below
+        const int64_t total = h[kStdCtrTotal];
+        const int32_t n_cand = (int32_t)h[kStdCtrCands];
+        R.n_candidates = n_cand;
+        if (n_cand > 0) {
+            uint32_t *smkey, *smval;
+            auto layout = [&](Carve k) {
+                P.matches = k.take<livo_std_pair>((size_t)total);
+                P.mkey = k.take<uint32_t>((size_t)total);
+                P.mval = k.take<uint32_t>((size_t)total);
+                smkey = k.take<uint32_t>((size_t)total);
+                smval = k.take<uint32_t>((size_t)total);
+                P.succ = k.take<livo_std_pair>((size_t)total);
+                return k.total();
+            };
+            RC_TRY(ensure_dev_bytes(&D.mbuf, &D.mbytes, layout(Carve{nullptr})));
+            layout(Carve{(char*)D.mbuf});
+            P.sval = smval;
+            RC_TRY(launch_std_match(P, true, c->stream));
+            RC_TRY(launch_std_keys(P, total, c->stream));
+            RC_TRY(sort_u32(c, P.mkey, smkey, P.mval, smval, total, 7));
+            RC_TRY(launch_std_verify(P, n_cand, c->stream));
+            D.cands.resize((size_t)n_cand);
+            D.coff.resize((size_t)n_cand + 1);
+            HIP_TRY(hipMemcpyAsync(&R, P.result, sizeof(R), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(D.cands.data(), P.cands, (size_t)n_cand * sizeof(livo_std_candidate),
+                                   hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(D.coff.data(), P.coff, ((size_t)n_cand + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(stream_wait(c->stream));  // wait 2: the result
+            D.P.matches = P.matches;
+            D.P.sval = P.sval;
+            D.n_matches = total;
+            D.n_cand = n_cand;
+            if (R.frame >= 0 && pairs && R.n_pairs > 0) {
+                const int64_t k = std::min<int64_t>(cap, R.n_pairs);
+                if (k > 0) {
+                    HIP_TRY(hipMemcpyAsync(pairs, P.succ + D.coff[(size_t)R.candidate], (size_t)k * sizeof(livo_std_pair),
+                                           hipMemcpyDeviceToHost, c->stream));
+                    HIP_TRY(stream_wait(c->stream));  // wait 3, only with a loop whose pairs are asked for
+                }
+            }
+        }
+    }
+    if (n_pairs) *n_pairs = R.n_pairs;
+    *out = R;
+    D.searched = true;
+    return LIVO_OK;
+}
+
+int livo_std_commit(livo_ctx* c, int32_t* frame) {
+    if (!c) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready || !D.staged) return LIVO_E_INVALID;
+    if (D.n_src > 0 && (D.id_min != D.id_max || D.id_min != (uint32_t)D.n_frames)) return LIVO_E_INVALID;
+    if (D.n_frames + 1 > D.max_frames || D.n_descs + D.n_src > D.max_descs || D.n_planes + D.n_src_planes > D.max_planes)
+        return LIVO_E_CAPACITY;
+    if (set_device(c)) return LIVO_E_HIP;
+    StdCommit K{};
+    K.src = D.src;
+    K.n = D.n_src;
+    K.n0 = D.n_descs;
+    K.src_planes = D.src_planes;
+    K.m = D.n_src_planes;
+    K.p0 = D.n_planes;
+    K.frame = D.n_frames;
+    K.hot = D.hot;
+    K.verts = D.verts;
+    K.planes = D.planes;
+    K.plane_off = D.d_plane_off;
+    K.nkey = D.nkey;
+    K.nseq = D.nseq;
+    RC_TRY(launch_std_commit(K, c->stream));
+    if (D.n_src > 0) {
+        RC_TRY(sort_u64(c, D.nkey, D.snkey, D.nseq, D.snseq, D.n_src));
+        RC_TRY(launch_std_merge(D.skey[D.cur], D.sseq[D.cur], D.n_descs, D.snkey, D.snseq, D.n_src, D.skey[1 - D.cur],
+                                D.sseq[1 - D.cur], c->stream));
+        D.cur = 1 - D.cur;
+        D.cells_known = false;
+    }
+    D.n_descs += D.n_src;
+    D.n_planes += D.n_src_planes;
+    D.plane_off.push_back((uint32_t)D.n_planes);
+    if (frame) *frame = D.n_frames;
+    D.n_frames++;
+    D.searched = false;  // (the last search's lists index the arrays of the index before the merge)
+    return LIVO_OK;
+}
+
+int livo_std_candidates(livo_ctx* c, livo_std_candidate* out, int64_t cap, int64_t* n) {
+    if (!c || !n || cap < 0) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready || !D.searched) return LIVO_E_INVALID;
+    *n = D.n_cand;
+    if (!out) return LIVO_OK;
+    if (cap < D.n_cand) return LIVO_E_RANGE;
+    for (int32_t k = 0; k < D.n_cand; k++) out[k] = D.cands[(size_t)k];
+    return LIVO_OK;
+}
+
+int livo_std_matches(livo_ctx* c, int32_t candidate, livo_std_pair* pairs, int64_t cap, int64_t* n) {
+    if (!c || !n || cap < 0) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready || !D.searched || candidate < 0 || candidate >= D.n_cand) return LIVO_E_INVALID;
+    const int64_t len = D.cands[(size_t)candidate].votes;
+    *n = len;
+    if (!pairs) return LIVO_OK;
+    if (cap < len) return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    std::vector<uint32_t> order((size_t)len);
+    std::vector<livo_std_pair> all((size_t)D.n_matches);
+    HIP_TRY(hipMemcpyAsync(order.data(), D.P.sval + D.coff[(size_t)candidate], (size_t)len * 4, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(all.data(), D.P.matches, (size_t)D.n_matches * sizeof(livo_std_pair), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(stream_wait(c->stream));
+    for (int64_t j = 0; j < len; j++) pairs[j] = all[order[(size_t)j]];
+    return LIVO_OK;
+}
+
+int livo_std_info_get(livo_ctx* c, livo_std_info* info) {
+    if (!c || !info) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready) return LIVO_E_INVALID;
+    if (!D.cells_known) {
+        if (set_device(c)) return LIVO_E_HIP;
+        unsigned cells = 0;
+        HIP_TRY(hipMemsetAsync(D.P.ctr + kStdCtrCells, 0, 4, c->stream));
+        RC_TRY(launch_std_count_cells(D.skey[D.cur], D.n_descs, D.P.ctr, c->stream));
+        HIP_TRY(hipMemcpyAsync(&cells, D.P.ctr + kStdCtrCells, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(stream_wait(c->stream));
+        D.cells = cells;
+        D.cells_known = true;
+    }
+    info->frames = D.n_frames;
+    info->descs = D.n_descs;
+    info->planes = D.n_planes;
+    info->cells = D.cells;
+    info->max_descs = D.max_descs;
+    info->max_frames = D.max_frames;
+    info->max_planes = D.max_planes;
+    info->staged_descs = D.staged ? D.n_src : -1;
+    info->staged_planes = D.staged ? D.n_src_planes : -1;
+    return LIVO_OK;
+}
+
+int livo_std_dump(livo_ctx* c, livo_std_desc* descs, int64_t desc_cap, int64_t* n_descs, int32_t frame,
+                  livo_std_plane* planes, int64_t plane_cap, int64_t* n_planes) {
+    if (!c || desc_cap < 0 || plane_cap < 0) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready || frame >= D.n_frames) return LIVO_E_INVALID;
+    if (set_device(c)) return LIVO_E_HIP;
+    if (n_descs) *n_descs = D.n_descs;
+    if (descs && D.n_descs > 0) {
+        if (desc_cap < D.n_descs) return LIVO_E_RANGE;
+        RC_TRY(ensure_scratch(c, (size_t)D.n_descs * sizeof(livo_std_desc)));
+        RC_TRY(launch_std_unpack(D.hot, D.verts, D.n_descs, (livo_std_desc*)c->scratch, c->stream));
+        HIP_TRY(hipMemcpyAsync(descs, c->scratch, (size_t)D.n_descs * sizeof(livo_std_desc), hipMemcpyDeviceToHost,
+                               c->stream));
+        HIP_TRY(stream_wait(c->stream));
+    }
+    if (frame >= 0) {
+        const int64_t p0 = D.plane_off[(size_t)frame], np = (int64_t)D.plane_off[(size_t)frame + 1] - p0;
+        if (n_planes) *n_planes = np;
+        if (planes && np > 0) {
+            if (plane_cap < np) return LIVO_E_RANGE;
+            HIP_TRY(hipMemcpyAsync(planes, D.planes + p0, (size_t)np * sizeof(livo_std_plane), hipMemcpyDeviceToHost,
+                                   c->stream));
+            HIP_TRY(stream_wait(c->stream));
+        }
+    }
+    return LIVO_OK;
 }
 
 int livo_sync(livo_ctx* c) {

@@ -1042,4 +1042,75 @@ int launch_inherit_nn(NNRec* dst, const int32_t* dst_perm, int64_t n_dst, const 
 // gpts (the cell grid's points its keys index) and loses the bit.
 int launch_fill_nn_coords(NNRec* nn, int64_t n, const float* gpts, void* stream);
 
+// ---- Loop search (std_kernels.hip): the resident STD database and SearchLoop ----
+// What the cell scan reads of a stored descriptor, one 64-byte line; the vertices,
+// which only matched pairs need, lie apart (StdVerts).
+struct alignas(64) StdHot {
+    double side[3], att[3];
+    uint32_t frame, pad;
+};
+static_assert(sizeof(StdHot) == 64, "hot record");
+struct StdVerts {
+    double A[3], B[3], C[3], center[3];
+};
+constexpr int kStdSamples = 50;       // candidate_verify's use_size bound (size / (size / 50 + 1))
+constexpr int kStdCellBias = 1 << 20; // cell coordinates are packed 21 bits an axis
+constexpr uint32_t kStdNoCand = LIVO_STD_MAX_CANDIDATES;  // a match's sort key when its frame is no candidate
+enum { kStdCtrTotal = 0, kStdCtrCands = 1, kStdCtrCells = 2, kStdCtrN = 4 };
+
+struct StdParams {
+    livo_std_params prm;
+    // the database: records in insertion order, the (cell key, sequence) index sorted
+    const StdHot* hot;
+    const StdVerts* verts;
+    const unsigned long long* skey;
+    const uint32_t* sseq;
+    int64_t n_db;
+    int32_t n_frames;
+    const livo_std_plane* planes;
+    const uint32_t* plane_off;  // n_frames + 1
+    // the staged key frame
+    const livo_std_desc* src;
+    int32_t n_src;
+    const livo_std_plane* src_planes;
+    int32_t n_src_planes;
+    // the search's arrays
+    uint32_t *cnt, *off;        // per source descriptor: matches, their exclusive scan
+    uint32_t* votes;            // per stored frame
+    int32_t* cand_of_frame;
+    livo_std_pair* matches;     // every match in selector order
+    uint32_t *mkey, *mval;      // candidate index per match / iota, and sorted by it:
+    const uint32_t* sval;       // a candidate's list = sval[coff[k] .. coff[k] + votes)
+    uint32_t* coff;
+    livo_std_candidate* cands;
+    uint32_t* vote_list;        // kStdSamples a candidate
+    double* sample_rt;          // 12 doubles a (candidate, sample): rot row-major, t
+    livo_std_pair* succ;        // success lists, at coff[k]
+    uint32_t* n_succ;
+    unsigned* ctr;              // kStdCtr*
+    livo_std_result* result;
+};
+int launch_std_match(const StdParams& p, bool emit, void* stream);
+int launch_std_rank(const StdParams& p, void* stream);
+int launch_std_keys(const StdParams& p, int64_t total, void* stream);
+int launch_std_verify(const StdParams& p, int n_cand, void* stream);
+struct StdCommit {
+    const livo_std_desc* src;
+    int64_t n, n0;              // staged descriptors, descriptors stored before them
+    const livo_std_plane* src_planes;
+    int64_t m, p0;
+    int32_t frame;
+    StdHot* hot;
+    StdVerts* verts;
+    livo_std_plane* planes;
+    uint32_t* plane_off;
+    unsigned long long* nkey;
+    uint32_t* nseq;
+};
+int launch_std_commit(const StdCommit& c, void* stream);
+int launch_std_merge(const unsigned long long* okey, const uint32_t* oseq, int64_t n0, const unsigned long long* nkey,
+                     const uint32_t* nseq, int64_t n, unsigned long long* dkey, uint32_t* dseq, void* stream);
+int launch_std_count_cells(const unsigned long long* skey, int64_t n, unsigned* ctr, void* stream);
+int launch_std_unpack(const StdHot* hot, const StdVerts* verts, int64_t n, livo_std_desc* out, void* stream);
+
 }  // namespace livo

@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -219,14 +220,67 @@ void run_lio(livo::LaserMappingGpu& lm, const float* scan, int64_t n, bool one_c
     }
 }
 
+// The loop mode: a sequence file (int32 n_frames, skip_near_num, candidate_num, 0; per frame int32 n, m,
+// then n livo_std_desc and m livo_std_plane) through StdStage / SearchLoop / AddSTDescs, one key frame
+// after the other as loop_detect does.  Prints "loop <k> <frame> <n_candidates> <n_pairs> <score rot t as
+// hex>" and "pairs <k> <src:frame:db_index ...>".
+int run_loop(const std::vector<char>& seq) {
+    if (seq.size() < 16) return 2;
+    const int32_t* head = reinterpret_cast<const int32_t*>(seq.data());
+    livo::LaserMappingGpu lm(0, nullptr);
+    livo_std_params q;
+    livo::check(livo_std_params_default(&q), "livo_std_params_default");
+    q.skip_near_num = head[1];
+    q.candidate_num = head[2];
+    lm.StdReset(1 << 16, head[0], 1 << 16, &q);
+    size_t off = 16;
+    for (int32_t k = 0; k < head[0]; k++) {
+        if (off + 8 > seq.size()) return 2;
+        int32_t nm[2];
+        std::memcpy(nm, seq.data() + off, 8);
+        off += 8;
+        if (nm[0] < 0 || nm[1] < 0 ||
+            off + (size_t)nm[0] * sizeof(livo_std_desc) + (size_t)nm[1] * sizeof(livo_std_plane) > seq.size())
+            return 2;
+        std::vector<livo_std_desc> descs((size_t)nm[0]);
+        std::vector<livo_std_plane> planes((size_t)nm[1]);
+        std::memcpy(descs.data(), seq.data() + off, descs.size() * sizeof(livo_std_desc));
+        off += descs.size() * sizeof(livo_std_desc);
+        std::memcpy(planes.data(), seq.data() + off, planes.size() * sizeof(livo_std_plane));
+        off += planes.size() * sizeof(livo_std_plane);
+        lm.StdStage(descs, planes);
+        const livo::LaserMappingGpu::LoopResult r = lm.SearchLoop();
+        if (lm.AddSTDescs() != k) return 1;
+        std::printf("loop %d %d %d %zu ", k, r.frame, r.n_candidates, r.pairs.size());
+        double v[13] = {r.score};
+        for (int i = 0; i < 9; i++) v[1 + i] = r.rot[i];
+        for (int i = 0; i < 3; i++) v[10 + i] = r.t[i];
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(v);
+        for (size_t i = 0; i < sizeof(v); i++) std::printf("%02x", b[i]);
+        std::printf("\npairs %d", k);
+        for (const livo_std_pair& p : r.pairs) std::printf(" %d:%d:%d", p.src, p.frame, p.db_index);
+        std::printf("\n");
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     const std::string mode = argc == 6 ? argv[5] : "";
-    if (argc != 5 && !(argc == 6 && (mode == "ivox" || mode == "ingest" || mode == "ingest_host" || mode == "lio" || mode == "lio_chain"))) {
-        std::fprintf(stderr, "usage: %s map.f32 scan.f32 state.f64 max_iter [ivox|ingest|ingest_host|lio|lio_chain]\n",
-                     argv[0]);
+    if (argc != 5 && !(argc == 6 && (mode == "ivox" || mode == "ingest" || mode == "ingest_host" || mode == "lio" || mode == "lio_chain" || mode == "loop"))) {
+        std::fprintf(stderr, "usage: %s map.f32 scan.f32 state.f64 max_iter [ivox|ingest|ingest_host|lio|lio_chain]\n"
+                             "       %s sequence.bin - - 0 loop\n",
+                     argv[0], argv[0]);
         return 2;
+    }
+    if (mode == "loop") {
+        try {
+            return run_loop(slurp(argv[1]));
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 1;
+        }
     }
     const bool ingest = mode == "ingest" || mode == "ingest_host";
     const bool ivox = argc == 6;

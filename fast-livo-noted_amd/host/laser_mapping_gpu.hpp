@@ -491,6 +491,56 @@ public:
         return ids;
     }
 
+    // ---- Loop closure (LaserMapping::loop_detect, laser_mapping.cpp:1223-1349): STDescManager's
+    // database on the device.  GenerateSTDescs stays on the host; its products are staged once. ----
+    struct LoopResult {
+        int frame = -1;          // loop_result.first
+        double score = 0.0;      // loop_result.second
+        double rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // loop_transform.second, row-major
+        double t[3] = {0, 0, 0};                      // loop_transform.first
+        std::vector<livo_std_pair> pairs;             // loop_std_pair, as indices (staged, stored)
+        int n_candidates = 0;
+    };
+
+    // STDescManager(config): an empty database (read_parameters' defaults where config is null)
+    void StdReset(int64_t max_descs, int64_t max_frames, int64_t max_planes, const livo_std_params* config = nullptr) {
+        livo_std_params p;
+        check(livo_std_params_default(&p), "livo_std_params_default");
+        check(livo_std_reset(ctx_, config ? config : &p, max_descs, max_frames, max_planes), "livo_std_reset");
+    }
+    // the hand-off of GenerateSTDescs(cloud, stds_vec): the key frame's descriptors and plane cloud
+    void StdStage(const std::vector<livo_std_desc>& stds_vec, const std::vector<livo_std_plane>& plane_cloud) {
+        check(livo_std_stage(ctx_, stds_vec.data(), (int64_t)stds_vec.size(), plane_cloud.data(),
+                             (int64_t)plane_cloud.size()),
+              "livo_std_stage");
+        staged_descs_ = (int64_t)stds_vec.size();
+    }
+    // std_manager->SearchLoop(stds_vec, loop_result, loop_transform, loop_std_pair) on the staged frame
+    LoopResult SearchLoop() {
+        LoopResult out;
+        livo_std_result r{};
+        int64_t n = 0;
+        out.pairs.resize((size_t)(staged_descs_ * 27));
+        check(livo_std_search(ctx_, &r, out.pairs.data(), (int64_t)out.pairs.size(), &n), "livo_std_search");
+        if (n > (int64_t)out.pairs.size()) {  // (a cell's run may hold several matches of one descriptor)
+            out.pairs.resize((size_t)n);
+            check(livo_std_search(ctx_, &r, out.pairs.data(), n, &n), "livo_std_search");
+        }
+        out.pairs.resize((size_t)n);
+        out.frame = r.frame;
+        out.score = r.score;
+        for (int i = 0; i < 9; i++) out.rot[i] = r.rot[i];
+        for (int i = 0; i < 3; i++) out.t[i] = r.t[i];
+        out.n_candidates = r.n_candidates;
+        return out;
+    }
+    // std_manager->AddSTDescs(stds_vec) of the staged frame -> its frame index
+    int32_t AddSTDescs() {
+        int32_t frame = -1;
+        check(livo_std_commit(ctx_, &frame), "livo_std_commit");
+        return frame;
+    }
+
     livo_ctx* ctx() const { return ctx_; }
     const livo_params& params() const { return params_; }
 
@@ -535,6 +585,7 @@ private:
     livo_params params_{};
     int32_t scan_id_ = -1;
     bool ivox_ = false;
+    int64_t staged_descs_ = 0;
 };
 
 }  // namespace livo

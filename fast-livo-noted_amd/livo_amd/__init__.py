@@ -336,6 +336,67 @@ def ingest_params(**kw) -> IngestParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+STD_MAX_FRAMES = 20000    # LIVO_STD_MAX_FRAMES
+STD_MAX_CANDIDATES = 64   # LIVO_STD_MAX_CANDIDATES
+
+
+class StdParams(C.Structure):
+    _fields_ = [("skip_near_num", C.c_int32), ("candidate_num", C.c_int32), ("rough_dis_threshold", C.c_double),
+                ("vertex_diff_threshold", C.c_double), ("icp_threshold", C.c_double), ("normal_threshold", C.c_double),
+                ("dis_threshold", C.c_double)]
+
+
+class StdDesc(C.Structure):
+    _fields_ = [("side_length", C.c_double * 3), ("vertex_A", C.c_double * 3), ("vertex_B", C.c_double * 3),
+                ("vertex_C", C.c_double * 3), ("center", C.c_double * 3), ("vertex_attached", C.c_double * 3),
+                ("frame_id", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class StdPlane(C.Structure):
+    _fields_ = [("xyz", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class StdPair(C.Structure):
+    _fields_ = [("src", C.c_int32), ("frame", C.c_int32), ("db_index", C.c_int32)]
+
+
+class StdResult(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("n_candidates", C.c_int32), ("n_pairs", C.c_int32), ("candidate", C.c_int32),
+                ("score", C.c_double), ("rot", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class StdCandidate(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("votes", C.c_int32), ("use_size", C.c_int32), ("max_vote", C.c_int32),
+                ("max_vote_index", C.c_int32), ("pad", C.c_int32), ("score", C.c_double), ("rot", C.c_double * 9),
+                ("t", C.c_double * 3)]
+
+
+class StdInfo(C.Structure):
+    _fields_ = [("frames", C.c_int64), ("descs", C.c_int64), ("planes", C.c_int64), ("cells", C.c_int64),
+                ("max_descs", C.c_int64), ("max_frames", C.c_int64), ("max_planes", C.c_int64),
+                ("staged_descs", C.c_int64), ("staged_planes", C.c_int64)]
+
+
+STD_DESC_DTYPE = np.dtype([("side_length", np.float64, (3,)), ("vertex_A", np.float64, (3,)),
+                           ("vertex_B", np.float64, (3,)), ("vertex_C", np.float64, (3,)),
+                           ("center", np.float64, (3,)), ("vertex_attached", np.float64, (3,)),
+                           ("frame_id", np.uint32), ("pad", np.uint32)])
+STD_PLANE_DTYPE = np.dtype([("xyz", np.float32, (3,)), ("normal", np.float32, (3,))])
+STD_PAIR_DTYPE = np.dtype([("src", np.int32), ("frame", np.int32), ("db_index", np.int32)])
+STD_CANDIDATE_DTYPE = np.dtype([("frame", np.int32), ("votes", np.int32), ("use_size", np.int32),
+                                ("max_vote", np.int32), ("max_vote_index", np.int32), ("pad", np.int32),
+                                ("score", np.float64), ("rot", np.float64, (9,)), ("t", np.float64, (3,))])
+
+
+def std_params(**kw) -> StdParams:
+    """livo_std_params_default (read_parameters' defaults) with the given members replaced."""
+    p = StdParams()
+    _check("livo_std_params_default", load().livo_std_params_default(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 _IMU_PARAM_FIELDS = ("cov_acc", "cov_gyr", "cov_bias_gyr", "cov_bias_acc", "mean_acc")
 
 
@@ -484,6 +545,16 @@ SIGNATURES = {
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "livo_lio_frame": (C.c_int, [_P, C.POINTER(ImuJob), C.POINTER(ImuParams), C.POINTER(ImuCarry), C.c_double,
                                  C.POINTER(LioParams), C.POINTER(State), C.POINTER(State), C.POINTER(LioStats)]),
+    "livo_std_params_default": (C.c_int, [C.POINTER(StdParams)]),
+    "livo_std_reset": (C.c_int, [_P, C.POINTER(StdParams), C.c_int64, C.c_int64, C.c_int64]),
+    "livo_std_stage": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64]),
+    "livo_std_search": (C.c_int, [_P, C.POINTER(StdResult), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "livo_std_commit": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "livo_std_candidates": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "livo_std_matches": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "livo_std_info_get": (C.c_int, [_P, C.POINTER(StdInfo)]),
+    "livo_std_dump": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _P, C.c_int64,
+                                C.POINTER(C.c_int64)]),
     "livo_sync": (C.c_int, [_P]),
 }
 
@@ -1337,6 +1408,74 @@ class Context:
             _check("livo_vmap_release_frames", self._L.livo_vmap_release_frames(self.h, _ptr(ids), len(ids),
                                                                                 C.byref(n)))
         return ids[:n.value]
+
+    def std_reset(self, params: StdParams | None = None, max_descs: int = 1 << 16, max_frames: int = 1024,
+                  max_planes: int = 1 << 18):
+        """An empty loop-search database (livo_std_reset)."""
+        _check("livo_std_reset", self._L.livo_std_reset(self.h, C.byref(params or std_params()), max_descs,
+                                                        max_frames, max_planes))
+
+    def std_stage(self, descs: np.ndarray, planes: np.ndarray):
+        """The current key frame: descriptors (STD_DESC_DTYPE) and plane cloud (STD_PLANE_DTYPE), uploaded once."""
+        descs = np.ascontiguousarray(descs, STD_DESC_DTYPE)
+        planes = np.ascontiguousarray(planes, STD_PLANE_DTYPE)
+        _check("livo_std_stage", self._L.livo_std_stage(self.h, _ptr(descs) if descs.size else None, descs.size,
+                                                        _ptr(planes) if planes.size else None, planes.size))
+
+    def std_search(self, pair_cap: int | None = None) -> dict:
+        """SearchLoop of the staged frame -> frame (-1: none), score, rot (3, 3), t, n_candidates, candidate,
+        pairs (STD_PAIR_DTYPE, the winner's success list)."""
+        r = StdResult()
+        n = C.c_int64()
+        cap = self.std_info()["staged_descs"] * 27 if pair_cap is None else pair_cap
+        pairs = np.zeros(max(cap, 0), STD_PAIR_DTYPE)
+        _check("livo_std_search", self._L.livo_std_search(self.h, C.byref(r), _ptr(pairs) if cap > 0 else None, cap,
+                                                          C.byref(n)))
+        if n.value > cap:  # (a cell's run may hold several matches of one source)
+            return self.std_search(int(n.value))
+        return {"frame": r.frame, "score": r.score, "rot": np.array(r.rot[:], np.float64).reshape(3, 3),
+                "t": np.array(r.t[:], np.float64), "n_candidates": r.n_candidates, "candidate": r.candidate,
+                "n_pairs": r.n_pairs, "pairs": pairs[:n.value].copy()}
+
+    def std_commit(self) -> int:
+        """AddSTDescs of the staged frame -> its frame index."""
+        f = C.c_int32()
+        _check("livo_std_commit", self._L.livo_std_commit(self.h, C.byref(f)))
+        return f.value
+
+    def std_candidates(self) -> np.ndarray:
+        """The last search's candidates in candidate order (STD_CANDIDATE_DTYPE)."""
+        n = C.c_int64()
+        _check("livo_std_candidates", self._L.livo_std_candidates(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, STD_CANDIDATE_DTYPE)
+        if n.value:
+            _check("livo_std_candidates", self._L.livo_std_candidates(self.h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def std_matches(self, candidate: int) -> np.ndarray:
+        """One candidate's match list in the selector's order (STD_PAIR_DTYPE)."""
+        n = C.c_int64()
+        _check("livo_std_matches", self._L.livo_std_matches(self.h, candidate, None, 0, C.byref(n)))
+        out = np.zeros(n.value, STD_PAIR_DTYPE)
+        if n.value:
+            _check("livo_std_matches", self._L.livo_std_matches(self.h, candidate, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def std_info(self) -> dict:
+        info = StdInfo()
+        _check("livo_std_info_get", self._L.livo_std_info_get(self.h, C.byref(info)))
+        return _stats_dict(info)
+
+    def std_dump(self, frame: int = -1):
+        """-> the stored descriptors in insertion order, and the plane cloud of `frame` (empty for -1)."""
+        nd, npl = C.c_int64(), C.c_int64()
+        _check("livo_std_dump", self._L.livo_std_dump(self.h, None, 0, C.byref(nd), frame, None, 0, C.byref(npl)))
+        descs = np.zeros(nd.value, STD_DESC_DTYPE)
+        planes = np.zeros(npl.value if frame >= 0 else 0, STD_PLANE_DTYPE)
+        _check("livo_std_dump", self._L.livo_std_dump(self.h, _ptr(descs) if descs.size else None, descs.size,
+                                                      C.byref(nd), frame, _ptr(planes) if planes.size else None,
+                                                      planes.size, C.byref(npl)))
+        return descs, planes
 
     def scan_inherit_neighbors(self, dst: int, src: int):
         _check("livo_scan_inherit_neighbors", self._L.livo_scan_inherit_neighbors(self.h, dst, src))

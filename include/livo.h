@@ -34,6 +34,8 @@
  *   livo_vmap_*         ← feat_map, imgs_ and the features' T_f_w_ (the resident visual map)
  *   livo_vio_match      ← LidarSelector::addFromSparseMap (the visual map matched into a frame)
  *                                                   src/lidar_selection.cpp:117-221
+ *   livo_std_*          ← STDescManager::SearchLoop / AddSTDescs (the loop search)
+ *                                                   include/STD/STDesc.cpp:299-374, 960-1280
  *
  * Conventions
  *   - plain pointers and sizes only; no C++ or torch types cross the ABI;
@@ -62,6 +64,7 @@ extern "C" {
  *    livo_cloud_publish, livo_cloud_info_get and the two LIVO_CLOUD_* ids added the same way.
  *    livo_imu_* (params, init, propagate, propagate_batch) and livo_scan_preprocess_imu too.
  *    livo_ingest_params_default, livo_frame_ingest_livox / _cloud, livo_frame_info / _dump / _take too.
+ *    livo_std_* (the loop search) too.
  * 8: livo_vio_select added (nothing else changed).
  * 7: livo_cloud_colorize added (nothing else changed).
  * 5: livo_ivox_info grew add_passes (round 4).
@@ -1085,6 +1088,96 @@ typedef struct livo_lio_stats {
 int livo_lio_frame(livo_ctx* ctx, const livo_imu_job* job, const livo_imu_params* imu, livo_imu_carry* carry,
                    double offset_limit_ms, const livo_lio_params* p, livo_state* state, livo_state* state_propagat,
                    livo_lio_stats* stats);
+
+/* ------------------------------------------------------------------------
+ * Loop search: the resident Stable Triangle Descriptor database (include/STD/STDesc.cpp)
+ *   STDescManager::AddSTDescs            :355-374
+ *   STDescManager::SearchLoop            :299-353
+ *     candidate_selector :960-1099, candidate_verify :1102-1192, triangle_solver :1194-1219,
+ *     plane_geometric_verify :1221-1280
+ * GenerateSTDescs stays on the host (its corner_extractor walks an unordered_map in iteration
+ * order); its products, the key frame's descriptors and plane cloud, are what livo_std_stage takes.
+ * ------------------------------------------------------------------------ */
+#define LIVO_STD_MAX_FRAMES 20000    /* MAX_FRAME_N (STDesc.h): the reference's vote array */
+#define LIVO_STD_MAX_CANDIDATES 64   /* candidate_num beyond it is refused (the reference's default: 50) */
+
+typedef struct livo_std_params {     /* read_parameters' defaults (:83-93), not STDesc.h's initialisers */
+    int32_t skip_near_num;           /* 50 */
+    int32_t candidate_num;           /* 50 */
+    double  rough_dis_threshold;     /* 0.01 */
+    double  vertex_diff_threshold;   /* 0.5 */
+    double  icp_threshold;           /* 0.5 */
+    double  normal_threshold;        /* 0.2 */
+    double  dis_threshold;           /* 0.5 */
+} livo_std_params;
+
+typedef struct livo_std_desc {       /* STDesc (STDesc.h), 152 B */
+    double   side_length[3], vertex_A[3], vertex_B[3], vertex_C[3], center[3], vertex_attached[3];
+    uint32_t frame_id;
+    uint32_t pad;
+} livo_std_desc;
+
+typedef struct livo_std_plane {      /* a plane cloud's point: x, y, z and normal_x, _y, _z */
+    float xyz[3], normal[3];
+} livo_std_plane;
+
+typedef struct livo_std_pair {
+    int32_t src;        /* index into the staged descriptors */
+    int32_t frame;      /* the stored descriptor's frame */
+    int32_t db_index;   /* ... and its insertion index in the database (livo_std_dump's order) */
+} livo_std_pair;
+
+typedef struct livo_std_result {     /* loop_result, loop_transform and loop_std_pair's size */
+    int32_t frame;                   /* -1: no loop */
+    int32_t n_candidates;
+    int32_t n_pairs;
+    int32_t candidate;               /* the winner's index in livo_std_candidates, -1 with no loop */
+    double  score;                   /* 0 with no loop */
+    double  rot[9];                  /* row-major; identity with no loop (laser_mapping.cpp:1255-1256) */
+    double  t[3];
+} livo_std_result;
+
+typedef struct livo_std_candidate {  /* one STDMatchList and what candidate_verify made of it */
+    int32_t frame, votes;            /* votes = the match list's length */
+    int32_t use_size, max_vote, max_vote_index, pad;
+    double  score;                   /* -1 with max_vote < 4; NaN with an empty source plane cloud */
+    double  rot[9], t[3];            /* identity / zero with max_vote < 4 */
+} livo_std_candidate;
+
+typedef struct livo_std_info {
+    int64_t frames, descs, planes, cells;
+    int64_t max_descs, max_frames, max_planes;
+    int64_t staged_descs, staged_planes;  /* -1: nothing staged */
+} livo_std_info;
+
+int livo_std_params_default(livo_std_params* p);
+/* An empty database for up to max_descs descriptors, max_frames key frames and max_planes plane
+ * points, with the search's parameters.  LIVO_E_INVALID: a NULL argument, a non-finite or negative
+ * threshold, skip_near_num < 0, candidate_num outside [0, LIVO_STD_MAX_CANDIDATES], a capacity < 1
+ * (all found before the context is read); LIVO_E_RANGE: max_frames > LIVO_STD_MAX_FRAMES, max_descs
+ * or max_planes > 2^31 - 1 - 1024. */
+int livo_std_reset(livo_ctx* ctx, const livo_std_params* params, int64_t max_descs, int64_t max_frames,
+                   int64_t max_planes);
+/* The current key frame, GenerateSTDescs' products, uploaded once; it stays resident until the next
+ * stage or reset (a commit keeps it staged).  LIVO_E_INVALID: NULL with a count > 0, a negative count,
+ * a non-finite descriptor or plane, no reset; LIVO_E_RANGE: a |side_length| >= 2^20 - 2. */
+int livo_std_stage(livo_ctx* ctx, const livo_std_desc* descs, int64_t n, const livo_std_plane* planes, int64_t m);
+/* SearchLoop of the staged frame against the committed ones.  pairs (may be NULL) receives the
+ * winner's success list in match-list order, up to cap entries; *n_pairs (may be NULL) its length.
+ * LIVO_E_INVALID: ctx or out NULL, cap < 0, no reset, nothing staged. */
+int livo_std_search(livo_ctx* ctx, livo_std_result* out, livo_std_pair* pairs, int64_t cap, int64_t* n_pairs);
+/* AddSTDescs of the staged frame, and its plane cloud as plane_cloud_vec_[*frame].  LIVO_E_INVALID:
+ * no reset, nothing staged, a staged frame_id that is not the new frame's index; LIVO_E_CAPACITY: the
+ * frame does not fit (nothing is added).  frame may be NULL. */
+int livo_std_commit(livo_ctx* ctx, int32_t* frame);
+/* The last search's candidates in candidate order, and one candidate's match list. */
+int livo_std_candidates(livo_ctx* ctx, livo_std_candidate* out, int64_t cap, int64_t* n);
+int livo_std_matches(livo_ctx* ctx, int32_t candidate, livo_std_pair* pairs, int64_t cap, int64_t* n);
+int livo_std_info_get(livo_ctx* ctx, livo_std_info* info);
+/* The stored descriptors in insertion order (descs NULL: the count only) and the plane cloud of
+ * `frame` (frame < 0 or planes NULL with n_planes NULL: skipped).  LIVO_E_RANGE: a cap too small. */
+int livo_std_dump(livo_ctx* ctx, livo_std_desc* descs, int64_t desc_cap, int64_t* n_descs, int32_t frame,
+                  livo_std_plane* planes, int64_t plane_cap, int64_t* n_planes);
 
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
