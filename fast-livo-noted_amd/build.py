@@ -39,6 +39,7 @@ SOURCES = [
     ("vmap_kernels.hip", True),
     ("ikd_incr_kernels.hip", True),
     ("std_kernels.hip", True),
+    ("std_gen_kernels.hip", True),
     ("prims.hip", True),
     ("livo_capi.cpp", False),
     ("map_build.cpp", False),

@@ -450,6 +450,18 @@ struct StdDev {
     std::vector<uint32_t> coff;
 };
 
+// GenerateSTDescs (livo_std_key_*, livo_std_generate): the key cloud and the stages' arrays, one
+// grow-only allocation per stage (points, voxels, jobs, corners, candidates).
+struct StdGenDev {
+    float* key = nullptr;              // the key cloud, x y z
+    size_t key_bytes = 0;
+    int64_t n_key = 0;
+    void* buf[5] = {};
+    size_t bytes[5] = {};
+    StdGen last{};                     // the last generate's arrays (livo_std_gen_debug, livo_std_staged's corners)
+    bool have = false;                 // the staged frame is that generate's
+};
+
 struct livo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -517,6 +529,7 @@ struct livo_ctx {
     ImuDev imu;                        // livo_imu_propagate(_batch): stream, staging, the resident Pose6D table
     IngestDev ing;                     // livo_frame_ingest_*: the current frame and its cursor
     StdDev stdb;                       // livo_std_*: the loop search's database, staged frame and last search
+    StdGenDev sgen;                    // livo_std_key_*, livo_std_generate
     void* vio_buf = nullptr;           // VIO frame (image, points, partials, slot)
     size_t vio_bytes = 0;
     DevImage bgr_img;                  // livo_cloud_colorize: the last uploaded BGR image (reused by bgr == NULL)
@@ -2160,6 +2173,9 @@ int livo_ctx_destroy(livo_ctx* c) {
     if (c->stdb.buf) (void)hipFree(c->stdb.buf);
     if (c->stdb.stage) (void)hipFree(c->stdb.stage);
     if (c->stdb.mbuf) (void)hipFree(c->stdb.mbuf);
+    if (c->sgen.key) (void)hipFree(c->sgen.key);
+    for (void* b : c->sgen.buf)
+        if (b) (void)hipFree(b);
     if (c->imu.st) (void)hipStreamSynchronize(c->imu.st);
     if (c->imu.buf) (void)hipFree(c->imu.buf);
     if (c->imu.table) (void)hipFree(c->imu.table);
@@ -6134,6 +6150,28 @@ int livo_std_reset(livo_ctx* c, const livo_std_params* p, int64_t max_descs, int
     return LIVO_OK;
 }
 
+// The staged frame's buffers for n descriptors and m planes (livo_std_stage, livo_std_generate).
+static int std_stage_layout(livo_ctx* c, int64_t n, int64_t m) {
+    StdDev& D = c->stdb;
+    const size_t nn = (size_t)std::max<int64_t>(n, 1), mm = (size_t)std::max<int64_t>(m, 1);
+    auto layout = [&](Carve k) {
+        D.src = k.take<livo_std_desc>(nn);
+        D.src_planes = k.take<livo_std_plane>(mm);
+        D.nkey = k.take<unsigned long long>(nn);
+        D.snkey = k.take<unsigned long long>(nn);
+        D.nseq = k.take<uint32_t>(nn);
+        D.snseq = k.take<uint32_t>(nn);
+        D.P.cnt = k.take<uint32_t>(nn);
+        D.P.off = k.take<uint32_t>(nn);
+        return k.total();
+    };
+    const size_t need = layout(Carve{nullptr});
+    if (need > D.stage_bytes) HIP_TRY(stream_wait(c->stream));  // (a commit may still read the frame it replaces)
+    RC_TRY(ensure_dev_bytes(&D.stage, &D.stage_bytes, need));
+    layout(Carve{(char*)D.stage});
+    return LIVO_OK;
+}
+
 int livo_std_stage(livo_ctx* c, const livo_std_desc* descs, int64_t n, const livo_std_plane* planes, int64_t m) {
     if (!c || n < 0 || m < 0 || (n > 0 && !descs) || (m > 0 && !planes)) return LIVO_E_INVALID;
     if (n > kStdMaxCount || m > kStdMaxCount) return LIVO_E_RANGE;
@@ -6155,22 +6193,7 @@ int livo_std_stage(livo_ctx* c, const livo_std_desc* descs, int64_t n, const liv
     if (!D.ready) return LIVO_E_INVALID;
     if (set_device(c)) return LIVO_E_HIP;
     D.staged = D.searched = false;
-    const size_t nn = (size_t)std::max<int64_t>(n, 1), mm = (size_t)std::max<int64_t>(m, 1);
-    auto layout = [&](Carve k) {
-        D.src = k.take<livo_std_desc>(nn);
-        D.src_planes = k.take<livo_std_plane>(mm);
-        D.nkey = k.take<unsigned long long>(nn);
-        D.snkey = k.take<unsigned long long>(nn);
-        D.nseq = k.take<uint32_t>(nn);
-        D.snseq = k.take<uint32_t>(nn);
-        D.P.cnt = k.take<uint32_t>(nn);
-        D.P.off = k.take<uint32_t>(nn);
-        return k.total();
-    };
-    const size_t need = layout(Carve{nullptr});
-    if (need > D.stage_bytes) HIP_TRY(stream_wait(c->stream));  // (a commit may still read the frame it replaces)
-    RC_TRY(ensure_dev_bytes(&D.stage, &D.stage_bytes, need));
-    layout(Carve{(char*)D.stage});
+    RC_TRY(std_stage_layout(c, n, m));
     if (n > 0) HIP_TRY(hipMemcpyAsync(D.src, descs, (size_t)n * sizeof(livo_std_desc), hipMemcpyHostToDevice, c->stream));
     if (m > 0)
         HIP_TRY(hipMemcpyAsync(D.src_planes, planes, (size_t)m * sizeof(livo_std_plane), hipMemcpyHostToDevice, c->stream));
@@ -6180,6 +6203,7 @@ int livo_std_stage(livo_ctx* c, const livo_std_desc* descs, int64_t n, const liv
     D.id_min = id_min;
     D.id_max = id_max;
     D.staged = true;
+    c->sgen.have = false;
     return LIVO_OK;
 }
 
@@ -6400,6 +6424,399 @@ int livo_std_dump(livo_ctx* c, livo_std_desc* descs, int64_t desc_cap, int64_t* 
             HIP_TRY(stream_wait(c->stream));
         }
     }
+    return LIVO_OK;
+}
+
+// ---- GenerateSTDescs on the device (include/STD/STDesc.cpp:264-297, :376-958, :1367-1415) ----
+int livo_std_gen_params_default(livo_std_gen_params* p) {
+    if (!p) return LIVO_E_INVALID;
+    std::memset(p, 0, sizeof(*p));
+    p->voxel_size = 2.0;  // read_parameters, STDesc.cpp:57-81
+    p->voxel_init_num = 10;
+    p->plane_detection_thre = 0.01;
+    p->plane_merge_normal_thre = 0.1;
+    p->proj_image_resolution = 0.5;
+    p->proj_dis_min = 0.0;
+    p->proj_dis_max = 2.0;
+    p->corner_thre = 10.0;
+    p->maximum_corner_num = 100;
+    p->non_max_suppression_radius = 2.0;
+    p->descriptor_near_num = 10;
+    p->descriptor_min_len = 2.0;
+    p->descriptor_max_len = 50.0;
+    p->std_side_resolution = 0.2;
+    return LIVO_OK;
+}
+
+// LIVO_OK, or the refusal of a parameter set (livo.h lists them).
+static int std_gen_params_check(const livo_std_gen_params* p) {
+    if (!p) return LIVO_E_INVALID;
+    const double t[11] = {p->voxel_size, p->plane_detection_thre, p->plane_merge_normal_thre, p->proj_image_resolution,
+                          p->proj_dis_min, p->proj_dis_max, p->corner_thre, p->non_max_suppression_radius,
+                          p->descriptor_min_len, p->descriptor_max_len, p->std_side_resolution};
+    for (double v : t)
+        if (!std::isfinite(v) || v < 0.0) return LIVO_E_INVALID;
+    if (!(p->voxel_size > 0.0) || !(p->proj_image_resolution > 0.0) || !(p->std_side_resolution > 0.0)) return LIVO_E_INVALID;
+    if (p->voxel_init_num < 0 || p->maximum_corner_num < 1) return LIVO_E_INVALID;
+    if (p->descriptor_near_num < 3 || p->descriptor_near_num > LIVO_STD_GEN_MAX_NEAR) return LIVO_E_INVALID;
+    const double reach = p->voxel_size * std::sqrt(17.0);
+    if (reach >= 10.0) return LIVO_E_RANGE;
+    if (2.0 * reach / p->proj_image_resolution + 5.0 > (double)LIVO_STD_GEN_MAX_IMAGE) return LIVO_E_RANGE;
+    if (p->descriptor_max_len * 1000.0 >= (double)((1 << 21) - 1)) return LIVO_E_RANGE;
+    if (p->descriptor_max_len / p->std_side_resolution >= (double)(kStdCellBias - 2)) return LIVO_E_RANGE;
+    return LIVO_OK;
+}
+
+// Room for n more points behind the key cloud's; a larger allocation takes the old points over.
+static int std_key_room(livo_ctx* c, int64_t n) {
+    StdGenDev& G = c->sgen;
+    if (G.n_key + n > kStdMaxCount) return LIVO_E_RANGE;
+    const size_t need = (size_t)(G.n_key + n) * 3 * sizeof(float);
+    if (need <= G.key_bytes) return LIVO_OK;
+    const size_t want = std::max(need, G.key_bytes * 2);
+    float* fresh = nullptr;
+    if (hipMalloc((void**)&fresh, want) != hipSuccess) return LIVO_E_OOM;
+    hipError_t e = hipSuccess;
+    if (G.n_key > 0)
+        e = hipMemcpyAsync(fresh, G.key, (size_t)G.n_key * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = stream_wait(c->stream);  // (a generate may still read the old points)
+    if (e != hipSuccess) {
+        (void)hipFree(fresh);
+        return LIVO_E_HIP;
+    }
+    if (G.key) (void)hipFree(G.key);
+    G.key = fresh;
+    G.key_bytes = want;
+    return LIVO_OK;
+}
+
+int livo_std_key_add(livo_ctx* c, int32_t scan_id) {
+    if (!c) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    CloudSrc S;
+    RC_TRY(frame_cloud(c, scan_id, &S));
+    if (S.n <= 0) return LIVO_OK;
+    if (set_device(c)) return LIVO_E_HIP;
+    RC_TRY(std_key_room(c, S.n));
+    StdGenDev& G = c->sgen;
+    RC_TRY(launch_std_gen_append(S.src, S.n, S.stride, G.key + G.n_key * 3, c->stream));
+    G.n_key += S.n;
+    return LIVO_OK;
+}
+
+int livo_std_key_add_host(livo_ctx* c, const float* xyz, int64_t n, int64_t stride_bytes) {
+    if (!c || n < 0 || (n > 0 && !xyz) || stride_bytes < 12 || stride_bytes % 4 != 0) return LIVO_E_INVALID;
+    const int64_t stride = stride_bytes / 4;
+    for (int64_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(xyz[i * stride + k])) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    if (n == 0) return LIVO_OK;
+    if (set_device(c)) return LIVO_E_HIP;
+    RC_TRY(std_key_room(c, n));
+    StdGenDev& G = c->sgen;
+    float* dst = G.key + G.n_key * 3;
+    if (stride == 3) {
+        HIP_TRY(hipMemcpyAsync(dst, xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    } else {
+        HIP_TRY(hipMemcpy2DAsync(dst, 12, xyz, (size_t)stride_bytes, 12, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(stream_wait(c->stream));  // host pointers are read before return
+    G.n_key += n;
+    return LIVO_OK;
+}
+
+int livo_std_key_clear(livo_ctx* c) {
+    if (!c) return LIVO_E_INVALID;
+    c->sgen.n_key = 0;
+    return LIVO_OK;
+}
+
+int livo_std_key_count(livo_ctx* c, int64_t* n) {
+    if (!c || !n) return LIVO_E_INVALID;
+    *n = c->sgen.n_key;
+    return LIVO_OK;
+}
+
+int livo_std_generate(livo_ctx* c, const livo_std_gen_params* p, livo_std_gen_stats* stats) {
+    if (!c) return LIVO_E_INVALID;
+    RC_TRY(std_gen_params_check(p));
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    StdGenDev& G = c->sgen;
+    if (!D.ready) return LIVO_E_INVALID;
+    if (set_device(c)) return LIVO_E_HIP;
+    hipStream_t st = c->stream;
+    livo_std_gen_stats S{};
+    StdGen g{};
+    g.prm = *p;
+    g.frame_id = (uint32_t)D.n_frames;
+    g.pts = G.key;
+    g.n = G.n_key;
+    S.points = g.n;
+    const double reach = p->voxel_size * std::sqrt(17.0);
+    const int seg_side = (int)(2.0 * reach / (5.0 * p->proj_image_resolution) + 1.0);
+    g.seg_max = seg_side * seg_side;  // (<= 256: the image side is at most LIVO_STD_GEN_MAX_IMAGE)
+    auto grow = [&](int which, size_t need) -> int {
+        if (need > G.bytes[which]) HIP_TRY(stream_wait(st));
+        return ensure_dev_bytes(&G.buf[which], &G.bytes[which], need);
+    };
+    // 1. voxel keys, the stable sort by (key, input index), the voxels' runs
+    {
+        const size_t n = (size_t)std::max<int64_t>(g.n, 1);
+        auto layout = [&](Carve k) {
+            g.ctr = k.take<unsigned>(kGenCtrN);
+            g.pkey = k.take<unsigned long long>(n);
+            g.skey = k.take<unsigned long long>(n);
+            g.piota = k.take<uint32_t>(n);
+            g.sidx = k.take<uint32_t>(n);
+            g.spts = k.take<float>(n * 3);
+            g.head = k.take<uint32_t>(n);
+            g.hpos = k.take<uint32_t>(n);
+            return k.total();
+        };
+        G.have = false;  // (the last generate's corner list lies in the arrays this one writes)
+        RC_TRY(grow(0, layout(Carve{nullptr})));
+        layout(Carve{(char*)G.buf[0]});
+    }
+    HIP_TRY(hipMemsetAsync(g.ctr, 0, kGenCtrN * sizeof(unsigned), st));
+    ScanCount heads, planes, jobs, corners, alive, survivors;
+    if (g.n > 0) {
+        RC_TRY(launch_std_gen_keys(g, st));
+        RC_TRY(sort_u64(c, g.pkey, g.skey, g.piota, g.sidx, g.n));
+        RC_TRY(launch_std_gen_heads(g, st));
+        RC_TRY(scan_u32(c, g.head, g.hpos, g.n));
+        RC_TRY(heads.read(g.hpos, g.head, g.n, st));
+        unsigned err = 0;
+        HIP_TRY(hipMemcpyAsync(&err, g.ctr + kGenCtrErr, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(stream_wait(st));
+        if (err & 1u) return LIVO_E_INVALID;
+        if (err & 2u) return LIVO_E_RANGE;
+        g.nv = heads.sum();
+    }
+    S.voxels = g.nv;
+    // 2.-4. planes, connections and the jobs' counts, per voxel
+    if (g.nv > 0) {
+        const size_t nv = (size_t)g.nv;
+        auto layout = [&](Carve k) {
+            g.vkey = k.take<unsigned long long>(nv);
+            g.vstart = k.take<uint32_t>(nv + 1);
+            g.vfirst = k.take<uint32_t>(nv);
+            g.viota = k.take<uint32_t>(nv);
+            g.ofirst = k.take<uint32_t>(nv);
+            g.order = k.take<uint32_t>(nv);
+            g.rank = k.take<uint32_t>(nv);
+            g.vplane = k.take<uint32_t>(nv);
+            g.vnorm = k.take<double>(nv * 3);
+            g.vcen = k.take<double>(nv * 3);
+            g.pflag = k.take<uint32_t>(nv);
+            g.ppos = k.take<uint32_t>(nv);
+            g.conn = k.take<uint32_t>(nv);
+            g.cidx = k.take<uint32_t>(nv * 6);
+            g.jcnt = k.take<uint32_t>(nv);
+            g.jpos = k.take<uint32_t>(nv);
+            return k.total();
+        };
+        RC_TRY(grow(1, layout(Carve{nullptr})));
+        layout(Carve{(char*)G.buf[1]});
+        RC_TRY(launch_std_gen_voxels(g, st));
+        RC_TRY(sort_u32(c, g.vfirst, g.ofirst, g.viota, g.order, g.nv, 32));  // pin 1: the order of first appearance
+        RC_TRY(launch_std_gen_planes(g, st));
+        RC_TRY(scan_u32(c, g.pflag, g.ppos, g.nv));
+        RC_TRY(scan_u32(c, g.jcnt, g.jpos, g.nv));
+        RC_TRY(planes.read(g.ppos, g.pflag, g.nv, st));
+        RC_TRY(jobs.read(g.jpos, g.jcnt, g.nv, st));
+        HIP_TRY(stream_wait(st));
+        S.plane_voxels = planes.sum();
+        g.nj = jobs.sum();
+    }
+    S.jobs = g.nj;
+    // 5. the jobs, their members and corners
+    if (g.nj > 0) {
+        const size_t nj = (size_t)g.nj;
+        auto layout = [&](Carve k) {
+            g.job_v = k.take<uint32_t>(nj);
+            g.job_c = k.take<uint32_t>(nj);
+            g.jslot = k.take<uint32_t>(nj * 27);
+            g.jpts = k.take<uint32_t>(nj);
+            g.ccnt = k.take<uint32_t>(nj);
+            g.cpos = k.take<uint32_t>(nj);
+            g.cbuf = k.take<livo_std_corner>(nj * (size_t)g.seg_max);
+            return k.total();
+        };
+        RC_TRY(grow(2, layout(Carve{nullptr})));
+        layout(Carve{(char*)G.buf[2]});
+        HIP_TRY(hipMemsetAsync(g.jslot, 0, nj * 27 * 4, st));
+        RC_TRY(launch_std_gen_jobs(g, st));
+        RC_TRY(scan_u32(c, g.ccnt, g.cpos, g.nj));
+        RC_TRY(corners.read(g.cpos, g.ccnt, g.nj, st));
+        unsigned err = 0;
+        HIP_TRY(hipMemcpyAsync(&err, g.ctr + kGenCtrErr, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(stream_wait(st));
+        if (err & 4u) return LIVO_E_RANGE;  // (not reachable: the parameter check bounds the image)
+        g.m = corners.sum();
+    }
+    S.corners_raw = g.m;
+    // 6. suppression and the cut
+    int64_t n_sup = 0;
+    if (g.m > 0) {
+        const size_t m = (size_t)g.m;
+        auto layout = [&](Carve k) {
+            g.call = k.take<livo_std_corner>(m);
+            g.csup = k.take<livo_std_corner>(m);
+            g.cfin = k.take<livo_std_corner>(m);
+            g.alive = k.take<uint32_t>(m);
+            g.apos = k.take<uint32_t>(m);
+            g.cutkey = k.take<uint32_t>(m);
+            g.cutval = k.take<uint32_t>(m);
+            g.scutkey = k.take<uint32_t>(m);
+            g.scutval = k.take<uint32_t>(m);
+            g.knn = k.take<uint32_t>(m * LIVO_STD_GEN_MAX_NEAR);
+            return k.total();
+        };
+        RC_TRY(grow(3, layout(Carve{nullptr})));
+        layout(Carve{(char*)G.buf[3]});
+        RC_TRY(launch_std_gen_corners(g, st));
+        RC_TRY(scan_u32(c, g.alive, g.apos, g.m));
+        RC_TRY(alive.read(g.apos, g.alive, g.m, st));
+        RC_TRY(launch_std_gen_keep(g, st));
+        HIP_TRY(stream_wait(st));
+        n_sup = alive.sum();
+        if ((int64_t)p->maximum_corner_num > n_sup) {  // (:603: the suppressed list as it is)
+            g.k = n_sup;
+            g.cfin = g.csup;
+        } else {
+            g.k = p->maximum_corner_num;
+            RC_TRY(sort_u32(c, g.cutkey, g.scutkey, g.cutval, g.scutval, n_sup, 32));
+            RC_TRY(launch_std_gen_pick(g, st));
+        }
+    }
+    S.corners_suppressed = n_sup;
+    S.corners = g.k;
+    // 7. the triangles
+    int64_t n_descs = 0;
+    g.kf = (int32_t)std::min<int64_t>(p->descriptor_near_num, g.k);
+    g.pairs = (p->descriptor_near_num - 1) * (p->descriptor_near_num - 2) / 2;
+    if (g.kf >= 3) {
+        g.nc = g.k * g.pairs;
+        if (g.nc > kStdMaxCount) return LIVO_E_RANGE;
+        S.triangles_tried = g.k * ((int64_t)(g.kf - 1) * (g.kf - 2) / 2);
+        const size_t nc = (size_t)g.nc;
+        auto layout = [&](Carve k) {
+            g.ckey = k.take<unsigned long long>(nc);
+            g.sckey = k.take<unsigned long long>(nc);
+            g.cval = k.take<uint32_t>(nc);
+            g.scval = k.take<uint32_t>(nc);
+            g.surv = k.take<uint32_t>(nc);
+            g.spos = k.take<uint32_t>(nc);
+            return k.total();
+        };
+        RC_TRY(grow(4, layout(Carve{nullptr})));
+        layout(Carve{(char*)G.buf[4]});
+        RC_TRY(launch_std_gen_cands(g, st));
+        RC_TRY(sort_u64(c, g.ckey, g.sckey, g.cval, g.scval, g.nc));
+        RC_TRY(launch_std_gen_surv(g, st));
+        RC_TRY(scan_u32(c, g.surv, g.spos, g.nc));
+        RC_TRY(survivors.read(g.spos, g.surv, g.nc, st));
+        HIP_TRY(stream_wait(st));
+        n_descs = survivors.sum();
+    } else {
+        g.nc = 0;
+    }
+    S.descs = n_descs;
+    // the products become the staged frame
+    D.staged = D.searched = false;
+    G.have = false;
+    RC_TRY(std_stage_layout(c, n_descs, S.plane_voxels));
+    g.descs_out = D.src;
+    g.planes_out = D.src_planes;
+    if (S.plane_voxels > 0) RC_TRY(launch_std_gen_planes_out(g, st));
+    if (n_descs > 0) RC_TRY(launch_std_gen_emit(g, st));
+    D.n_src = n_descs;
+    D.n_src_planes = S.plane_voxels;
+    D.id_min = D.id_max = g.frame_id;
+    D.staged = true;
+    G.last = g;
+    G.have = true;
+    G.n_key = 0;  // laser_mapping.cpp:1249
+    if (stats) *stats = S;
+    return LIVO_OK;
+}
+
+int livo_std_staged(livo_ctx* c, livo_std_desc* descs, int64_t desc_cap, int64_t* n_descs, livo_std_plane* planes,
+                    int64_t plane_cap, int64_t* n_planes, livo_std_corner* corners, int64_t corner_cap,
+                    int64_t* n_corners) {
+    if (!c || desc_cap < 0 || plane_cap < 0 || corner_cap < 0) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    StdDev& D = c->stdb;
+    if (!D.ready || !D.staged) return LIVO_E_INVALID;
+    const StdGenDev& G = c->sgen;
+    const int64_t nk = G.have ? G.last.k : 0;
+    if (n_descs) *n_descs = D.n_src;
+    if (n_planes) *n_planes = D.n_src_planes;
+    if (n_corners) *n_corners = nk;
+    if ((descs && desc_cap < D.n_src) || (planes && plane_cap < D.n_src_planes) || (corners && corner_cap < nk))
+        return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    if (descs && D.n_src > 0)
+        HIP_TRY(hipMemcpyAsync(descs, D.src, (size_t)D.n_src * sizeof(livo_std_desc), hipMemcpyDeviceToHost, c->stream));
+    if (planes && D.n_src_planes > 0)
+        HIP_TRY(hipMemcpyAsync(planes, D.src_planes, (size_t)D.n_src_planes * sizeof(livo_std_plane), hipMemcpyDeviceToHost,
+                               c->stream));
+    if (corners && nk > 0)
+        HIP_TRY(hipMemcpyAsync(corners, G.last.cfin, (size_t)nk * sizeof(livo_std_corner), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(stream_wait(c->stream));
+    return LIVO_OK;
+}
+
+int livo_std_gen_debug(livo_ctx* c, int32_t* voxels, int64_t voxel_cap, int64_t* n_voxels, int32_t* jobs, int64_t job_cap,
+                       int64_t* n_jobs) {
+    if (!c || voxel_cap < 0 || job_cap < 0) return LIVO_E_INVALID;
+    if (hip_device_count() <= 0) return LIVO_E_HIP;
+    const StdGenDev& G = c->sgen;
+    if (!G.have) return LIVO_E_INVALID;
+    const StdGen& g = G.last;
+    if (n_voxels) *n_voxels = g.nv;
+    if (n_jobs) *n_jobs = g.nj;
+    if ((voxels && voxel_cap < g.nv) || (jobs && job_cap < g.nj)) return LIVO_E_RANGE;
+    if (set_device(c)) return LIVO_E_HIP;
+    const size_t nv = (size_t)g.nv, nj = (size_t)g.nj;
+    std::vector<uint32_t> order(nv), rank(nv), vstart(nv + 1), vfirst(nv), vplane(nv), job_v(nj), job_c(nj), jpts(nj),
+        jslot(nj * 27);
+    auto down = [&](std::vector<uint32_t>& h, const uint32_t* d) {
+        return h.empty() ? hipSuccess : hipMemcpyAsync(h.data(), d, h.size() * 4, hipMemcpyDeviceToHost, c->stream);
+    };
+    if (nv > 0) {
+        HIP_TRY(down(order, g.order));
+        HIP_TRY(down(rank, g.rank));
+        HIP_TRY(down(vstart, g.vstart));
+        HIP_TRY(down(vfirst, g.vfirst));
+        HIP_TRY(down(vplane, g.vplane));
+    }
+    if (nj > 0) {
+        HIP_TRY(down(job_v, g.job_v));
+        HIP_TRY(down(job_c, g.job_c));
+        HIP_TRY(down(jpts, g.jpts));
+        HIP_TRY(down(jslot, g.jslot));
+    }
+    HIP_TRY(stream_wait(c->stream));
+    if (voxels)
+        for (size_t r = 0; r < nv; r++) {
+            const uint32_t v = order[r];
+            voxels[r * 3] = (int32_t)vfirst[v];
+            voxels[r * 3 + 1] = (int32_t)(vstart[v + 1] - vstart[v]);
+            voxels[r * 3 + 2] = (int32_t)vplane[v];
+        }
+    if (jobs)
+        for (size_t j = 0; j < nj; j++) {
+            jobs[j * 30] = (int32_t)rank[job_v[j]];
+            jobs[j * 30 + 1] = (int32_t)rank[job_c[j]];
+            jobs[j * 30 + 2] = (int32_t)jpts[j];
+            for (int s = 0; s < 27; s++) {
+                const uint32_t w = jslot[j * 27 + s];
+                jobs[j * 30 + 3 + s] = w ? (int32_t)rank[w - 1] + 1 : 0;
+            }
+        }
     return LIVO_OK;
 }
 

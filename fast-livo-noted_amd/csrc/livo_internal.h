@@ -1113,4 +1113,63 @@ int launch_std_merge(const unsigned long long* okey, const uint32_t* oseq, int64
 int launch_std_count_cells(const unsigned long long* skey, int64_t n, unsigned* ctr, void* stream);
 int launch_std_unpack(const StdHot* hot, const StdVerts* verts, int64_t n, livo_std_desc* out, void* stream);
 
+// ---- GenerateSTDescs (std_gen_kernels.hip): the key cloud's voxels, planes, jobs, corners, triangles ----
+constexpr int kStdGenSide = LIVO_STD_GEN_MAX_IMAGE;
+constexpr int kStdGenCoordMax = kStdCellBias - 2;  // voxel coordinates are packed like the cells, 21 bits an axis
+constexpr int kStdGenSweeps = 10;                  // cyclic Jacobi sweeps of init_plane's eigen-solve
+constexpr int kStdGenReach = 27 * 6;               // the jobs that can reach one voxel
+enum { kGenCtrErr = 0, kGenCtrN = 4 };             // bit 0: a non-finite point, 1: a coordinate out of range, 2: an image limit
+struct StdGen {
+    livo_std_gen_params prm;
+    uint32_t frame_id;
+    unsigned* ctr;
+    // points: input order, and sorted by (voxel key, input index)
+    const float* pts;
+    int64_t n;
+    unsigned long long *pkey, *skey;
+    uint32_t *piota, *sidx;
+    float* spts;
+    uint32_t *head, *hpos;
+    // voxels, in key order (rank / order: to and from the visiting order)
+    int64_t nv;
+    unsigned long long* vkey;
+    uint32_t *vstart, *vfirst, *viota, *ofirst, *order, *rank;
+    uint32_t* vplane;
+    double *vnorm, *vcen;
+    uint32_t *pflag, *ppos;     // by rank: plane flags and their scan
+    livo_std_plane* planes_out;
+    uint32_t *conn, *cidx;      // connect_ (bits 0-5) and is_check_connect_ (8-13); the neighbours
+    uint32_t *jcnt, *jpos;      // by rank
+    // jobs
+    int64_t nj;
+    uint32_t *job_v, *job_c, *jslot, *jpts;
+    int32_t seg_max;            // corner slots a job
+    uint32_t *ccnt, *cpos;
+    livo_std_corner* cbuf;
+    // corners: of every job, suppressed, final
+    int64_t m, k;
+    int32_t kf, pairs;          // neighbours found, (m, n) pairs a corner
+    livo_std_corner *call, *csup, *cfin;
+    uint32_t *alive, *apos, *cutkey, *cutval, *scutkey, *scutval;
+    uint32_t* knn;
+    // candidates
+    int64_t nc;
+    unsigned long long *ckey, *sckey;
+    uint32_t *cval, *scval, *surv, *spos;
+    livo_std_desc* descs_out;
+};
+int launch_std_gen_append(const float* src, int64_t n, int stride, float* dst, void* stream);
+int launch_std_gen_keys(const StdGen& g, void* stream);
+int launch_std_gen_heads(const StdGen& g, void* stream);
+int launch_std_gen_voxels(const StdGen& g, void* stream);
+int launch_std_gen_planes(const StdGen& g, void* stream);
+int launch_std_gen_planes_out(const StdGen& g, void* stream);
+int launch_std_gen_jobs(const StdGen& g, void* stream);
+int launch_std_gen_corners(const StdGen& g, void* stream);
+int launch_std_gen_keep(const StdGen& g, void* stream);
+int launch_std_gen_pick(const StdGen& g, void* stream);
+int launch_std_gen_cands(const StdGen& g, void* stream);
+int launch_std_gen_surv(const StdGen& g, void* stream);
+int launch_std_gen_emit(const StdGen& g, void* stream);
+
 }  // namespace livo

@@ -492,7 +492,7 @@ public:
     }
 
     // ---- Loop closure (LaserMapping::loop_detect, laser_mapping.cpp:1223-1349): STDescManager's
-    // database on the device.  GenerateSTDescs stays on the host; its products are staged once. ----
+    // database on the device.  GenerateSTDescs runs there too (loop_detect); StdStage takes a host's products. ----
     struct LoopResult {
         int frame = -1;          // loop_result.first
         double score = 0.0;      // loop_result.second
@@ -541,6 +541,28 @@ public:
         return frame;
     }
 
+    // The loop detection of a LiDAR frame (laser_mapping.cpp:1239-1262): the frame's world cloud joins the key
+    // cloud; every sub_frame_num frames GenerateSTDescs runs on it, SearchLoop when more than skip_near_num key
+    // frames are stored, then AddSTDescs.  -> true when a key frame was made (out, may be null, holds its search).
+    bool loop_detect(int sub_frame_num, int skip_near_num, const livo_std_gen_params* config = nullptr,
+                     LoopResult* out = nullptr, livo_std_gen_stats* stats = nullptr) {
+        check(livo_std_key_add(ctx_, LIVO_CLOUD_WORLD), "livo_std_key_add");
+        if (++key_frames_pending_ < sub_frame_num) return false;
+        key_frames_pending_ = 0;
+        livo_std_gen_params p;
+        check(livo_std_gen_params_default(&p), "livo_std_gen_params_default");
+        livo_std_gen_stats st{};
+        check(livo_std_generate(ctx_, config ? config : &p, &st), "livo_std_generate");
+        staged_descs_ = st.descs;
+        if (stats) *stats = st;
+        LoopResult none;
+        livo_std_info info{};
+        check(livo_std_info_get(ctx_, &info), "livo_std_info_get");
+        if (out) *out = info.frames > skip_near_num ? SearchLoop() : none;
+        AddSTDescs();
+        return true;
+    }
+
     livo_ctx* ctx() const { return ctx_; }
     const livo_params& params() const { return params_; }
 
@@ -586,6 +608,7 @@ private:
     int32_t scan_id_ = -1;
     bool ivox_ = false;
     int64_t staged_descs_ = 0;
+    int key_frames_pending_ = 0;       // frames in the key cloud since the last key frame (loop_detect)
 };
 
 }  // namespace livo

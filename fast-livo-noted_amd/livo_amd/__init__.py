@@ -397,6 +397,41 @@ def std_params(**kw) -> StdParams:
     return p
 
 
+STD_GEN_MAX_IMAGE = 80    # LIVO_STD_GEN_MAX_IMAGE
+STD_GEN_MAX_NEAR = 64     # LIVO_STD_GEN_MAX_NEAR
+
+
+class StdGenParams(C.Structure):
+    _fields_ = [("voxel_size", C.c_double), ("plane_detection_thre", C.c_double), ("plane_merge_normal_thre", C.c_double),
+                ("proj_image_resolution", C.c_double), ("proj_dis_min", C.c_double), ("proj_dis_max", C.c_double),
+                ("corner_thre", C.c_double), ("non_max_suppression_radius", C.c_double),
+                ("descriptor_min_len", C.c_double), ("descriptor_max_len", C.c_double), ("std_side_resolution", C.c_double),
+                ("voxel_init_num", C.c_int32), ("maximum_corner_num", C.c_int32), ("descriptor_near_num", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class StdGenStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("points", "voxels", "plane_voxels", "jobs", "corners_raw", "corners_suppressed",
+                                         "corners", "triangles_tried", "descs")]
+
+
+class StdCorner(C.Structure):
+    _fields_ = [("xyz", C.c_float * 3), ("attached", C.c_float), ("normal", C.c_float * 3), ("pad", C.c_float)]
+
+
+STD_CORNER_DTYPE = np.dtype([("xyz", np.float32, (3,)), ("attached", np.float32), ("normal", np.float32, (3,)),
+                             ("pad", np.float32)])
+
+
+def std_gen_params(**kw) -> StdGenParams:
+    """livo_std_gen_params_default (read_parameters' defaults) with the given members replaced."""
+    p = StdGenParams()
+    _check("livo_std_gen_params_default", load().livo_std_gen_params_default(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 _IMU_PARAM_FIELDS = ("cov_acc", "cov_gyr", "cov_bias_gyr", "cov_bias_acc", "mean_acc")
 
 
@@ -553,6 +588,15 @@ SIGNATURES = {
     "livo_std_candidates": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "livo_std_matches": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "livo_std_info_get": (C.c_int, [_P, C.POINTER(StdInfo)]),
+    "livo_std_gen_params_default": (C.c_int, [C.POINTER(StdGenParams)]),
+    "livo_std_key_add": (C.c_int, [_P, C.c_int32]),
+    "livo_std_key_add_host": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
+    "livo_std_key_clear": (C.c_int, [_P]),
+    "livo_std_key_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "livo_std_generate": (C.c_int, [_P, C.POINTER(StdGenParams), C.POINTER(StdGenStats)]),
+    "livo_std_staged": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64), _P, C.c_int64, C.POINTER(C.c_int64), _P,
+                                  C.c_int64, C.POINTER(C.c_int64)]),
+    "livo_std_gen_debug": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64), _P, C.c_int64, C.POINTER(C.c_int64)]),
     "livo_std_dump": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _P, C.c_int64,
                                 C.POINTER(C.c_int64)]),
     "livo_sync": (C.c_int, [_P]),
@@ -1476,6 +1520,56 @@ class Context:
                                                       C.byref(nd), frame, _ptr(planes) if planes.size else None,
                                                       planes.size, C.byref(npl)))
         return descs, planes
+
+    def std_key_add(self, scan_id: int = CLOUD_WORLD):
+        """Appends a resident cloud (the published world cloud by default) to the key cloud, device to device."""
+        _check("livo_std_key_add", self._L.livo_std_key_add(self.h, scan_id))
+
+    def std_key_add_host(self, xyz: np.ndarray):
+        """Appends host points (n x 3 or wider rows, float32; the first three columns) to the key cloud."""
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        xyz = xyz.reshape(-1, xyz.shape[-1] if xyz.ndim > 1 else 3)
+        _check("livo_std_key_add_host", self._L.livo_std_key_add_host(self.h, _ptr(xyz) if xyz.size else None, xyz.shape[0],
+                                                                      xyz.shape[1] * 4))
+
+    def std_key_clear(self):
+        _check("livo_std_key_clear", self._L.livo_std_key_clear(self.h))
+
+    def std_key_count(self) -> int:
+        n = C.c_int64()
+        _check("livo_std_key_count", self._L.livo_std_key_count(self.h, C.byref(n)))
+        return int(n.value)
+
+    def std_generate(self, params: StdGenParams | None = None) -> dict:
+        """GenerateSTDescs of the key cloud; its products become the staged frame.  -> the stages' counts."""
+        st = StdGenStats()
+        _check("livo_std_generate", self._L.livo_std_generate(self.h, C.byref(params or std_gen_params()), C.byref(st)))
+        return _stats_dict(st)
+
+    def std_staged(self):
+        """-> the staged frame's descriptors, plane cloud and final corner list (STD_CORNER_DTYPE)."""
+        nd, npl, nc = C.c_int64(), C.c_int64(), C.c_int64()
+        _check("livo_std_staged", self._L.livo_std_staged(self.h, None, 0, C.byref(nd), None, 0, C.byref(npl), None, 0,
+                                                          C.byref(nc)))
+        descs = np.zeros(nd.value, STD_DESC_DTYPE)
+        planes = np.zeros(npl.value, STD_PLANE_DTYPE)
+        corners = np.zeros(nc.value, STD_CORNER_DTYPE)
+        _check("livo_std_staged", self._L.livo_std_staged(
+            self.h, _ptr(descs) if descs.size else None, descs.size, C.byref(nd), _ptr(planes) if planes.size else None,
+            planes.size, C.byref(npl), _ptr(corners) if corners.size else None, corners.size, C.byref(nc)))
+        return descs, planes, corners
+
+    def std_gen_debug(self):
+        """The last generate's voxels (visiting order: first point, count, plane flag) and jobs (voxel rank, plane
+        voxel rank, projected points, 27 member ranks + 1)."""
+        nv, nj = C.c_int64(), C.c_int64()
+        _check("livo_std_gen_debug", self._L.livo_std_gen_debug(self.h, None, 0, C.byref(nv), None, 0, C.byref(nj)))
+        vox = np.zeros((nv.value, 3), np.int32)
+        jobs = np.zeros((nj.value, 30), np.int32)
+        _check("livo_std_gen_debug", self._L.livo_std_gen_debug(self.h, _ptr(vox) if vox.size else None, nv.value,
+                                                                C.byref(nv), _ptr(jobs) if jobs.size else None, nj.value,
+                                                                C.byref(nj)))
+        return vox, jobs
 
     def scan_inherit_neighbors(self, dst: int, src: int):
         _check("livo_scan_inherit_neighbors", self._L.livo_scan_inherit_neighbors(self.h, dst, src))

@@ -34,7 +34,8 @@
  *   livo_vmap_*         ← feat_map, imgs_ and the features' T_f_w_ (the resident visual map)
  *   livo_vio_match      ← LidarSelector::addFromSparseMap (the visual map matched into a frame)
  *                                                   src/lidar_selection.cpp:117-221
- *   livo_std_*          ← STDescManager::SearchLoop / AddSTDescs (the loop search)
+ *   livo_std_*          ← STDescManager::SearchLoop / AddSTDescs (the loop search) and
+ *                         GenerateSTDescs (livo_std_key_*, livo_std_generate)
  *                                                   include/STD/STDesc.cpp:299-374, 960-1280
  *
  * Conventions
@@ -1095,8 +1096,8 @@ int livo_lio_frame(livo_ctx* ctx, const livo_imu_job* job, const livo_imu_params
  *   STDescManager::SearchLoop            :299-353
  *     candidate_selector :960-1099, candidate_verify :1102-1192, triangle_solver :1194-1219,
  *     plane_geometric_verify :1221-1280
- * GenerateSTDescs stays on the host (its corner_extractor walks an unordered_map in iteration
- * order); its products, the key frame's descriptors and plane cloud, are what livo_std_stage takes.
+ * GenerateSTDescs' products, the key frame's descriptors and plane cloud, are what livo_std_stage
+ * takes; livo_std_generate (below) makes them on the device from the resident key cloud.
  * ------------------------------------------------------------------------ */
 #define LIVO_STD_MAX_FRAMES 20000    /* MAX_FRAME_N (STDesc.h): the reference's vote array */
 #define LIVO_STD_MAX_CANDIDATES 64   /* candidate_num beyond it is refused (the reference's default: 50) */
@@ -1178,6 +1179,96 @@ int livo_std_info_get(livo_ctx* ctx, livo_std_info* info);
  * `frame` (frame < 0 or planes NULL with n_planes NULL: skipped).  LIVO_E_RANGE: a cap too small. */
 int livo_std_dump(livo_ctx* ctx, livo_std_desc* descs, int64_t desc_cap, int64_t* n_descs, int32_t frame,
                   livo_std_plane* planes, int64_t plane_cap, int64_t* n_planes);
+
+/* ------------------------------------------------------------------------
+ * A key frame's descriptors on the device: STDescManager::GenerateSTDescs (STDesc.cpp:264-297)
+ *   init_voxel_map :376-422, init_plane :1367-1409, getPlane :492-507, build_connection :424-490,
+ *   corner_extractor :509-617, extract_corner :619-781, non_maxi_suppression :783-822,
+ *   build_stdesc :824-958
+ * over the key cloud, the frames of the world cloud a key frame is made of
+ * (laser_mapping.cpp:1239-1248).  Where the reference's result is implementation-defined the port
+ * pins it: voxels are visited in order of first appearance in the key cloud; a
+ * plane's normal has its component of largest magnitude positive (the first of equal ones); the
+ * maximum_corner_num cut orders by attached count descending, then by index in the suppressed
+ * list; build_stdesc visits only the neighbours that exist, ordered by (distance, index).
+ * ------------------------------------------------------------------------ */
+#define LIVO_STD_GEN_MAX_IMAGE 80    /* the side of extract_corner's projection image the kernel holds */
+#define LIVO_STD_GEN_MAX_NEAR 64     /* descriptor_near_num beyond it is refused */
+
+typedef struct livo_std_gen_params { /* read_parameters' defaults (:57-81) */
+    double  voxel_size;                  /* 2.0 */
+    double  plane_detection_thre;        /* 0.01 */
+    double  plane_merge_normal_thre;     /* 0.1 */
+    double  proj_image_resolution;       /* 0.5 */
+    double  proj_dis_min;                /* 0 */
+    double  proj_dis_max;                /* 2 */
+    double  corner_thre;                 /* 10 */
+    double  non_max_suppression_radius;  /* 2.0 */
+    double  descriptor_min_len;          /* 2 */
+    double  descriptor_max_len;          /* 50 */
+    double  std_side_resolution;         /* 0.2 */
+    int32_t voxel_init_num;              /* 10 */
+    int32_t maximum_corner_num;          /* 100 */
+    int32_t descriptor_near_num;         /* 10 */
+    int32_t pad;
+} livo_std_gen_params;
+
+typedef struct livo_std_gen_stats {
+    int64_t points, voxels, plane_voxels, jobs;
+    int64_t corners_raw, corners_suppressed, corners;  /* before suppression, after it, after the cut */
+    int64_t triangles_tried;                           /* the (i, m, n) visited */
+    int64_t descs;
+} livo_std_gen_stats;
+
+typedef struct livo_std_corner {     /* the PointXYZINormal fields build_stdesc reads */
+    float xyz[3];
+    float attached;                  /* intensity: the points of the corner's cell */
+    float normal[3];
+    float pad;
+} livo_std_corner;
+
+int livo_std_gen_params_default(livo_std_gen_params* p);
+/* The key cloud: resident, grow-only, x y z floats in world coordinates.  livo_std_key_add appends
+ * a resident cloud device to device; it takes the ids livo_frame_to_world takes (LIVO_CLOUD_WORLD
+ * is the reference's case: the caller vouches that another id's cloud is in world coordinates) and
+ * answers LIVO_E_NOSCAN as that call does.  A resident scan is appended in the order it is stored in,
+ * which is not the order it was uploaded in (the published clouds are stored as published); the
+ * voxel visiting order follows the key cloud's order.  livo_std_key_add_host appends n host points, the next
+ * stride_bytes (>= 12) behind the last; LIVO_E_INVALID for a non-finite one.  LIVO_E_RANGE: more
+ * than 2^31 - 1 - 1024 points. */
+int livo_std_key_add(livo_ctx* ctx, int32_t scan_id);
+int livo_std_key_add_host(livo_ctx* ctx, const float* xyz, int64_t n, int64_t stride_bytes);
+int livo_std_key_clear(livo_ctx* ctx);
+int livo_std_key_count(livo_ctx* ctx, int64_t* n);
+/* GenerateSTDescs of the key cloud.  Its products become the staged frame, the state
+ * livo_std_stage leaves, with frame_id = the number of committed frames; the key cloud is cleared
+ * (laser_mapping.cpp:1249).  An empty cloud, or one without planes, stages zero descriptors.  Two
+ * calls on the same input give the same bytes.  stats may be NULL.
+ * Found before the context is read: LIVO_E_INVALID: a NULL argument, a non-finite or negative
+ * threshold, voxel_size, proj_image_resolution or std_side_resolution not > 0, voxel_init_num < 0,
+ * maximum_corner_num < 1, descriptor_near_num outside [3, LIVO_STD_GEN_MAX_NEAR]; LIVO_E_RANGE:
+ * voxel_size * sqrt(17) >= 10 (extract_corner's box starts at +-10 and a point of the 27 voxels
+ * round V lies up to sqrt(17) edges from the connected plane's centre), an image side
+ * (int)(2 * voxel_size * sqrt(17) / proj_image_resolution + 5) > LIVO_STD_GEN_MAX_IMAGE,
+ * descriptor_max_len * 1000 >= 2^21 - 1 or descriptor_max_len / std_side_resolution >= 2^20 - 2
+ * (the packed keys).  Then LIVO_E_INVALID: no livo_std_reset, a non-finite point of a cloud added
+ * on the device; LIVO_E_RANGE: a voxel coordinate beyond +-(2^20 - 2).  A refused call leaves the
+ * key cloud and the staged frame as they were (but for the staged frame's corner list, which the
+ * device-side refusals drop). */
+int livo_std_generate(livo_ctx* ctx, const livo_std_gen_params* params, livo_std_gen_stats* stats);
+/* The staged frame read back: descriptors, plane cloud and, behind a livo_std_generate, the final
+ * corner list (0 behind a livo_std_stage).  Each of the three: NULL with its count pointer set
+ * gives the count only; LIVO_E_RANGE: a cap too small.  LIVO_E_INVALID: nothing staged. */
+int livo_std_staged(livo_ctx* ctx, livo_std_desc* descs, int64_t desc_cap, int64_t* n_descs, livo_std_plane* planes,
+                    int64_t plane_cap, int64_t* n_planes, livo_std_corner* corners, int64_t corner_cap,
+                    int64_t* n_corners);
+/* For tests only (no caller of the reference's interface needs it; it may change): diagnostics of the
+ * last livo_std_generate, in the order the stages made them: per voxel in
+ * visiting order its first point's index, point count and plane flag (3 x voxels), and per job
+ * its voxel's visiting rank, its direction's plane voxel's rank, the points projected and the 27
+ * member ranks + 1 (30 x jobs).  NULL with the count pointer set gives the counts. */
+int livo_std_gen_debug(livo_ctx* ctx, int32_t* voxels, int64_t voxel_cap, int64_t* n_voxels, int32_t* jobs,
+                       int64_t job_cap, int64_t* n_jobs);
 
 int livo_sync(livo_ctx* ctx);
 /* Diagnostics: the incremental map's grid rebuilds since the context was made,
